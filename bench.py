@@ -15,11 +15,14 @@ of N x 312.5 Mbp (30x; at N = 8 exactly configs[2]: 500 M reads, 2.5 Gbp), reads
 rank, the k-mer shuffle an RCCL all_to_all_v, dictionary / prune / unipaths sharded by bucket owner (row e-3), pathing local -- weak scaling.
 
 Prints ONE JSON line (rank 0).  `value` = job-wide canonical k-mer instances per second over
-the whole step; the phase rates, the roofline object of the dominant kernel, the count-phase
-fraction of BASELINE.md section 3, the host-resident (PCIe-inclusive) rate of the one-shot C
-entry point, a second workload with planted repeats and a second haplotype, and the CPU
-baseline (the real reference's Step 2, oracle/_ref, timed on this box's host cores on a
-bounded sample) are carried alongside.
+the whole step; the phase rates, the roofline object of the dominant kernel and the count-phase
+fraction of BASELINE.md section 3 are carried alongside.  A plain run does nothing else: set-up,
+warm-up, the timed steps, the line.  With --full it also carries what takes runs of its own: the
+dominant kernel without overlap, the device copy rate, the host-resident (PCIe-inclusive) rate of
+the one-shot C entry point, a second workload with planted repeats and a second haplotype, the
+CPU baseline (the real reference's Step 2, oracle/_ref, timed on this box's host cores on a
+bounded sample) with its parity verdicts, the extras of the other steps, and on several GPUs the
+self-check of the ranks.  --dump-outputs DIR writes the last timed step's result as .npy files.
 """
 import argparse
 import json
@@ -111,6 +114,31 @@ def with_copy_rate(roofline, dev):
         roofline["measured_copy_GBs"] = None
         roofline["measured_copy_error"] = str(e)[:200]
     return roofline
+
+
+DUMP_SAMPLE = 1 << 18          # --dump-outputs: elements kept of a longer array (18 arrays x 2 MB of float64 at most: under 64 MB)
+DUMP_SEED = 20260
+
+
+def dump_outputs(out_dir, res):
+    """Step2Result -> out_dir/<name>.npy, float64 (every value is an integer below 2^53, so exact).  An array longer than DUMP_SAMPLE is
+    cut to the elements at DUMP_SAMPLE positions drawn with a fixed seed from its length: the same result gives the same files."""
+    h = res.hbv
+    arrays = {"hbv_from_off": h.from_off, "hbv_from_v": h.from_v, "hbv_from_e": h.from_e, "hbv_to_off": h.to_off, "hbv_to_e": h.to_e,
+              "hbv_edge_packed": h.edge_packed, "hbv_edge_byte_off": h.edge_byte_off, "hbv_edge_len": h.edge_len,
+              "vleft": res.vleft, "vright": res.vright, "to_v": res.to_v, "fwd_xlat": res.fwd_xlat, "rev_xlat": res.rev_xlat,
+              "path_offset": res.path_offset, "path_off": res.path_off, "path_edges": res.path_edges, "hist": res.hist,
+              "counts": np.array([res.n_kmer_instances, res.n_kmers_distinct, res.n_kmers_solid, res.n_reads_pathed, res.n_reads_multipathed])}
+    os.makedirs(out_dir, exist_ok=True)
+    total = 0
+    for name, x in arrays.items():
+        x = np.asarray(x).reshape(-1)
+        if len(x) > DUMP_SAMPLE:
+            x = x[np.sort(np.random.default_rng(DUMP_SEED).choice(len(x), DUMP_SAMPLE, replace=False))]
+        x = x.astype(np.float64)
+        np.save(os.path.join(out_dir, name + ".npy"), x)
+        total += x.nbytes
+    assert total <= 64 << 20, total
 
 
 def cpu_baseline(n_reads, genome_len, seed, dev, planted=False):
@@ -303,7 +331,7 @@ def main_step3(a, extra=False):
     if extra:
         ctx.close(); del d; torch.cuda.empty_cache()
         return result
-    if not a.no_cpu_baseline:
+    if a.full and not a.no_cpu_baseline:
         # the REAL reference's Step 3 (oracle/_ref/ref_step3) on the host cores, on the Step-2 output of a bounded sample of the same workload
         from oracle import oracle3 as O3
         ctx.close(); del d; torch.cuda.empty_cache()
@@ -331,7 +359,8 @@ def main_step3(a, extra=False):
         result["cpu_baseline"] = {"value": s3.n_kmer_instances / secs, "unit": "K2-mers/s", "cores": cores, "kind": kind, "seconds": secs,
                                   "sample": f"Step-2 output of {dc['n']} reads of the same workload ({s3.n_kmer_instances} K2-mer occurrences); includes reading "
                                             f".small_K.hbv/.paths and writing .large_K.hbv/.paths", "reads_per_s": dc["n"] / secs}
-    with_copy_rate(result["roofline"], dev)
+    if a.full:
+        with_copy_rate(result["roofline"], dev)
     emit(json.dumps(result))
 
 
@@ -455,7 +484,7 @@ def main_step1(a, extra=False):
     if extra:
         ctx.close(); del t1, t2; torch.cuda.empty_cache()
         return result
-    if not a.no_cpu_baseline and world == 1:
+    if a.full and not a.no_cpu_baseline and world == 1:
         # the REAL reference's Step 1 (oracle/_ref/ref_step1: ExtractReads + WriteAll) on the host cores, on the first records of the same texts
         from oracle import oracle1 as O1
         n_cpu = min(int(a.cpu_reads) & ~1, n)
@@ -474,7 +503,8 @@ def main_step1(a, extra=False):
             cores, kind = 1, "port"
         result["cpu_baseline"] = {"value": n_cpu / secs, "unit": "reads/s", "cores": cores, "kind": kind, "seconds": secs,
                                   "sample": f"the first {n_cpu} reads of the same two fastq texts, read from files in a temporary directory (time inside ExtractReads)"}
-    with_copy_rate(result["roofline"], dev)
+    if a.full:
+        with_copy_rate(result["roofline"], dev)
     emit(json.dumps(result))
 
 
@@ -528,7 +558,7 @@ def main_pipeline(a, extra=False):
     if extra:
         ctx.close(); del t1, t2; torch.cuda.empty_cache()
         return result
-    if not a.no_cpu_baseline:
+    if a.full and not a.no_cpu_baseline:
         # the REAL reference's Steps 1, 2 and 3 (oracle/_ref) on the host cores, on the first records of the same texts, through its files
         from oracle import oracle as O, oracle1 as O1, oracle3 as O3
         n_cpu = min(int(a.cpu_reads) & ~1, n)
@@ -594,7 +624,7 @@ def main_gfa(a, extra=False):
     }
     if extra:
         return result
-    if not a.no_cpu_baseline:
+    if a.full and not a.no_cpu_baseline:
         # the REAL reference's hbv2gfa (oracle/_ref/ref_hbv2gfa) on the same graph, files in a temporary directory
         from oracle import oracle_gfa as OG
         if os.path.exists(OG.REF_GFA_BIN):
@@ -607,7 +637,8 @@ def main_gfa(a, extra=False):
             same = gfa.gfa_dump(h).gfa == ref_text
             result["cpu_baseline"] = {"value": r.canonical_size / secs, "unit": "bases/s", "cores": 1, "kind": "reference", "seconds": secs,
                                       "sample": "the same graph, whole tool run (reads .hbv, writes _raw.gfa)", "same_text_as_gpu": bool(same)}
-    with_copy_rate(result["roofline"], dev)
+    if a.full:
+        with_copy_rate(result["roofline"], dev)
     emit(json.dumps(result))
 
 
@@ -629,7 +660,15 @@ def main():
     ap.add_argument("--gfa", action="store_true", help="measure the GFA dump of the Step-2 graph (SURVEY 8f N4) instead: its own JSON line")
     ap.add_argument("--K2", type=int, default=200)
     ap.add_argument("--snp-every", type=int, default=2000, help="--step3: second haplotype with one SNP per this many bases (SURVEY 8d diploid variant)")
+    ap.add_argument("--full", action="store_true", help="also everything beside the headline figure: CPU baselines and their parity verdicts, the extras, "
+                                                        "the multi-GPU self-check, the kernel alone without overlap, the device copy rate")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last one computed (the Step-2 result a caller fetches) "
+                                                          "as DIR/<name>.npy, float64, larger arrays as a fixed seeded sample")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if a.dump_outputs and (a.step3 or a.step1 or a.gfa or a.pipeline):
+        ap.error("--dump-outputs writes the Step-2 result of the default line; it does not apply to --step3 / --step1 / --gfa / --pipeline")
     guard_stdout()
     if a.step3:
         return main_step3(a)
@@ -748,10 +787,12 @@ def main():
         p = torch.tensor([sizes["reads_pathed"], sizes["path_elements"]], dtype=torch.int64, device=dev)
         dist.all_reduce(p)
         sizes["reads_pathed"], sizes["path_elements"] = int(p[0].item()), int(p[1].item())
-    # ---- the first run on several GPUs validates itself: who took part, do all ranks hold the same graph, is it the
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, ctx.fetch())
+    # ---- (--full) a run on several GPUs validates itself: who took part, do all ranks hold the same graph, is it the
     #      graph ONE rank builds from the same reads (a 2 M-read subsample: every rank's first reads, gathered on rank 0 and run there alone)
     selfcheck = None
-    if use_dist:
+    if use_dist and a.full:
         import hashlib
         res_g = ctx.fetch()
         hb = F.hbv_to_bytes(res_g.hbv)
@@ -853,12 +894,12 @@ def main():
                         "same_launch_count": pk.get("launches") == per_step_launches,
                         "ms_ratio_run_over_profile": (avg_ms * per_step_launches / pk["ms"]) if pk.get("ms") else None}
         # In the single-GPU step the counting kernel shares the GPU with the dictionary build (k_table_insert runs on a
-        # side stream while the next bucket slice is counted): its launches are longer than on their own.  One extra,
+        # side stream while the next bucket slice is counted): its launches are longer than on their own.  (--full) One extra,
         # untimed step without that overlap gives the kernel's own duration next to the live one.
         alone = None
         # (skipped under rocprofv3, whose per-kernel averages should be those of the timed launches)
         profiled = "rocprof" in os.environ.get("LD_PRELOAD", "") or any(k.startswith("ROCPROF") for k in os.environ)
-        if not use_dist and kname.startswith("k_count") and not profiled:
+        if a.full and not use_dist and kname.startswith("k_count") and not profiled:
             os.environ["W2RAP_NO_OVERLAP"] = "1"
             try:
                 ctx.profile(reset=True)
@@ -908,7 +949,7 @@ def main():
             result["exchanges"] = xinfo.get("exchange_log")
         if selfcheck:
             result.update(selfcheck)                      # top-level keys: rccl_ranks, device_uuids, graph_equal_across_ranks, *_equal_single_rank, model_ms_per_step
-    if rank == 0 and world == 1 and not a.no_extras:
+    if rank == 0 and world == 1 and a.full and not a.no_extras:
         # ---- SURVEY 8d metric (1): reads resident in HOST memory -> the one-shot C entry point (upload through the pinned staging pump, compute,
         # download of graph and paths).  Untimed extra; the SECOND call is quoted (the first pays the context's device pool once per process).
         ctx.close(); ctx = None
@@ -1014,7 +1055,7 @@ def main():
         except Exception as e:
             result["planted_workload"] = {"error": str(e)[:300]}
         torch.cuda.empty_cache()
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if rank == 0 and world == 1 and a.full and not a.no_cpu_baseline:
         if ctx is not None:
             ctx.close()
         d = None
@@ -1078,7 +1119,7 @@ def main():
                 result["planted_parity_error"] = str(e)[:300]
                 parity_failed = True
             torch.cuda.empty_cache()
-    if rank == 0 and world == 1 and not a.no_extras:
+    if rank == 0 and world == 1 and a.full and not a.no_extras:
         # ---- the "next" rows of SURVEY.md 8f on the same box in the same run (untimed extras like planted_workload: each is its own
         # workload and its own steps; the full lines come from bench.py --step3 / --step1 / --gfa / --pipeline)
         import copy
@@ -1098,7 +1139,7 @@ def main():
             except Exception as ex:
                 extras[name] = {"error": str(ex)[:300]}
         result["extras"] = extras
-    if rank == 0:
+    if rank == 0 and a.full:
         with_copy_rate(result["roofline"], dev)
     emit(json.dumps(result))
     if use_dist:

@@ -78,6 +78,34 @@ def fixture_data(request):
     return load_fixture(request.param)
 
 
+REFRUNS = os.path.join(GOLDEN, "refruns")
+
+
+def reference_outputs(case, workdir, inputs, outputs, run):
+    """A run of a reference binary (oracle/_ref, built from the reference's sources, which the repository does not hold) replayed from
+    tests/golden/refruns/<case>/: the files it wrote (`outputs`, relative to workdir) are put into workdir and its stdout is returned.
+    The inputs it read (`inputs`) must be the recorded ones (SHA-256).  W2RAP_RECORD_REFERENCE=1 (`make_golden.py refruns`) records
+    the case instead by calling run(), which runs the binary in workdir and returns its stdout (or None)."""
+    import hashlib
+    import json
+    import shutil
+    src = os.path.join(REFRUNS, case)
+    digests = {f: hashlib.sha256(open(os.path.join(workdir, f), "rb").read()).hexdigest() for f in inputs}
+    if os.environ.get("W2RAP_RECORD_REFERENCE") == "1":
+        out = run()
+        os.makedirs(src, exist_ok=True)
+        for f in outputs:
+            shutil.copy(os.path.join(workdir, f), os.path.join(src, os.path.basename(f)))
+        with open(os.path.join(src, "run.json"), "w") as fh:
+            json.dump({"inputs_sha256": digests, "stdout": out if isinstance(out, str) else None}, fh, indent=1)
+    with open(os.path.join(src, "run.json")) as fh:
+        rec = json.load(fh)
+    assert rec["inputs_sha256"] == digests, f"{case}: the inputs are not the ones the reference run was recorded on"
+    for f in outputs:
+        shutil.copy(os.path.join(src, os.path.basename(f)), os.path.join(workdir, f))
+    return rec["stdout"]
+
+
 def golden_bytes(name, tag, ext):
     with open(os.path.join(GOLDEN, f"{name}.{tag}.{ext}"), "rb") as f:
         return f.read()

@@ -16,7 +16,8 @@ and, from the REAL reference Step 3 (oracle/_ref/ref_step3, K2 = 200) run on tho
 and, for Step 1 (fastq ingest), step1_r1.fastq / step1_r2.fastq with the REAL reference's frag_reads_orig.fastb/.qualp for them
 (step1.ref.fastb / step1.ref.qualp, from oracle/_ref/ref_step1; `make_golden.py step1`).
 and, from the REAL reference hbv2gfa tool (oracle/_ref/ref_hbv2gfa -g 20; `make_golden.py gfa`), for the graphs named in GFA_GOLDENS
-    <graph>.ref_raw.gfa and <graph>.ref_gfa_stats.txt (its stdout between "=== Graph stats === " and "Dumping gfa").
+    <graph>.ref_raw.gfa and <graph>.ref_gfa_stats.txt (its stdout between "=== Graph stats === " and "Dumping gfa"),
+and (`make_golden.py refruns`) refruns/<case>/: the files and stdout of every reference run the tests make, with the SHA-256 of its inputs.
 All of these are data (inputs and expected outputs); no reference source is stored.
 """
 import os
@@ -116,8 +117,22 @@ def gfa_goldens():
         open(os.path.join(HERE, g + ".ref_gfa_stats.txt"), "w").write(txt.split("=== Graph stats === \n")[1].split("Dumping gfa")[0])
 
 
+# the tests whose reference runs are replayed from refruns/<case>/ (conftest.reference_outputs)
+REFRUN_TESTS = ("tests/test_step3_consumer.py", "tests/test_step3_oracle.py", "tests/test_gfa_oracle.py", "tests/test_step1_oracle.py")
+
+
+def refruns():
+    """runs those tests with W2RAP_RECORD_REFERENCE=1: every reference run they make is done live and recorded"""
+    import subprocess
+    shutil.rmtree(os.path.join(HERE, "refruns"), ignore_errors=True)
+    subprocess.check_call([sys.executable, "-m", "pytest", "-q", "-m", "not gpu", *REFRUN_TESTS], cwd=ROOT,
+                          env=dict(os.environ, W2RAP_RECORD_REFERENCE="1"))
+
+
 def main():
     O.build(ref=True)
+    if len(sys.argv) > 1 and sys.argv[1] == "refruns":
+        return refruns()
     if len(sys.argv) > 1 and sys.argv[1] == "gfa":
         return gfa_goldens()
     if len(sys.argv) > 1 and sys.argv[1] == "step1":

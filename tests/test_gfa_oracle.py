@@ -6,7 +6,7 @@ import shutil
 import numpy as np
 import pytest
 
-from conftest import GOLDEN
+from conftest import GOLDEN, reference_outputs
 from w2rap_contigger_amd import formats as F
 from oracle import oracle_gfa as OG
 
@@ -26,12 +26,13 @@ def test_gfa_oracle_involution_is_an_involution():
     assert np.array_equal(inv[inv], np.arange(h.n_edges)) and np.array_equal(h.edge_len[inv], h.edge_len)
 
 
-@pytest.mark.skipif(not os.path.exists(OG.REF_GFA_BIN), reason="needs the reference build (oracle/_ref)")
 @pytest.mark.parametrize("g", ("random20k.ref8", "random20k.ref.large_K", "palindrome_circle.ref8.large_K"))
 def test_gfa_oracle_against_the_reference_binary(g, tmp_path):
     shutil.copy(os.path.join(GOLDEN, g + ".hbv"), tmp_path / "g.hbv")
     shutil.copy(os.path.join(GOLDEN, g + ".paths"), tmp_path / "g.paths")
-    txt, gfa = OG.run_reference_gfa(str(tmp_path), "g", "o", 5)
+    txt = reference_outputs(f"hbv2gfa_{g}_g5", str(tmp_path), ["g.hbv", "g.paths"], ["o_raw.gfa"],
+                            lambda: OG.run_reference_gfa(str(tmp_path), "g", "o", 5)[0])
+    gfa = open(tmp_path / "o_raw.gfa", "rb").read()
     h = F.read_hbv(os.path.join(GOLDEN, g + ".hbv"))
     assert OG.raw_gfa(h) == gfa
     assert OG.stats_text(h, 5000) == txt.split("=== Graph stats === \n")[1].split("Dumping gfa")[0]

@@ -385,7 +385,7 @@ def test_bench_distributed_code_path_on_one_gpu(mods):
     def run(extra_env, launcher):
         env = dict(os.environ, **extra_env)
         cmd = launcher + [os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "0", "--reads", "5e7",
-                          "--no-cpu-baseline"]
+                          "--no-cpu-baseline", "--full"]
         out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
         assert out.returncode == 0, out.stderr[-2000:]
         return json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
@@ -409,7 +409,7 @@ def test_bench_with_two_ranks_sharing_the_gpu(mods):
     def run(extra_env, launcher, gpus, reads, genome):
         env = dict(os.environ, **extra_env)
         cmd = launcher + [os.path.join(ROOT, "bench.py"), "--gpus", str(gpus), "--steps", "1", "--warmup", "1", "--reads", str(reads), "--genome", str(genome),
-                          "--no-cpu-baseline", "--no-extras"]
+                          "--no-cpu-baseline", "--no-extras", "--full"]
         out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
         assert out.returncode == 0, out.stderr[-3000:]
         return json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])

@@ -5,7 +5,7 @@ import os
 import numpy as np
 import pytest
 
-from conftest import GOLDEN
+from conftest import GOLDEN, reference_outputs
 from w2rap_contigger_amd import formats as F
 from oracle import oracle1 as O1
 
@@ -85,7 +85,6 @@ def test_oracle1_one_interleaved_file_gives_the_pairs_files(tmp_path):
         O1.run_files([b"@a/1\nA\n+\nI\n", b"@a/2\nA\n+\nI\n", b"@a 3\nA\n+\nI\n"])
 
 
-@pytest.mark.skipif(not os.path.exists(O1.REF1_BIN), reason="needs the reference build (oracle/_ref)")
 def test_oracle1_file_grouping_against_the_reference_binary(tmp_path):
     """which files pair up is decided by their first read names (ExtractReads.cc:218-258): same name -> a pair in the order given; a file
     whose name nobody shares is read on its own; groups come out sorted by name -- the real reference on the same files"""
@@ -105,7 +104,8 @@ def test_oracle1_file_grouping_against_the_reference_binary(tmp_path):
         d.mkdir()
         for fn, text in files:
             open(d / fn, "wb").write(text)
-        O1.run_reference1(str(d), ",".join(str(d / fn) for fn, _ in files))
+        reference_outputs(f"step1_grouping_{name}", str(d), [fn for fn, _ in files], ["frag_reads_orig.fastb", "frag_reads_orig.qualp"],
+                          lambda: O1.run_reference1(str(d), ",".join(str(d / fn) for fn, _ in files)))
         r = O1.run_files([t for _, t in files])
         F.write_fastb(d / "o.fastb", r["packed"], r["byte_off"], r["read_len"])
         F.write_qualp_blobs(d / "o.qualp", r["pq"], r["pq_off"])

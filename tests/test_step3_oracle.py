@@ -7,7 +7,7 @@ import os
 import numpy as np
 import pytest
 
-from conftest import GOLDEN, FIXTURES, relabel_compare
+from conftest import GOLDEN, FIXTURES, reference_outputs, relabel_compare
 from w2rap_contigger_amd import formats as F
 from oracle import oracle as O, oracle3 as O3
 
@@ -64,7 +64,6 @@ def test_oracle3_rejects_a_graph_without_reverse_complements():
         O3.run(h2, (p[0][:0], p[1][:1], p[2][:0]), 200)
 
 
-@pytest.mark.skipif(not os.path.exists(O3.REF3_BIN), reason="oracle/_ref/ref_step3 not built (needs /root/reference once)")
 @pytest.mark.parametrize("K2", [100, 260, 72, 640])
 def test_oracle3_other_large_k_against_the_reference_run_here(K2, tmp_path):
     """the goldens are K2 = 200; other members of the reference's K list are checked against the reference binary itself"""
@@ -73,7 +72,8 @@ def test_oracle3_other_large_k_against_the_reference_run_here(K2, tmp_path):
     d = tmp_path
     shutil.copy(os.path.join(GOLDEN, f"{name}.ref.hbv"), d / "t.small_K.hbv")
     shutil.copy(os.path.join(GOLDEN, f"{name}.ref.paths"), d / "t.small_K.paths")
-    O3.run_reference3(str(d), "t", K2, 1)
+    reference_outputs(f"step3_{name}_K{K2}", str(d), ["t.small_K.hbv", "t.small_K.paths"], ["t.large_K.hbv", "t.large_K.paths"],
+                      lambda: O3.run_reference3(str(d), "t", K2, 1))
     rh = F.read_hbv(d / "t.large_K.hbv")
     hc, ho = O.edge_hint_from_hbv(rh)
     h, p = _small(name, "ref")
@@ -97,14 +97,14 @@ def test_oracle3_extend_paths_replays_the_reference_byte_for_byte():
     assert (len(r0.place_off) - 1, r0.n_instances) == (320, 66813) and r.n_instances == 123670
 
 
-@pytest.mark.skipif(not os.path.exists(O3.REF3_BIN), reason="oracle/_ref/ref_step3 not built (needs /root/reference once)")
 @pytest.mark.parametrize("name,K2", [("repeats_snps", 100), ("palindrome_circle", 200), ("random20k", 260)])
 def test_oracle3_extend_paths_against_the_reference_run_here(name, K2, tmp_path):
     import shutil
     d = tmp_path
     shutil.copy(os.path.join(GOLDEN, f"{name}.ref.hbv"), d / "t.small_K.hbv")
     shutil.copy(os.path.join(GOLDEN, f"{name}.ref.paths"), d / "t.small_K.paths")
-    O3.run_reference3(str(d), "t", K2, 1, extend_paths=True)
+    reference_outputs(f"step3_{name}_K{K2}_extend", str(d), ["t.small_K.hbv", "t.small_K.paths"], ["t.large_K.hbv", "t.large_K.paths"],
+                      lambda: O3.run_reference3(str(d), "t", K2, 1, extend_paths=True))
     rh = F.read_hbv(d / "t.large_K.hbv")
     hc, ho = O.edge_hint_from_hbv(rh)
     h, p = _small(name, "ref")
@@ -113,7 +113,6 @@ def test_oracle3_extend_paths_against_the_reference_run_here(name, K2, tmp_path)
     assert F.hbv_to_bytes(O3.to_hbv(r), zero_padding=True) == F.hbv_to_bytes(rh, zero_padding=True)
 
 
-@pytest.mark.skipif(not os.path.exists(O3.REF3_BIN), reason="oracle/_ref/ref_step3 not built (needs /root/reference once)")
 @pytest.mark.parametrize("K2", [200, 100])
 @pytest.mark.parametrize("name", ["circle", "palindrome", "chains"])
 def test_oracle3_hand_made_cases_against_the_reference_run_here(name, K2, tmp_path):
@@ -123,7 +122,8 @@ def test_oracle3_hand_made_cases_against_the_reference_run_here(name, K2, tmp_pa
     d = tmp_path
     F.write_hbv(d / "t.small_K.hbv", h)
     F.write_paths(d / "t.small_K.paths", *p)
-    O3.run_reference3(str(d), "t", K2, 1)
+    reference_outputs(f"step3_case_{name}_K{K2}", str(d), ["t.small_K.hbv", "t.small_K.paths"], ["t.large_K.hbv", "t.large_K.paths"],
+                      lambda: O3.run_reference3(str(d), "t", K2, 1))
     rh = F.read_hbv(d / "t.large_K.hbv")
     hc, ho = O.edge_hint_from_hbv(rh)
     r = O3.run(h, p, K2, hc, ho)

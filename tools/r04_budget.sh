@@ -3,7 +3,7 @@
 rm -f gpurun_out/r04_budget.txt
 for b in 12 10 8 6; do
   echo "== W2RAP_PATH_BUDGET=$b uniform" >> gpurun_out/r04_budget.txt
-  W2RAP_PATH_BUDGET=$b timeout 600 python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-extras 2>/dev/null | python -c "
+  W2RAP_PATH_BUDGET=$b timeout 600 python bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-extras 2>/dev/null | python -c "
 import json,sys
 r=json.loads(sys.stdin.readline()); k=r['kernel_ms_per_step']
 print('step', round(r['ms_per_step'],1), 'path phase', round(r['phase_ms']['path'],2), {x: round(v,2) for x,v in k.items() if 'path' in x})" >> gpurun_out/r04_budget.txt
