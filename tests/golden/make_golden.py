@@ -39,10 +39,21 @@ FIXTURES = {
     "random20k": ("random", 11, 2000, 101, True),
     "repeats_snps": ("repeats_snps", 12, 6000, 102, False),
     "palindrome_circle": ("palindrome_circle", 13, 2300, 103, False),
+    "long_mixed": ("long_mixed", 0, 0, 0, False),               # (long_mixed_inputs; not in conftest.FIXTURES: its tests name it)
 }
 
 
+def long_mixed_inputs():
+    """PE250 on a small diploid genome (repeats, SNPs, a stretch of dense SNPs, short-period tandem arrays) plus 40 reads of 300 to
+    3,000 bases and two of ~20 k from the same genome: the oracle pinned on reads far longer than PE150 / 251 (`make_golden.py long_mixed`)"""
+    contigs = synth.diploid_genome(24_000, 21, snp_every=300, dense=(3_000, 6_000, 70), tandem=((9_000, 6, 600), (15_000, 13, 800)))
+    extra = list(np.random.default_rng(22).integers(300, 3_001, 40)) + [20_000, 19_500]
+    return synth.read_length_workload(contigs, 1_500, 23, read_len=250, insert=500, extra_lengths=extra)
+
+
 def make_inputs(kind, gseed, n_pairs, rseed, edge_cases):
+    if kind == "long_mixed":
+        return long_mixed_inputs()
     contigs = synth.fixture_genome(kind, gseed)
     codes, quals = synth.sample_reads(contigs, n_pairs, rseed)
     codes, quals = codes.numpy(), quals.numpy()
@@ -141,8 +152,11 @@ def main():
         for name in FIXTURES:
             step3_goldens(name)
         return
-    for name, spec in FIXTURES.items():
-        codes, quals, off = make_inputs(*spec)
+    names = list(FIXTURES)
+    if len(sys.argv) > 1 and sys.argv[1] in FIXTURES:           # one fixture only
+        names = [sys.argv[1]]
+    for name in names:
+        codes, quals, off = make_inputs(*FIXTURES[name])
         fastb, qualp = os.path.join(HERE, name + ".fastb"), os.path.join(HERE, name + ".qualp")
         F.write_fastb(fastb, *F.pack_bases(codes, off))
         F.write_qualp(qualp, quals, off)

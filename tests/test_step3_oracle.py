@@ -21,7 +21,7 @@ def _large(name, tag):
 
 
 @pytest.mark.parametrize("tag", ["ref", "ref8"])
-@pytest.mark.parametrize("name", FIXTURES)
+@pytest.mark.parametrize("name", FIXTURES + ["long_mixed"])          # (long_mixed: reads of up to 20 k bases, tests/golden/make_golden.py)
 def test_oracle3_replays_the_reference_byte_for_byte(name, tag):
     h, p = _small(name, tag)
     rh, rp = _large(name, tag)

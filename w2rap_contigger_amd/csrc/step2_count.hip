@@ -203,6 +203,7 @@ __global__ void __launch_bounds__(256, MINW) k_superkmers(uint64_t n, uint32_t c
                                                     uint32_t* __restrict__ bcount /* [pb_hi - pb_lo] */,
                                                     uint32_t nbl_part, uint32_t inv_nbl, unsigned long long* __restrict__ part_kmers,
                                                     uint2* __restrict__ s_desc, uint32_t spp, uint32_t npass,
+                                                    const uint64_t* __restrict__ pass_off /* [n + 1]: read r's passes start at pass_off[r] */,
                                                     uint32_t* __restrict__ o_read, uint32_t* __restrict__ o_bkt, uint32_t* __restrict__ o_meta,
                                                     uint32_t* __restrict__ o_rank,
                                                     uint64_t ov_cap, unsigned long long* __restrict__ ov_cursor /*[0] entries*/) {
@@ -243,10 +244,7 @@ __global__ void __launch_bounds__(256, MINW) k_superkmers(uint64_t n, uint32_t c
         win_c = 0;
         if (r + stride < r_end && lane < 16 && gl_n > K) win_c = win_load(off_n, (gl_n + 3) >> 2);
         gl_c = gl_n; off_c = off_n; gl_n = gl_nn; off_n = off_nn;
-        if (gl <= K) {                                           // strict, BuildReadQGraph.cc:1064: no records, empty slots
-            for (unsigned i = lane; i < spp * npass; i += 64) s_desc[r * npass * spp + i] = make_uint2(0u, NONE32);
-            continue;
-        }
+        if (gl <= K) continue;                                   // strict, BuildReadQGraph.cc:1064: no records, no passes, no slots
         const unsigned nk_total = gl - (K - 1);
         const unsigned nbytes_read = (gl + 3) >> 2;
         for (unsigned c0 = 0; c0 < nk_total; c0 += 128) {
@@ -346,7 +344,7 @@ __global__ void __launch_bounds__(256, MINW) k_superkmers(uint64_t n, uint32_t c
                 sth[h] = start && mine; bkh[h] = bkt - pb_lo; nkh[h] = start ? nxt - lane : 0;
             }
             unsigned cnt = 0;
-            const uint64_t slot0 = (r * npass + c0 / 128) * spp;
+            const uint64_t slot0 = (pass_off[r] + c0 / 128) * spp;
             // the histogram atomic RETURNS the record's rank inside its bucket: it travels in the descriptor (16 bits; the rare
             // bucket that gets more than 65535 records from these reads sends the surplus through the overflow list), so the
             // scatter pass needs no atomic of its own.  Both halves' atomics are in flight before either result is used.
@@ -383,8 +381,6 @@ __global__ void __launch_bounds__(256, MINW) k_superkmers(uint64_t n, uint32_t c
             for (unsigned i = lane; i < spp; i += 64) s_desc[slot0 + i] = i < cnt ? dbuf[i] : make_uint2(0u, NONE32);
             wave_lds_fence();
         }
-        // passes this read does not have (shorter than the longest read)
-        for (unsigned i = ((nk_total + 127) / 128) * spp + lane; i < spp * npass; i += 64) s_desc[r * npass * spp + i] = make_uint2(0u, NONE32);
     }
     if (part_kmers) {
         wave_lds_fence();
@@ -568,7 +564,12 @@ __global__ void __launch_bounds__(256, 4) k_superkmers_lane(uint64_t n, const ui
 // One thread per descriptor slot (then per overflow entry): the record's place is its bucket's base + the rank K1's
 // histogram atomic returned; cut the 2*(nk+61) stream bits [left flank][k-mers' bases][right flank] out of the read
 // (unaligned 8-byte loads), store the 32-B record.  No atomics.
-__global__ void __launch_bounds__(256) k_scatter_records(uint64_t nslots, uint32_t slots_per_read, const uint2* __restrict__ s_desc,
+// (PASS_OFF: the wavefront kernel's layout, spp slots per pass a read has -- slots_per_read is spp, pass_off[nreads + 1] the reads' first passes)
+// (its binary search costs ~log2(nreads) dependent loads per slot; it runs only where the longest read passes 315 bases or W2RAP_K1=wave,
+// never on the PE150 lane route, and its cost on long-read inputs has not been measured)
+template <bool PASS_OFF>
+__global__ void __launch_bounds__(256) k_scatter_records(uint64_t nslots, uint32_t slots_per_read, const uint64_t* __restrict__ pass_off, uint64_t nreads,
+                                                          const uint2* __restrict__ s_desc,
                                                           uint64_t nov, const uint32_t* __restrict__ o_read,
                                                           const uint32_t* __restrict__ o_bkt, const uint32_t* __restrict__ o_meta,
                                                           const uint32_t* __restrict__ o_rank,
@@ -586,7 +587,12 @@ __global__ void __launch_bounds__(256) k_scatter_records(uint64_t nslots, uint32
     if (i < nslots) {
         const uint2 d = s_desc[i];
         if (d.y != NONE32) { meta = d.y & 0xFFFFFFu; b = d.x & 0xFFFFFFu; slot = (d.x >> 24) | ((d.y >> 24) << 8); }
-        r = (uint32_t)(i / slots_per_read);
+        if (PASS_OFF) {                                          // the read whose passes hold pass i / spp: pass_off[lo] <= pass < pass_off[hi]
+            const uint64_t ps = i / slots_per_read;
+            uint64_t lo = 0, hi = nreads;
+            while (hi - lo > 1) { const uint64_t mid = (lo + hi) >> 1; if (pass_off[mid] <= ps) lo = mid; else hi = mid; }
+            r = (uint32_t)lo;
+        } else r = (uint32_t)(i / slots_per_read);
     } else if (i - nslots < nov) { r = o_read[i - nslots]; b = o_bkt[i - nslots]; meta = o_meta[i - nslots]; slot = o_rank[i - nslots]; }
     const bool valid = meta != NONE32;
     uint64_t dst = ~0ull;
@@ -1981,12 +1987,43 @@ static uint32_t k1_chunk_reads() {                      // consecutive reads per
 // K1 on reads [0, nr) of (boff, good): the lane-per-read kernel when a read's slots fit its LDS staging (spp * npass <= 16: reads up to
 // ~315 good bases at the default 8 slots per pass), the wavefront-per-read kernel otherwise or with W2RAP_K1=wave
 // (W2RAP_K1_MINW: 6 or 7 waves per SIMD instead of 8 for the latter -- 80 / 72 VGPRs, no spills -- an A/B knob)
+static bool k1_wave(uint32_t spp, uint32_t npass) {
+    const char* k1v = getenv("W2RAP_K1");
+    return (k1v && !strcmp(k1v, "wave")) || spp * npass > 16;
+}
+
+__global__ void __launch_bounds__(256) k_k1_passes(uint64_t n, const uint16_t* __restrict__ good, uint32_t* __restrict__ np) {
+    const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= n) return;
+    const uint32_t g = good[r];
+    np[r] = g > K ? (g - (K - 1) + 127) / 128 : 0;
+}
+
+// The wavefront kernel's descriptor slots: spp per pass of 128 k-mer positions that read r HAS, from slot pass_off[r] * spp on -- sized by
+// the reads' own lengths, not n times the longest read's passes (one read of 65,535 bases among 600 k PE150 reads: 20 GB of slots).
+// pass_off: [nr + 1] (the caller's); *total: the passes of all nr reads.
+static int k1_pass_offsets(Ctx& c, uint64_t nr, const uint16_t* good, uint64_t* pass_off, uint64_t* total) {
+    *total = 0;
+    if (!nr) return 0;
+    uint32_t* np = nullptr;
+    W2_ALLOC(np, uint32_t, nr);
+    LAUNCH(c, "k_k1_passes", k_k1_passes, dim3((unsigned)((nr + 255) / 256)), dim3(256), 0, nr, good, np);
+    W2_HIP(hipGetLastError());
+    W2_TRY(exclusive_scan_u32_to_u64(c, np, pass_off, nr));
+    W2_HIP(hipMemcpyAsync(total, pass_off + nr, 8, hipMemcpyDeviceToHost, c.stream));
+    W2_HIP(hipStreamSynchronize(c.stream));
+    c.release(np);
+    return 0;
+}
+
 static int launch_k1(Ctx& c, uint64_t nr, const uint64_t* boff, const uint16_t* good, uint32_t pb_lo, uint32_t pb_hi, uint32_t* bcount,
                      uint32_t nbl_part, uint32_t inv_nbl, unsigned long long* d_part, uint2* s_desc, uint32_t spp, uint32_t npass,
+                     const uint64_t* pass_off /* k1_wave: k1_pass_offsets' */,
                      uint32_t* o_read, uint32_t* o_bkt, uint32_t* o_meta, uint32_t* o_rank, uint64_t ov_cap, unsigned long long* d_ov_cur) {
-    const char* k1v = getenv("W2RAP_K1");
-    const bool wave_kernel = k1v && !strcmp(k1v, "wave");
-    if (!wave_kernel && spp * npass <= 16) {
+    if (getenv("W2RAP_TRACE"))                           // the route (tests assert it: a moved threshold must not go unnoticed)
+        fprintf(stderr, "[w2rap] K1 route: %s, npass %u, spp %u, %llu reads, longest %u\n", k1_wave(spp, npass) ? "wave" : "lane",
+                npass, spp, (unsigned long long)nr, c.max_len);
+    if (!k1_wave(spp, npass)) {
         // (four waves per SIMD: with five -- the staging area of 8 slots per read would leave room -- the scatter pass beside it loses more
         // than this kernel gains, partition 20.6 -> 23.8 ms; W2RAP_K1_ALIGN64: the cuts of the wavefront-per-read kernel, for the test that
         // compares the two)
@@ -2007,13 +2044,13 @@ static int launch_k1(Ctx& c, uint64_t nr, const uint64_t* boff, const uint16_t* 
     static const int k1_minw = getenv("W2RAP_K1_MINW") ? atoi(getenv("W2RAP_K1_MINW")) : 8;
     if (k1_minw == 6)
         LAUNCH(c, "k_superkmers", k_superkmers<6>, dim3(grid), dim3(256), 0, nr, k1_chunk, c.d_bases, boff, good, c.NB, pb_lo, pb_hi, bcount, nbl_part, inv_nbl, d_part,
-               s_desc, spp, npass, o_read, o_bkt, o_meta, o_rank, ov_cap, d_ov_cur);
+               s_desc, spp, npass, pass_off, o_read, o_bkt, o_meta, o_rank, ov_cap, d_ov_cur);
     else if (k1_minw == 7)
         LAUNCH(c, "k_superkmers", k_superkmers<7>, dim3(grid), dim3(256), 0, nr, k1_chunk, c.d_bases, boff, good, c.NB, pb_lo, pb_hi, bcount, nbl_part, inv_nbl, d_part,
-               s_desc, spp, npass, o_read, o_bkt, o_meta, o_rank, ov_cap, d_ov_cur);
+               s_desc, spp, npass, pass_off, o_read, o_bkt, o_meta, o_rank, ov_cap, d_ov_cur);
     else
         LAUNCH(c, "k_superkmers", k_superkmers<8>, dim3(grid), dim3(256), 0, nr, k1_chunk, c.d_bases, boff, good, c.NB, pb_lo, pb_hi, bcount, nbl_part, inv_nbl, d_part,
-               s_desc, spp, npass, o_read, o_bkt, o_meta, o_rank, ov_cap, d_ov_cur);
+               s_desc, spp, npass, pass_off, o_read, o_bkt, o_meta, o_rank, ov_cap, d_ov_cur);
     W2_HIP(hipGetLastError());
     return 0;
 }
@@ -2050,14 +2087,18 @@ int count_partition(Ctx& c, uint32_t nb, uint32_t n_parts, uint32_t pb_lo, uint3
     uint2* s_desc = nullptr; uint32_t *o_read = nullptr, *o_bkt = nullptr, *o_meta = nullptr, *o_rank = nullptr;
     uint64_t ov_cap = n / 8 + 1024;
     W2_ALLOC(o_read, uint32_t, ov_cap); W2_ALLOC(o_bkt, uint32_t, ov_cap); W2_ALLOC(o_meta, uint32_t, ov_cap); W2_ALLOC(o_rank, uint32_t, ov_cap);
-    uint64_t nslots = 0, nov = 0;
+    uint64_t nslots = 0, nov = 0, npass_tot = 0;
+    uint64_t* pass_off = nullptr;
+    bool wave = false;
     for (;;) {
-        nslots = n * npass * spp;
+        wave = k1_wave(spp, npass);
+        if (wave && !pass_off) { W2_ALLOC(pass_off, uint64_t, n + 1); W2_TRY(k1_pass_offsets(c, n, c.d_good, pass_off, &npass_tot)); }
+        nslots = wave ? npass_tot * spp : n * npass * spp;
         W2_ALLOC(s_desc, uint2, nslots);
         W2_HIP(hipMemsetAsync(c.d_bcount, 0, (size_t)nbr * 4, st));
         W2_HIP(hipMemsetAsync(d_ov_cur, 0, 16, st));
         if (d_part) W2_HIP(hipMemsetAsync(d_part, 0, 64 * 64 * 8, st));
-        if (n) W2_TRY(launch_k1(c, n, c.d_boff, c.d_good, pb_lo, pb_hi, c.d_bcount, nbl_part, inv_nbl, d_part, s_desc, spp, npass, o_read, o_bkt, o_meta, o_rank, ov_cap, d_ov_cur));
+        if (n) W2_TRY(launch_k1(c, n, c.d_boff, c.d_good, pb_lo, pb_hi, c.d_bcount, nbl_part, inv_nbl, d_part, s_desc, spp, npass, pass_off, o_read, o_bkt, o_meta, o_rank, ov_cap, d_ov_cur));
         W2_TRY(exclusive_scan_u32_to_u64(c, c.d_bcount, c.d_bbase, nbr));
         unsigned long long h_ov = 0;
         W2_HIP(hipMemcpyAsync(&c.nrec, c.d_bbase + nbr, 8, hipMemcpyDeviceToHost, st));
@@ -2081,11 +2122,16 @@ int count_partition(Ctx& c, uint32_t nb, uint32_t n_parts, uint32_t pb_lo, uint3
         uint64_t bases_bytes = 0;
         W2_HIP(hipMemcpy(&bases_bytes, c.d_boff + n, 8, hipMemcpyDeviceToHost));
         const uint64_t nthreads = nslots + nov;
-        LAUNCH(c, "k_scatter_records", k_scatter_records, dim3((unsigned)((nthreads + 255) / 256)), dim3(256), 0, nslots, npass * spp, s_desc,
+        if (wave)
+            LAUNCH(c, "k_scatter_records", k_scatter_records<true>, dim3((unsigned)((nthreads + 255) / 256)), dim3(256), 0, nslots, spp, pass_off, n, s_desc,
+                   nov, o_read, o_bkt, o_meta, o_rank, c.d_bases, c.d_boff, bases_bytes, c.d_bbase, c.d_recs);
+        else
+        LAUNCH(c, "k_scatter_records", k_scatter_records<false>, dim3((unsigned)((nthreads + 255) / 256)), dim3(256), 0, nslots, npass * spp, nullptr, 0, s_desc,
                nov, o_read, o_bkt, o_meta, o_rank, c.d_bases, c.d_boff, bases_bytes, c.d_bbase, c.d_recs);
         W2_HIP(hipGetLastError());
     }
     W2_HIP(hipStreamSynchronize(st));
+    if (pass_off) c.release(pass_off);
     c.release(d_ov_cur); if (d_part) c.release(d_part); c.release(s_desc); c.release(o_read); c.release(o_bkt); c.release(o_meta); c.release(o_rank);
     return 0;
 }
@@ -2121,6 +2167,8 @@ int count_partition_batched(Ctx& c, uint32_t nb, unsigned n_batches, unsigned* n
     const uint64_t per_batch = n_batches > 1 ? (((uint64_t)((double)n / ((double)n_batches - 1.0 + last_frac)) + 2) & ~1ull) : ((n + 1) & ~1ull);
     uint64_t ov_cap[2] = {per_batch / 8 + 1024, per_batch / 8 + 1024};
     uint64_t slots_alloc[2] = {0, 0};
+    uint64_t* pass_off[2] = {nullptr, nullptr};                         // (k1_wave: per batch buffer, the batch it holds, its passes)
+    uint64_t pass_k[2] = {~0ull, ~0ull}, npass_tot[2] = {0, 0};
     for (int b = 0; b < 2; ++b) {
         W2_ALLOC(d_bbase[b], uint64_t, (uint64_t)nbl + 1);
         W2_ALLOC(o_read[b], uint32_t, ov_cap[b]); W2_ALLOC(o_bkt[b], uint32_t, ov_cap[b]); W2_ALLOC(o_meta[b], uint32_t, ov_cap[b]);
@@ -2138,12 +2186,19 @@ int count_partition_batched(Ctx& c, uint32_t nb, unsigned n_batches, unsigned* n
         uint32_t* bcount = c.d_bcount + (uint64_t)k * nbl;
         if (k >= 2) W2_HIP(hipEventSynchronize(ev_k2[k - 2]));            // the scatter that read these double buffers is done
         uint64_t nslots = 0, nov = 0, nrec_k = 0;
+        bool wave = false;
         for (;;) {
-            nslots = nr * npass * spp;
+            wave = k1_wave(spp, npass);
+            if (wave && pass_k[b] != k) {
+                if (!pass_off[b]) W2_ALLOC(pass_off[b], uint64_t, per_batch + 1);
+                W2_TRY(k1_pass_offsets(c, nr, c.d_good + r0, pass_off[b], &npass_tot[b]));
+                pass_k[b] = k;
+            }
+            nslots = wave ? npass_tot[b] * spp : nr * npass * spp;
             if (slots_alloc[b] < nslots) { if (s_desc[b]) c.release(s_desc[b]); W2_ALLOC(s_desc[b], uint2, nslots); slots_alloc[b] = nslots; }
             W2_HIP(hipMemsetAsync(bcount, 0, (size_t)nbl * 4, st));
             W2_HIP(hipMemsetAsync(d_ov_cur, 0, 16, st));
-            if (nr) W2_TRY(launch_k1(c, nr, c.d_boff + r0, c.d_good + r0, pb_lo, pb_hi, bcount, 0u, 0u, nullptr, s_desc[b], spp, npass, o_read[b], o_bkt[b], o_meta[b], o_rank[b], ov_cap[b], d_ov_cur));
+            if (nr) W2_TRY(launch_k1(c, nr, c.d_boff + r0, c.d_good + r0, pb_lo, pb_hi, bcount, 0u, 0u, nullptr, s_desc[b], spp, npass, wave ? pass_off[b] : nullptr, o_read[b], o_bkt[b], o_meta[b], o_rank[b], ov_cap[b], d_ov_cur));
             W2_TRY(exclusive_scan_u32_to_u64(c, bcount, d_bbase[b], nbl));
             unsigned long long h_ov = 0;
             W2_HIP(hipMemcpyAsync(&nrec_k, d_bbase[b] + nbl, 8, hipMemcpyDeviceToHost, st));
@@ -2174,7 +2229,11 @@ int count_partition_batched(Ctx& c, uint32_t nb, unsigned n_batches, unsigned* n
         hipStream_t sk = n_batches > 1 ? st2 : st;
         if (nrec_k) {
             const uint64_t nthreads = nslots + nov;
-            LAUNCH_ON(c, sk, "k_scatter_records", k_scatter_records, dim3((unsigned)((nthreads + 255) / 256)), dim3(256), 0, nslots, npass * spp, s_desc[b],
+            if (wave)
+                LAUNCH_ON(c, sk, "k_scatter_records", k_scatter_records<true>, dim3((unsigned)((nthreads + 255) / 256)), dim3(256), 0, nslots, spp, pass_off[b], nr, s_desc[b],
+                          nov, o_read[b], o_bkt[b], o_meta[b], o_rank[b], c.d_bases, c.d_boff + r0, bases_bytes, d_bbase[b], c.d_recs + seg_base * REC_DWORDS);
+            else
+            LAUNCH_ON(c, sk, "k_scatter_records", k_scatter_records<false>, dim3((unsigned)((nthreads + 255) / 256)), dim3(256), 0, nslots, npass * spp, nullptr, 0, s_desc[b],
                       nov, o_read[b], o_bkt[b], o_meta[b], o_rank[b], c.d_bases, c.d_boff + r0, bases_bytes, d_bbase[b], c.d_recs + seg_base * REC_DWORDS);
             W2_HIP(hipGetLastError());
         }
@@ -2187,7 +2246,7 @@ int count_partition_batched(Ctx& c, uint32_t nb, unsigned n_batches, unsigned* n
     c.nrec = seg_base;
     if (!c.d_recs) W2_ALLOC(c.d_recs, uint32_t, REC_DWORDS);
     for (int b = 0; b < 2; ++b) {
-        c.release(d_bbase[b]); if (s_desc[b]) c.release(s_desc[b]);
+        c.release(d_bbase[b]); if (s_desc[b]) c.release(s_desc[b]); if (pass_off[b]) c.release(pass_off[b]);
         c.release(o_read[b]); c.release(o_bkt[b]); c.release(o_meta[b]); c.release(o_rank[b]);
     }
     c.release(d_ov_cur);

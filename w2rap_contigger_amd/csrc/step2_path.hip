@@ -28,6 +28,9 @@ constexpr unsigned PCS = 256;          // counter slots
 constexpr unsigned LP = 2;             // parts of a read kept in LDS (most reads end with <= 4: seed, gap, seed, ...)
 constexpr unsigned PL = 4;             // path elements of a read kept in LDS: logical positions pmid-1 .. pmid+PL-2
 constexpr unsigned PATH_THREADS = 256;
+constexpr uint32_t LONG_READ = 1024;                    // reads longer than this get a pathing pass of their own ...
+constexpr uint64_t SCRATCH_CAP = 16ull << 30;           // ... where every lane's scratch sized by the longest read would pass this
+constexpr uint64_t LONG_SCRATCH = 2ull << 30;           // the scratch of that pass's lanes (at least one block's)
 #ifndef W2RAP_PATH_TICKETS
 #define W2RAP_PATH_TICKETS 1
 #endif
@@ -1150,6 +1153,28 @@ __global__ void __launch_bounds__(256) k_path_gather(uint64_t n, const uint32_t*
     }
 }
 
+// Reads of more than `cap` bases -> long_list, the others -> short_list (one atomic per wavefront and list; the order inside a list does
+// not matter: every read's path lands at its own plen / inl entry).  cnt: [0] short reads, [1] long reads, [2] the longest short read.
+__global__ void __launch_bounds__(256) k_split_long(uint64_t n, const uint32_t* __restrict__ len, uint32_t cap, uint32_t* __restrict__ short_list,
+                                                    uint32_t* __restrict__ long_list, unsigned long long* __restrict__ cnt) {
+    const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t L = r < n ? len[r] : 0;
+    const bool lg = r < n && L > cap, sh = r < n && !lg;
+    const unsigned long long ms = __ballot(sh), ml = __ballot(lg);
+    const unsigned lane = threadIdx.x & 63;
+    unsigned long long bs = 0, bl = 0;
+    if (lane == 0) {
+        if (ms) bs = atomicAdd(&cnt[0], (unsigned long long)__popcll(ms));
+        if (ml) bl = atomicAdd(&cnt[1], (unsigned long long)__popcll(ml));
+    }
+    bs = __shfl(bs, 0); bl = __shfl(bl, 0);
+    if (sh) short_list[bs + __builtin_amdgcn_mbcnt_hi((uint32_t)(ms >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)ms, 0u))] = (uint32_t)r;
+    if (lg) long_list[bl + __builtin_amdgcn_mbcnt_hi((uint32_t)(ml >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)ml, 0u))] = (uint32_t)r;
+    uint32_t m = sh ? L : 0;
+    for (int o = 32; o > 0; o >>= 1) { const uint32_t m2 = __shfl_down(m, o); m = m2 > m ? m2 : m; }
+    if (lane == 0 && m) atomicMax(&cnt[2], (unsigned long long)m);
+}
+
 int phase_path(Ctx& c) {
     if (!c.graphed) { c.err = "path_reads called before build_graph"; return W2RAP_E_STATE; }
     c.pathed_done = false;
@@ -1191,8 +1216,44 @@ int phase_path(Ctx& c) {
     A.from_off = c.d_from_off; A.from_v = c.d_from_v; A.from_e = c.d_from_e;
     A.to_off = c.d_to_off; A.to_v = c.d_to_v; A.to_e = c.d_to_e;
     A.T = T; A.maxparts = maxparts; A.pcap = pcap; A.pmid = pmid; A.rd_dwords = rd_dwords;
-    W2_ALLOC(A.parts, uint4, (uint64_t)(maxparts > LP ? maxparts - LP : 1) * T);
-    W2_ALLOC(A.pbuf, int32_t, (uint64_t)pcap * T);
+    // Reads far longer than the others: a lane's scratch (the parts and path elements it spills behind the LDS ones) is sized by the
+    // longest read, for every persistent lane -- one read of 65,535 bases among 600 k PE150 reads would ask for ~1 TB.  Where that scratch
+    // passes SCRATCH_CAP, the reads of more than LONG_READ bases are pathed by the listed kernel in a pass of their own, on as many lanes as
+    // LONG_SCRATCH affords, and the other reads by the listed kernel in a pass sized by the longest of them.  The short reads then leave
+    // k_path_dyn / k_path_wave for the listed kernel without a part budget: correct (oracle parity, tests/test_gpu_read_lengths.py), slower
+    // on such inputs by an amount not measured; PE150 and every set without such reads keep their routes.
+    auto parts_of = [](uint32_t L) -> uint32_t { return (L >= K ? L - K + 1 : 1) + 2; };
+    auto lane_bytes = [&](uint32_t L) -> uint64_t { const uint32_t mp = parts_of(L); return (uint64_t)(mp > LP ? mp - LP : 1) * 16 + (uint64_t)(2 * L + 2 + mp) * 4; };
+    const bool long_pass = maxL > LONG_READ && lane_bytes(maxL) * T > SCRATCH_CAP;
+    uint32_t *short_list = nullptr, *long_list = nullptr, L_short = 0, T_short = 0, T_long = 0;
+    uint64_t n_short = 0, n_long = 0;
+    if (long_pass) {
+        unsigned long long* d_cnt = nullptr;
+        W2_ALLOC(d_cnt, unsigned long long, 3);
+        W2_ALLOC(short_list, uint32_t, n); W2_ALLOC(long_list, uint32_t, n);
+        W2_HIP(hipMemsetAsync(d_cnt, 0, 24, st));
+        LAUNCH(c, "k_split_long", k_split_long, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, n, c.d_len, LONG_READ, short_list, long_list, d_cnt);
+        W2_HIP(hipGetLastError());
+        unsigned long long h_cnt[3];
+        W2_HIP(hipMemcpyAsync(h_cnt, d_cnt, sizeof(h_cnt), hipMemcpyDeviceToHost, st));
+        W2_HIP(hipStreamSynchronize(st));
+        c.release(d_cnt);
+        n_short = h_cnt[0]; n_long = h_cnt[1]; L_short = (uint32_t)h_cnt[2];
+        const uint64_t gl = (uint64_t)c.sm_count * std::min<size_t>(8, (160 * 1024) / (lds_static + 512));     // the listed kernel's blocks
+        T_short = (uint32_t)std::min<uint64_t>((n_short + PATH_THREADS - 1) / PATH_THREADS, gl) * PATH_THREADS;
+        T_long = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>({(n_long + PATH_THREADS - 1) / PATH_THREADS, gl,
+                                                                      LONG_SCRATCH / (lane_bytes(maxL) * PATH_THREADS)})) * PATH_THREADS;
+        const uint32_t mp_s = parts_of(L_short);
+        A.T = 0;
+        W2_ALLOC(A.parts, uint4, std::max<uint64_t>((uint64_t)(mp_s > LP ? mp_s - LP : 1) * T_short, (uint64_t)(maxparts - LP) * T_long));
+        W2_ALLOC(A.pbuf, int32_t, std::max<uint64_t>((uint64_t)(2 * L_short + 2 + mp_s) * T_short, (uint64_t)pcap * T_long));
+        if (getenv("W2RAP_TRACE"))
+            fprintf(stderr, "[w2rap] pathing long-read pass: %llu reads of more than %u bases on %u lanes, %llu others (longest %u) on %u lanes\n",
+                    (unsigned long long)n_long, LONG_READ, T_long, (unsigned long long)n_short, L_short, T_short);
+    } else {
+        W2_ALLOC(A.parts, uint4, (uint64_t)(maxparts > LP ? maxparts - LP : 1) * T);
+        W2_ALLOC(A.pbuf, int32_t, (uint64_t)pcap * T);
+    }
     W2_ALLOC(A.plen, uint32_t, n); W2_ALLOC(A.inl, int2, n);
     W2_ALLOC(c.d_path_offset, int32_t, n);
     W2_ALLOC(c.d_path_off, uint64_t, n + 1);
@@ -1217,6 +1278,9 @@ int phase_path(Ctx& c) {
     if (const char* v = getenv("W2RAP_PATH_BUDGET")) A.part_budget = (uint32_t)atoi(v);   // (0: everything in one pass)
     A.defer_cap = A.part_budget ? n : 0;
     W2_ALLOC(A.defer, uint32_t, A.defer_cap);
+    if (getenv("W2RAP_TRACE"))                           // the routes (tests assert them: a moved threshold must not go unnoticed)
+        fprintf(stderr, "[w2rap] pathing route: longest %u, main %s, many-part %s, part budget %u, %u slots\n", maxL,
+                long_pass ? "split" : dyn ? "dyn" : staged ? "staged" : "global", wave_ok ? "wave" : "listed", A.part_budget, long_pass ? T_short + T_long : T);
     uint64_t pool_cap = 2 * n + (1u << 20) + (wave_ok ? (uint64_t)c.sm_count * 4 * 4 * WAVE_SLAB : 0);
     if (const char* v = getenv("W2RAP_PATH_POOL")) pool_cap = (uint64_t)atoll(v);        // (tests: force the retry)
     unsigned long long h_all[4 + 2 * PCS];
@@ -1259,7 +1323,8 @@ int phase_path(Ctx& c) {
     // Qualities that are still travelling (w2rap_step2_run's late upload): the first part of the reads is pathed as soon as ITS qualities
     // are up -- the extension's scores are all that reads them --, the rest behind the upload's end.
     uint64_t split = 0;
-    if (c.quals_job) {
+    if (c.quals_job && long_pass) W2_TRY(quals_wait(c));
+    else if (c.quals_job) {
         W2_TRY(quals_wait_prefix(c, &split));
         if (split == 0 || split >= n) { split = 0; W2_TRY(quals_wait(c)); }
     }
@@ -1268,7 +1333,23 @@ int phase_path(Ctx& c) {
         if (!A.pool) return W2RAP_E_HIP;
         A.pool_cap = pool_cap;
         W2_HIP(hipMemsetAsync(A.counters, 0, (4 + 2 * PCS) * 8, st));
-        for (int part = 0; part < (split ? 2 : 1); ++part) {
+        if (long_pass) {
+            for (int pass = 0; pass < 2; ++pass) {           // the short reads, then the long ones; the pool cursor and the statistics go on
+                PathArgs B = A;
+                const uint32_t L = pass ? maxL : L_short;
+                B.r_first = 0; B.n = pass ? n_long : n_short; B.list = pass ? long_list : short_list; B.T = pass ? T_long : T_short;
+                B.maxparts = parts_of(L); B.pmid = L + 1; B.pcap = B.pmid + B.maxparts + L + 1; B.rd_dwords = 0;
+                B.part_budget = 0; B.defer = nullptr; B.defer_cap = 0;
+                if (!B.n) continue;
+                W2_HIP(hipMemsetAsync(A.counters, 0, 8, st));                 // the chunk queue
+                if (idx) LAUNCH(c, "k_path_deferred", (k_path<false, true, true>), dim3(B.T / PATH_THREADS), dim3(PATH_THREADS), 0, B);
+                else LAUNCH(c, "k_path_deferred", (k_path<false, true, false>), dim3(B.T / PATH_THREADS), dim3(PATH_THREADS), 0, B);
+                W2_HIP(hipGetLastError());
+            }
+            W2_HIP(hipMemcpyAsync(h_all, A.counters, sizeof(h_all), hipMemcpyDeviceToHost, st));
+            W2_HIP(hipStreamSynchronize(st));
+        }
+        else for (int part = 0; part < (split ? 2 : 1); ++part) {
             A.r_first = part ? split : 0; A.n = split && !part ? split : n;
             if (part) {
                 W2_TRY(quals_wait(c));                                   // everything is up (and c.stream waits for the last copy)
@@ -1284,6 +1365,8 @@ int phase_path(Ctx& c) {
                 W2_TRY(launch(B, true));
                 W2_HIP(hipMemcpyAsync(h_all, A.counters, sizeof(h_all), hipMemcpyDeviceToHost, st));
                 W2_HIP(hipStreamSynchronize(st));
+                if (getenv("W2RAP_TRACE"))
+                    fprintf(stderr, "[w2rap] pathing many-part pass: %llu reads, %s\n", (unsigned long long)B.n, wave_ok ? "wave" : "listed");
                 if (wave_ok && getenv("W2RAP_TRACE"))
                     fprintf(stderr, "[w2rap] k_path_wave: %llu reads, shader clocks per read: positional lookups %.0f, sequential rest %.0f\n",
                             (unsigned long long)B.n, (double)h_all[0] / (double)B.n, (double)h_all[3] / (double)B.n);
@@ -1322,6 +1405,7 @@ int phase_path(Ctx& c) {
     for (unsigned i = 0; i < PCS; ++i) { c.n_pathed += h_all[4 + 2 * i]; c.n_multipathed += h_all[5 + 2 * i]; }
     c.d_path_edges = d_out; c.path_total = total;
     c.release(A.parts); c.release(A.pbuf); c.release(A.plen); c.release(A.inl); c.release(A.pool); c.release(A.counters); c.release(A.defer);
+    if (long_pass) { c.release(short_list); c.release(long_list); }
     c.pathed_done = true;
     return 0;
 }

@@ -94,6 +94,74 @@ def sample_reads(contigs, n_pairs: int, seed: int, device="cpu", err_rate=0.005,
     return codes.contiguous(), quals.contiguous()
 
 
+def diploid_genome(length: int, seed: int, snp_every=300, dense=None, repeat_len=500, n_repeats=5, tandem=()):
+    """Two haplotypes of a random genome: `n_repeats` exact copies of one `repeat_len` repeat, a 300 bp inverted repeat, tandem
+    arrays tandem = ((start, period, bases), ...), a heterozygous SNP every ~`snp_every` bases and, in dense = (start, end, every),
+    one every ~`every` bases there.  -> [hap1, hap2]"""
+    rng = np.random.default_rng(seed)
+    g = rng.integers(0, 4, length, dtype=np.uint8)
+    rep = rng.integers(0, 4, repeat_len, dtype=np.uint8)
+    for p in np.linspace(length // 20, length - length // 20 - repeat_len, n_repeats).astype(np.int64):
+        g[p:p + repeat_len] = rep
+    a = length // 3
+    g[2 * a:2 * a + 300] = rc_codes(g[a:a + 300])
+    for s0, period, bases in tandem:
+        g[s0:s0 + bases] = np.tile(rng.integers(0, 4, period, dtype=np.uint8), bases // period + 1)[:bases]
+    hap2 = g.copy()
+    sites = [np.arange(snp_every // 2, length, snp_every) + rng.integers(-snp_every // 4, snp_every // 4 + 1, len(range(snp_every // 2, length, snp_every)))]
+    if dense is not None:
+        s, e, every = dense
+        sites.append(np.arange(s, e, every) + rng.integers(0, every // 2 + 1, len(range(s, e, every))))
+    sites = np.unique(np.clip(np.concatenate(sites), 0, length - 1))
+    hap2[sites] = (hap2[sites] + 1 + rng.integers(0, 3, len(sites))) & 3
+    return [g, hap2]
+
+
+def sample_reads_of_lengths(contigs, lengths, seed: int, err_rate=0.005, tail_frac=0.2):
+    """Single reads of the given lengths (any, 0 included) from random places and strands of `contigs`, with the errors, qualities
+    and Q2 tails of sample_reads.  -> list of (codes u8, quals u8); a read longer than every contig is an error."""
+    rng = np.random.default_rng(seed)
+    lens = np.array([len(c) for c in contigs], dtype=np.int64)
+    out = []
+    gq = np.array(GOOD_Q, np.uint8)
+    for L in lengths:
+        L = int(L)
+        ok = np.nonzero(lens >= L)[0]
+        if len(ok) == 0:
+            raise ValueError(f"no contig holds a read of {L} bases")
+        c = contigs[int(rng.choice(ok))]
+        s = int(rng.integers(0, len(c) - L + 1))
+        codes = c[s:s + L].copy()
+        if rng.integers(0, 2):
+            codes = rc_codes(codes)
+        err = rng.random(L) < err_rate
+        codes[err] = (codes[err] + rng.integers(1, 4, int(err.sum()))) & 3
+        quals = gq[rng.integers(0, len(gq), L)]
+        quals[err] = rng.integers(2, 13, int(err.sum()))
+        if L and rng.random() < tail_frac:
+            quals[L - min(L, int(rng.integers(1, 21))):] = 2
+        out.append((codes.astype(np.uint8), quals.astype(np.uint8)))
+    return out
+
+
+def read_length_workload(contigs, n_pairs: int, seed: int, read_len=READ_LEN, insert=INSERT, extra_lengths=(), shuffle=True):
+    """Paired reads of `read_len` (sample_reads) plus single reads of `extra_lengths` from the same genome, shuffled together.
+    -> (codes u8, quals u8, off u64[n+1]) host arrays, the layout oracle.run takes"""
+    reads = []
+    if n_pairs:
+        codes, quals = sample_reads(contigs, n_pairs, seed, read_len=read_len, insert=insert)
+        codes, quals = codes.numpy(), quals.numpy()
+        reads = [(codes[i], quals[i]) for i in range(len(codes))]
+    reads += sample_reads_of_lengths(contigs, extra_lengths, seed + 7919)
+    if shuffle:
+        order = np.random.default_rng(seed + 1).permutation(len(reads))
+        reads = [reads[i] for i in order]
+    lens = np.array([len(r[0]) for r in reads], np.uint64)
+    off = np.zeros(len(reads) + 1, np.uint64)
+    np.cumsum(lens, out=off[1:])
+    return (np.concatenate([r[0] for r in reads]).astype(np.uint8), np.concatenate([r[1] for r in reads]).astype(np.uint8), off)
+
+
 def pack_fixed(codes: torch.Tensor) -> torch.Tensor:
     """[n, L] base codes -> [n, ceil(L/4)] packed bytes (.fastb per-read layout, base i at bits 2*(i%4))"""
     n, L = codes.shape
