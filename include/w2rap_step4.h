@@ -1,0 +1,111 @@
+/* w2rap_step4.h -- C ABI of the MI355X-native replacement for w2rap-contigger's Step 4, "Cleaning graph" (Clean200x).
+ * Exported by the same shared library as Steps 1-3 (w2rap_contigger_amd/libw2rap_step2.so).
+ *
+ * Drop-in boundary.  w2rap_step4_run replaces exactly this block of the reference's main (src/modules/w2rap-contigger.cc:395-399):
+ *     inv.clear();
+ *     hbvr.Involution(inv);                                              // src/paths/HyperBasevector.cc:648-660
+ *     Clean200x(hbvr, inv, pathsr, bases, quals, 0, 3, min_size);        // src/paths/long/large/Clean200.cc:202-389
+ * Inputs are what BinaryReader::readFile(<prefix>.large_K.hbv), LoadReadPathVec(<prefix>.large_K.paths) and the loads of
+ * frag_reads_orig.fastb / .qualp hold (:322-328, :388-389); outputs are what BinaryWriter::writeFile(<prefix>.large_K.clean.hbv, hbvr)
+ * and WriteReadPathVec(pathsr, <prefix>.large_K.clean.paths) serialise (:404-405).
+ *
+ * What runs where.  Everything proportional to the reads -- the paths index (invert(), VecUtilities.h:693-719), the placements of
+ * reads on branch vertices, the quality-weighted vote, the verdict (AnalyzeScores) and the rewrite of the read paths -- runs in HIP
+ * kernels for gfx950; there is no CPU fallback (W2RAP_E_NO_DEVICE).  The edit of the graph itself (DeleteEdges,
+ * RemoveUnneededVertices2, CleanupCore: O(edges), serial in the reference, numbering defined by its stack order) runs on the host
+ * inside the library; its time is reported separately (ms_graph_edit_host).
+ *
+ * Plain pointers and sizes; never throws; returns 0 or a W2RAP_E_* code (w2rap_step2.h) with a message in `err`.  Integer arithmetic
+ * throughout: results are exact, byte for byte the reference's.
+ */
+#ifndef W2RAP_STEP4_H_
+#define W2RAP_STEP4_H_
+
+#include "w2rap_step2.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+/* ---- inputs (host memory) ------------------------------------------------------------------------------------------------- */
+typedef struct w2rap_step4_in {
+    int32_t  K;                      /* hbvr.K(): the large K, 200 by default; 16 <= K <= 640 */
+    uint64_t n_edge_objs;            /* hbvr.EdgeObjectCount() */
+    const uint8_t*  edge_packed;     /* each object ceil(len/4) bytes, base i at bits 2*(i%4) of byte i/4 (.hbv edges_ section) */
+    const uint64_t* edge_byte_off;   /* [n_edge_objs+1] */
+    const uint32_t* edge_len;        /* [n_edge_objs] bases, >= K */
+    /* the adjacency LISTS as the .hbv file holds them: their order is From(v) / To(v), which IFrom(v, j) and the stacks of
+       RemoveUnneededVertices2 depend on.  Every edge object appears once in from_e and once in to_e */
+    uint64_t n_vertices;             /* hbvr.N() */
+    const uint64_t* from_off;        /* [n_vertices+1] */
+    const int32_t*  from_v;          /* [n_edge_objs] From(v) */
+    const int32_t*  from_e;          /* [n_edge_objs] from_edge_obj_ */
+    const uint64_t* to_off;          /* [n_vertices+1] */
+    const int32_t*  to_e;            /* [n_edge_objs] to_edge_obj_ */
+    const int32_t*  inv;             /* [n_edge_objs] hbvr.Involution (w2rap_step3_out.inv2), or NULL: computed here from the sequences */
+    /* pathsr */
+    uint64_t n_paths;
+    const int32_t*  path_offset;     /* [n_paths] */
+    const uint64_t* path_off;        /* [n_paths+1] */
+    const int32_t*  path_edges;
+    /* the reads: frag_reads_orig.fastb and the UNPACKED .qualp values, one byte per base */
+    uint64_t n_reads;                /* == n_paths */
+    const uint8_t*  read_packed;
+    const uint64_t* read_byte_off;   /* [n_reads+1] */
+    const uint32_t* read_len;        /* [n_reads] */
+    const uint8_t*  quals;
+    const uint64_t* qual_off;        /* [n_reads+1]; qual_off[r+1] - qual_off[r] == read_len[r] */
+} w2rap_step4_in;
+
+typedef struct w2rap_step4_params {
+    int32_t  device;                 /* HIP device ordinal */
+    uint32_t min_size;               /* -s / --min_size: a component that is one edge of at most min_size K-mers is deleted; default 0 (off) */
+    uint32_t flags;
+} w2rap_step4_params;
+#define W2RAP_STEP4_VOTE_ONLY 1u     /* run pass 1's vote (and min_size), return its deleted list, edit nothing: the outputs hold the input graph and paths */
+
+/* ---- outputs (library-allocated HOST memory; free with w2rap_step4_free) ---------------------------------------------------- */
+typedef struct w2rap_step4_out {
+    int32_t  K;
+    /* the clean graph, field layout of w2rap_step3_out */
+    uint64_t n_vertices;
+    uint64_t n_edge_objs;
+    uint8_t*  edge_packed;
+    uint64_t* edge_byte_off;         /* [n_edge_objs+1] */
+    uint32_t* edge_len;              /* [n_edge_objs] */
+    int32_t*  vleft;                 /* [n_edge_objs] */
+    int32_t*  vright;                /* [n_edge_objs] */
+    uint64_t* from_off;              /* [n_vertices+1] */
+    int32_t*  from_v;
+    int32_t*  from_e;
+    uint64_t* to_off;                /* [n_vertices+1] */
+    int32_t*  to_v;
+    int32_t*  to_e;
+    int32_t*  inv;                   /* [n_edge_objs] the involution of the clean graph */
+    /* the read paths on it */
+    uint64_t n_paths;
+    int32_t*  path_offset;           /* [n_paths] */
+    uint64_t* path_off;              /* [n_paths+1] */
+    int32_t*  path_edges;
+    /* per pass: the sorted unique edge ids handed to hb.DeleteEdges (Clean200.cc:384), ids of THAT pass's input graph */
+    uint64_t n_deleted[2];
+    int32_t*  deleted[2];
+    uint64_t n_runs_merged[2];       /* edges RemoveUnneededVertices2 added (a run and its mirror count as two) */
+    uint64_t n_branch_vertices;      /* vertices with an edge in and two or more out, both passes */
+    uint64_t n_skipped_too_many_exts;/* of those: more than 10 walks (Clean200.cc:246) */
+    uint64_t n_placements;           /* (read, start) placements scored, both passes */
+    float ms_index[2], ms_vote[2], ms_paths[2];      /* device time per pass, milliseconds */
+    float ms_graph_edit_host[2];                     /* HOST time of the graph edit per pass, milliseconds */
+    void* _owner;                    /* internal */
+} w2rap_step4_out;
+
+int  w2rap_step4_run(const w2rap_step4_in* in, const w2rap_step4_params* params, w2rap_step4_out* out, char* err, size_t errlen);
+void w2rap_step4_free(w2rap_step4_out* out);
+
+/* per-kernel device time of the last w2rap_step4_run in this process: "kernel_name total_ms launches\n" lines; returns the bytes needed */
+size_t w2rap_step4_profile(char* buf, size_t len);
+
+#ifdef __cplusplus
+}
+#endif
+#endif /* W2RAP_STEP4_H_ */

@@ -1,0 +1,785 @@
+// step4_clean.hip -- Step 4, "Cleaning graph": Clean200x (src/paths/long/large/Clean200.cc:202-389) on the large-K graph.
+//
+// Per pass (two of them):
+//   device  k4_index_count / scan / k4_index_fill    invert(paths): per edge the reads whose path holds it, one listing per occurrence
+//   device  k4_walks            GetExtensions (:445-470) for every branch vertex, one wavefront each: <= 10 walks, their bases gathered
+//                               into a table [vertex][position][walk] (a byte per base, 16 walks' slots per position = one 16-B load)
+//   device  k4_item_count / scan / k4_place_count / scan / k4_place_fill
+//                               ONE flat list of placements (vertex, read, start, strand) over all branch vertices (:267-340)
+//   device  k4_score            per placement <= 10 running sums over <= 250 + K - 1 positions (:292-309, :341-359) -> (out-edge, margin)
+//   device  k4_reduce           the 16 threshold sums per (vertex, out-edge): a segmented reduction per tile of placements
+//   device  k4_verdict          AnalyzeScores (:391-443) -> a dead flag per edge object
+//   host    edit_graph          min_size (:370-380), DeleteEdges, RemoveUnneededVertices2 (GapToyTools3.cc:87-294), CleanupCore
+//                               (GapToyTools.cc:417-453): O(edges), the reference's numbering follows from its stack order
+//   device  k4_path_len / scan / k4_path_write       Cleanup's truncation + both renumberings of the read paths in one go
+// Integer arithmetic throughout; the order in which placements are listed does not matter (only sums of margins are used).
+#include <algorithm>
+#include <chrono>
+#include <cstring>
+#include <string>
+#include <unordered_map>
+#include <vector>
+#include "ctx.h"
+#include "../../include/w2rap_step4.h"
+
+namespace w2 {
+namespace {
+
+constexpr int MAX_EXTS = 10, MAX_RL = 250, MAX_DEL = 15, MIN_WIN = 100, MAX_LOSE = 50, MIN_RATIO = 5;
+constexpr unsigned WSLOTS = 16;           // table slots per position (walks 0..9 used)
+constexpr unsigned NSUM = MAX_EXTS * (MAX_DEL + 1);   // threshold sums per branch vertex: [out-edge][d]
+
+inline unsigned grid4(uint64_t n, unsigned b = 256) { return (unsigned)((n + b - 1) / b); }
+
+struct Task { uint32_t bv; uint32_t role; int32_t edge; uint32_t pad; };     // role 0: in-edge, 1: out-edge, 2: inv[in-edge], 3: inv[out-edge]
+struct Place { uint32_t bv; uint32_t rid; int32_t start; uint32_t rc; };
+
+// ---- paths index ---------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k4_index_count(uint64_t total, const int32_t* __restrict__ pe, uint32_t* __restrict__ cnt) {
+    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < total) atomicAdd(&cnt[pe[i]], 1u);
+}
+// one thread per read: its entries in order (the listing order inside an edge does not matter to any sum)
+__global__ __launch_bounds__(256) void k4_index_fill(uint64_t n, const uint64_t* __restrict__ poff, const int32_t* __restrict__ pe,
+                                                     const uint64_t* __restrict__ ioff, uint32_t* __restrict__ cursor, uint32_t* __restrict__ list) {
+    const uint64_t r = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (r >= n) return;
+    for (uint64_t i = poff[r]; i < poff[r + 1]; ++i) {
+        const int32_t e = pe[i];
+        list[ioff[e] + atomicAdd(&cursor[e], 1u)] = (uint32_t)r;
+    }
+}
+
+// ---- walks ---------------------------------------------------------------------------------------------------------------
+struct GraphDev {
+    unsigned K; uint64_t E, NV;
+    const uint32_t* elen; const uint64_t* ebyte; const uint8_t* ebits;
+    const uint64_t* from_off; const int32_t* from_e; const uint64_t* to_off; const int32_t* to_e; const int32_t* vright; const int32_t* inv;
+};
+
+// bases [from, from + cnt) of edge e -> column `col` of the vertex's table from position `dst`, clipped at Lmax
+__device__ inline void put_bases(uint8_t* tab, unsigned col, unsigned dst, const uint8_t* eb, unsigned from, unsigned cnt, unsigned Lmax, unsigned lane) {
+    if (dst >= Lmax) return;
+    if (cnt > Lmax - dst) cnt = Lmax - dst;
+    for (unsigned t = lane; t < cnt; t += 64) tab[(uint64_t)(dst + t) * WSLOTS + col] = (uint8_t)packed_base(eb, from + t);
+}
+
+// one wavefront per branch vertex.  State in LDS, written by lane 0, read by all (uniform control flow).
+__global__ __launch_bounds__(64) void k4_walks(uint32_t B, const int32_t* __restrict__ bvert, GraphDev g, unsigned Lmax,
+                                               uint8_t* __restrict__ tabs, int32_t* __restrict__ nwalks, int32_t* __restrict__ depth_out, uint8_t* __restrict__ ei_out) {
+    __shared__ int s_len[MAX_EXTS], s_last[MAX_EXTS], s_ei[MAX_EXTS];
+    __shared__ int s_count, s_depth;
+    const unsigned b = blockIdx.x, lane = threadIdx.x;
+    if (b >= B) return;
+    const int v = bvert[b];
+    uint8_t* tab = tabs + (uint64_t)b * Lmax * WSLOTS;
+    const int K = (int)g.K;
+    const uint64_t f0 = g.from_off[v];
+    const int n = (int)(g.from_off[v + 1] - f0);
+    if (lane == 0) s_depth = MAX_RL;
+    __syncthreads();
+    for (int pass = 0; pass < 2; ++pass) {
+        if (lane == 0) s_count = n;
+        for (int j = 0; j < n && j < MAX_EXTS; ++j) {
+            const int e = g.from_e[f0 + j];
+            if (lane == 0) { s_len[j] = (int)g.elen[e] - K + 1; s_last[j] = e; s_ei[j] = j; }
+            put_bases(tab, j, 0, g.ebits + g.ebyte[e], 0, g.elen[e], Lmax, lane);
+        }
+        __syncthreads();
+        int i = 0;
+        while (i < MAX_EXTS && i < s_count) {
+            const int len = s_len[i], depth = s_depth;
+            if (len >= depth) { ++i; continue; }
+            const int w = g.vright[s_last[i]];
+            const uint64_t w0 = g.from_off[w];
+            const int deg = (int)(g.from_off[w + 1] - w0);
+            if (deg == 0) {
+                __syncthreads();
+                if (lane == 0) s_depth = len < depth ? len : depth;
+                __syncthreads();
+                ++i;
+                continue;
+            }
+            const unsigned cur = (unsigned)(len + K - 1);
+            const int count0 = s_count, eii = s_ei[i];
+            __syncthreads();                                 // everybody has read the state this step is based on
+            for (int m = 0; m < deg; ++m) {
+                const int e = g.from_e[w0 + m];
+                const int col = m == 0 ? i : count0 + m - 1;
+                if (col < MAX_EXTS) {
+                    if (m) for (unsigned t = lane; t < cur && t < Lmax; t += 64) tab[(uint64_t)t * WSLOTS + col] = tab[(uint64_t)t * WSLOTS + i];
+                    put_bases(tab, col, cur, g.ebits + g.ebyte[e], (unsigned)(K - 1), g.elen[e] - (unsigned)(K - 1), Lmax, lane);
+                    if (lane == 0) { s_len[col] = len + (int)g.elen[e] - K + 1; s_last[col] = e; s_ei[col] = eii; }
+                }
+            }
+            if (lane == 0) s_count = count0 + deg - 1;
+            __syncthreads();
+        }
+        __syncthreads();
+    }
+    if (lane == 0) { nwalks[b] = s_count; depth_out[b] = s_depth; }
+    if (lane < MAX_EXTS) ei_out[(uint64_t)b * WSLOTS + lane] = lane < (unsigned)s_count ? (uint8_t)s_ei[lane] : (uint8_t)0xFF;
+}
+
+// ---- placements ----------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k4_item_count(uint64_t T, const Task* __restrict__ tasks, const int32_t* __restrict__ nwalks,
+                                                     const uint32_t* __restrict__ icnt, uint32_t* __restrict__ out) {
+    const uint64_t t = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (t >= T) return;
+    out[t] = nwalks[tasks[t].bv] > MAX_EXTS ? 0u : icnt[tasks[t].edge];
+}
+
+struct PlaceArgs {
+    uint64_t T, n_items; const Task* tasks; const uint64_t* item_off;       // [T+1]
+    const uint64_t* ioff; const uint32_t* ilist;
+    const int32_t* p_offset; const uint64_t* p_off; const int32_t* p_edges; const int32_t* bvert;
+};
+
+// the placements of one item (task, listing k): every j with p[j] == edge, filtered and placed as Clean200.cc:267-340 does
+template <bool WRITE>
+__device__ inline uint32_t item_places(const PlaceArgs& a, const GraphDev& g, uint64_t item, Place* out) {
+    uint64_t lo = 0, hi = a.T;                                // the last task whose first item is <= item
+    while (hi - lo > 1) { const uint64_t mid = (lo + hi) >> 1; if (a.item_off[mid] <= item) lo = mid; else hi = mid; }
+    const Task t = a.tasks[lo];
+    const uint32_t rid = a.ilist[a.ioff[t.edge] + (item - a.item_off[lo])];
+    const uint64_t p0 = a.p_off[rid], p1 = a.p_off[rid + 1];
+    const int v = a.bvert[t.bv];
+    const uint64_t t0 = g.to_off[v], t1 = g.to_off[v + 1];
+    int start = a.p_offset[rid];
+    uint32_t k = 0;
+    for (uint64_t j = p0; j < p1; ++j) {
+        const int32_t e = a.p_edges[j];
+        const int km = (int)g.elen[e] - (int)g.K + 1;
+        if (e == t.edge) {
+            bool skip = false;
+            if (t.role == 1 && j > p0) { const int32_t q = a.p_edges[j - 1]; for (uint64_t u = t0; u < t1; ++u) skip |= g.to_e[u] == q; }
+            if (t.role == 3 && j + 1 < p1) { const int32_t q = a.p_edges[j + 1]; for (uint64_t u = t0; u < t1; ++u) skip |= g.inv[g.to_e[u]] == q; }
+            if (!skip) {
+                if (WRITE) out[k] = Place{t.bv, rid, (t.role == 0 || t.role == 3) ? start - km : start, t.role >= 2 ? 1u : 0u};
+                ++k;
+            }
+        }
+        start -= km;
+    }
+    return k;
+}
+__global__ __launch_bounds__(256) void k4_place_count(PlaceArgs a, GraphDev g, uint32_t* __restrict__ cnt) {
+    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < a.n_items) cnt[i] = item_places<false>(a, g, i, nullptr);
+}
+__global__ __launch_bounds__(256) void k4_place_fill(PlaceArgs a, GraphDev g, const uint64_t* __restrict__ poff, Place* __restrict__ places) {
+    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < a.n_items && poff[i + 1] > poff[i]) item_places<true>(a, g, i, places + poff[i]);
+}
+
+// ---- the vote ------------------------------------------------------------------------------------------------------------
+struct ReadsDev { const uint8_t* bases; const uint64_t* boff; const uint32_t* len; const uint8_t* quals; const uint64_t* qoff; };
+
+// one thread per placement: q[l] = sum of the qualities where the read differs from walk l; per out-edge the minimum over its walks;
+// a strict winner scores the margin.  out: key = vertex * 16 + out-edge, margin (0: no score)
+__global__ __launch_bounds__(256) void k4_score(uint64_t NP, const Place* __restrict__ places, ReadsDev R, unsigned K, unsigned Lmax,
+                                                const uint8_t* __restrict__ tabs, const int32_t* __restrict__ nwalks, const int32_t* __restrict__ depth,
+                                                const uint8_t* __restrict__ ei, const int32_t* __restrict__ outdeg, uint2* __restrict__ out) {
+    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= NP) return;
+    const Place p = places[i];
+    const int N = nwalks[p.bv], n = outdeg[p.bv];
+    const int L = depth[p.bv] + (int)K - 1;
+    const int rl = (int)R.len[p.rid];
+    const uint8_t* rb = R.bases + R.boff[p.rid];
+    const uint8_t* rq = R.quals + R.qoff[p.rid];
+    const uint4* tab = reinterpret_cast<const uint4*>(tabs + (uint64_t)p.bv * Lmax * WSLOTS);
+    int lo, hi;       // positions whose read base exists
+    if (!p.rc) { lo = p.start > 0 ? p.start : 0; hi = p.start + rl < L ? p.start + rl : L; }                       // rpos = pos - start
+    else { const int a = (int)K - 1 - p.start; lo = a - rl > 0 ? a - rl : 0; hi = a < L ? a : L; }                // rpos = K - 2 - pos - start
+    int q[MAX_EXTS];
+#pragma unroll
+    for (int l = 0; l < MAX_EXTS; ++l) q[l] = 0;
+    for (int pos = lo; pos < hi; ++pos) {
+        const int rpos = p.rc ? (int)K - 2 - pos - p.start : pos - p.start;
+        unsigned base = packed_base(rb, (uint64_t)rpos);
+        if (p.rc) base = 3u - base;                          // rbexts[l][s - pos - 1] is the complement of bexts[l][pos]
+        const int qual = rq[rpos];
+        const uint4 w = tab[pos];
+        const uint32_t ws[4] = {w.x, w.y, w.z, w.w};
+#pragma unroll
+        for (int l = 0; l < MAX_EXTS; ++l) q[l] += ((ws[l >> 2] >> (8 * (l & 3))) & 0xFFu) != base ? qual : 0;
+    }
+    const uint8_t* e = ei + (uint64_t)p.bv * WSLOTS;
+    int qq[MAX_EXTS];
+#pragma unroll
+    for (int j = 0; j < MAX_EXTS; ++j) qq[j] = 1000000000;
+#pragma unroll
+    for (int l = 0; l < MAX_EXTS; ++l) {
+        const int j = l < N ? (int)e[l] : -1;
+#pragma unroll
+        for (int jj = 0; jj < MAX_EXTS; ++jj) if (jj == j && q[l] < qq[jj]) qq[jj] = q[l];
+    }
+    int best = 0x7FFFFFFF, arg = 0;
+#pragma unroll
+    for (int j = 0; j < MAX_EXTS; ++j) if (j < n && qq[j] < best) { best = qq[j]; arg = j; }
+    int second = 0x7FFFFFFF;
+#pragma unroll
+    for (int j = 0; j < MAX_EXTS; ++j) if (j < n && j != arg && qq[j] < second) second = qq[j];
+    out[i] = best < second ? make_uint2(p.bv * WSLOTS + (uint32_t)arg, (uint32_t)(second - best)) : make_uint2(p.bv * WSLOTS, 0u);
+}
+
+// tile of 256 consecutive placements (sorted by vertex): thread (out-edge j, threshold d) walks the tile in LDS and adds a vertex's
+// partial sum to qsum[vertex][j][d] once per (tile, vertex): different addresses but for a vertex that spans several tiles
+__global__ __launch_bounds__(256) void k4_reduce(uint64_t NP, const uint2* __restrict__ sc, unsigned long long* __restrict__ qsum) {
+    __shared__ uint2 s[256];
+    const uint64_t base = (uint64_t)blockIdx.x * 256;
+    const unsigned t = threadIdx.x;
+    const unsigned cnt = NP - base < 256 ? (unsigned)(NP - base) : 256u;
+    if (t < cnt) s[t] = sc[base + t];
+    __syncthreads();
+    if (t >= NSUM) return;
+    const unsigned j = t >> 4, d = t & 15u;
+    unsigned long long acc = 0;
+    uint32_t cur = s[0].x / WSLOTS;
+    for (unsigned k = 0; k < cnt; ++k) {
+        const uint2 x = s[k];
+        const uint32_t bv = x.x / WSLOTS;
+        if (bv != cur) { if (acc) atomicAdd(&qsum[(uint64_t)cur * NSUM + t], acc); acc = 0; cur = bv; }
+        if ((x.x % WSLOTS) == j && x.y > d) acc += x.y;
+    }
+    if (acc) atomicAdd(&qsum[(uint64_t)cur * NSUM + t], acc);
+}
+
+// AnalyzeScores, version 3.  Sorting the sums is not needed: with top = the largest sum, the first r that passes deletes exactly the
+// out-edges whose sum is <= max_lose and <= top / min_ratio (sums sorted descending: whoever follows a passing rank passes too).
+__global__ __launch_bounds__(256) void k4_verdict(uint32_t B, const int32_t* __restrict__ bvert, GraphDev g, const int32_t* __restrict__ nwalks,
+                                                  const unsigned long long* __restrict__ qsum, uint8_t* __restrict__ dead) {
+    const uint32_t b = blockIdx.x * 256 + threadIdx.x;
+    if (b >= B || nwalks[b] > MAX_EXTS) return;
+    const int v = bvert[b];
+    const uint64_t f0 = g.from_off[v];
+    const int n = (int)(g.from_off[v + 1] - f0);
+    const unsigned long long* qs = qsum + (uint64_t)b * NSUM;
+    for (int d = 0; d <= MAX_DEL; ++d) {
+        unsigned long long top = 0;
+        for (int j = 0; j < n; ++j) top = qs[j * 16 + d] > top ? qs[j * 16 + d] : top;
+        if (top < (unsigned long long)MIN_WIN) continue;
+        bool any = false;
+        for (int j = 0; j < n; ++j) {
+            const unsigned long long x = qs[j * 16 + d];
+            if (x <= (unsigned long long)MAX_LOSE && top >= (unsigned long long)MIN_RATIO * x) {
+                const int e = g.from_e[f0 + j];
+                dead[e] = 1; dead[g.inv[e]] = 1;
+                any = true;
+            }
+        }
+        if (any) break;
+    }
+}
+
+// ---- read paths: Cleanup's truncation, RemoveUnneededVertices2's renumbering (first entry moves the offset, repeated ids collapse) and
+// CleanupCore's renumbering at once.  map[e] = the edge's final id, or -1 for an edge object the pass deleted; add[e] = offsets[e]
+__global__ __launch_bounds__(256) void k4_path_len(uint64_t n, const uint64_t* __restrict__ poff, const int32_t* __restrict__ pe,
+                                                   const int32_t* __restrict__ map, uint32_t* __restrict__ nlen) {
+    const uint64_t r = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (r >= n) return;
+    uint32_t k = 0; int32_t last = -1;
+    for (uint64_t i = poff[r]; i < poff[r + 1]; ++i) {
+        const int32_t m = map[pe[i]];
+        if (m < 0) break;
+        if (k == 0 || m != last) { ++k; last = m; }
+    }
+    nlen[r] = k;
+}
+__global__ __launch_bounds__(256) void k4_path_write(uint64_t n, const uint64_t* __restrict__ poff, const int32_t* __restrict__ pe, const int32_t* __restrict__ offs,
+                                                     const int32_t* __restrict__ map, const int32_t* __restrict__ add, const uint64_t* __restrict__ noff,
+                                                     int32_t* __restrict__ npe, int32_t* __restrict__ noffs) {
+    const uint64_t r = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (r >= n) return;
+    uint64_t o = noff[r]; const uint64_t o0 = o; int32_t last = -1;
+    int32_t off = offs[r];
+    for (uint64_t i = poff[r]; i < poff[r + 1]; ++i) {
+        const int32_t m = map[pe[i]];
+        if (m < 0) break;
+        if (o == o0) off += add[pe[i]];
+        if (o == o0 || m != last) { npe[o++] = m; last = m; }
+    }
+    noffs[r] = off;
+}
+
+// ---- the graph on the host (digraphE<basevector>: ordered adjacency lists, edge objects as base codes) -------------------------------
+struct HostGraph {
+    int K = 0;
+    std::vector<std::vector<int>> frm, frm_e, to, to_e;
+    std::vector<std::vector<uint8_t>> edges;
+    int kmers(int e) const { return (int)edges[e].size() - K + 1; }
+    void left_right(std::vector<int>& tl, std::vector<int>& tr) const {
+        tl.assign(edges.size(), -1); tr.assign(edges.size(), -1);
+        for (size_t v = 0; v < frm.size(); ++v) { for (int e : frm_e[v]) tl[e] = (int)v; for (int e : to_e[v]) tr[e] = (int)v; }
+    }
+    void used(std::vector<char>& u) const { u.assign(edges.size(), 0); for (auto& l : to_e) for (int e : l) u[e] = 1; }
+    void add_edge(int v, int w, std::vector<uint8_t>&& seq) {              // DigraphTemplate.h:1829-1839
+        const int n = (int)edges.size();
+        edges.push_back(std::move(seq));
+        const size_t i = std::upper_bound(frm[v].begin(), frm[v].end(), w) - frm[v].begin();
+        frm[v].insert(frm[v].begin() + i, w); frm_e[v].insert(frm_e[v].begin() + i, n);
+        const size_t j = std::upper_bound(to[w].begin(), to[w].end(), v) - to[w].begin();
+        to[w].insert(to[w].begin() + j, v); to_e[w].insert(to_e[w].begin() + j, n);
+    }
+    void delete_edges(const std::vector<char>& dead) {                     // DigraphTemplate.h:2017-2027: the lists keep their order
+        for (size_t v = 0; v < frm.size(); ++v) {
+            size_t k = 0;
+            for (size_t i = 0; i < frm_e[v].size(); ++i) if (!dead[frm_e[v][i]]) { frm[v][k] = frm[v][i]; frm_e[v][k] = frm_e[v][i]; ++k; }
+            frm[v].resize(k); frm_e[v].resize(k);
+            k = 0;
+            for (size_t i = 0; i < to_e[v].size(); ++i) if (!dead[to_e[v][i]]) { to[v][k] = to[v][i]; to_e[v][k] = to_e[v][i]; ++k; }
+            to[v].resize(k); to_e[v].resize(k);
+        }
+    }
+};
+
+// HyperBasevector::Involution (HyperBasevector.cc:648-660) for a graph whose edge sequences are distinct: the object holding the reverse complement
+int host_involution(const HostGraph& g, std::vector<int>& inv, std::string& err) {
+    std::unordered_map<std::string, int> where;
+    where.reserve(g.edges.size() * 2);
+    for (size_t e = 0; e < g.edges.size(); ++e) {
+        if (!where.emplace(std::string(g.edges[e].begin(), g.edges[e].end()), (int)e).second) { err = "Involution: two edge objects with the same sequence"; return W2RAP_E_GRAPH; }
+    }
+    inv.assign(g.edges.size(), -1);
+    std::string rc;
+    for (size_t e = 0; e < g.edges.size(); ++e) {
+        const auto& s = g.edges[e];
+        rc.resize(s.size());
+        for (size_t i = 0; i < s.size(); ++i) rc[i] = (char)(3 - s[s.size() - 1 - i]);
+        auto it = where.find(rc);
+        if (it == where.end()) { err = "Involution: an edge object has no reverse complement in the graph (HyperBasevector.cc:648-660 needs every edge's RC)"; return W2RAP_E_GRAPH; }
+        inv[e] = it->second;
+    }
+    return 0;
+}
+
+// one pass's edit.  in: dead[e] from the vote (ids of g).  out: the sorted unique deleted list, g and inv edited,
+// map[e] (old id -> final id, -1: deleted) and add[e] (offsets[e]) for the path kernels, the number of merged runs
+void edit_graph(HostGraph& g, std::vector<int>& inv, std::vector<char>& dead, unsigned min_size, bool edit, std::vector<int32_t>& deleted,
+                std::vector<int32_t>& map, std::vector<int32_t>& add, uint64_t& n_merged) {
+    const size_t NV = g.frm.size(), E0 = g.edges.size();
+    if (min_size > 0) {                                                      // Clean200.cc:370-380
+        for (size_t v = 0; v < NV; ++v) {
+            if (!g.to[v].empty() || g.frm[v].size() != 1) continue;
+            const int w = g.frm[v][0];
+            if ((int)v == w || g.to[w].size() != 1 || !g.frm[w].empty()) continue;
+            const int e = g.frm_e[v][0];
+            if (g.kmers(e) > (int)min_size) continue;
+            dead[e] = 1;
+        }
+    }
+    deleted.clear();
+    for (size_t e = 0; e < E0; ++e) if (dead[e]) deleted.push_back((int32_t)e);
+    n_merged = 0;
+    if (!edit) return;
+    g.delete_edges(dead);
+    // Cleanup: a path is cut at its first edge that is no longer in the graph (`alive` below)
+    std::vector<char> alive;
+    g.used(alive);
+    // RemoveUnneededVertices2
+    std::vector<int> to_left, to_right;
+    g.left_right(to_left, to_right);
+    std::vector<char> kill(NV, 0);
+    std::vector<int> queue;
+    for (size_t v = 0; v < NV; ++v)
+        if (g.frm[v].size() == 1 && g.to[v].size() == 1 && g.frm[v][0] != g.to[v][0] && !g.edges[g.frm_e[v][0]].empty() && !g.edges[g.to_e[v][0]].empty()) {
+            kill[v] = 1; queue.push_back((int)v);
+        }
+    std::vector<std::pair<int, int>> bound;
+    while (!queue.empty()) {
+        const int v = queue.back(); queue.pop_back();
+        if (!kill[v]) continue;
+        int eleft, vl = v;
+        do { kill[vl] = 0; eleft = g.to_e[vl][0]; vl = g.to[vl][0]; } while (kill[vl]);
+        int eright, vr = v;
+        do { kill[vr] = 0; eright = g.frm_e[vr][0]; vr = g.frm[vr][0]; } while (kill[vr]);
+        if (eleft < inv[eright]) { bound.emplace_back(eleft, eright); bound.emplace_back(inv[eright], inv[eleft]); }
+    }
+    std::vector<int> renum(E0), offsets(E0, 0), new_nos;
+    for (size_t e = 0; e < E0; ++e) renum[e] = (int)e;
+    std::vector<char> dead2(E0, 0);
+    while (!bound.empty()) {
+        const auto b = bound.back(); bound.pop_back();
+        const int new_no = (int)g.edges.size();
+        int off = g.kmers(b.first);
+        renum[b.first] = new_no; dead2[b.first] = 1;
+        for (int v = to_right[b.first]; v != to_right[b.second]; v = g.frm[v][0]) {
+            const int e = g.frm_e[v][0];
+            dead2[e] = 1; offsets[e] = off; renum[e] = new_no; off += g.kmers(e);
+        }
+        std::vector<uint8_t> ne(g.edges[b.first]);
+        ne.reserve((size_t)off + g.K - 1);
+        for (int v = to_right[b.first]; v != to_right[b.second]; v = g.frm[v][0]) {
+            const int e = g.frm_e[v][0];
+            ne.resize((size_t)offsets[e]);
+            ne.insert(ne.end(), g.edges[e].begin(), g.edges[e].end());
+        }
+        g.add_edge(to_left[b.first], to_right[b.second], std::move(ne));
+        new_nos.push_back(new_no);
+    }
+    n_merged = new_nos.size();
+    dead2.resize(g.edges.size(), 0);
+    g.delete_edges(dead2);
+    inv.resize(g.edges.size(), -1);
+    for (size_t k = 0; k + 1 < new_nos.size(); k += 2) { inv[new_nos[k]] = new_nos[k + 1]; inv[new_nos[k + 1]] = new_nos[k]; }
+    // CleanupCore
+    std::vector<char> u;
+    g.used(u);
+    std::vector<int> to_new(u.size(), -1);
+    int c = 0;
+    for (size_t i = 0; i < u.size(); ++i) if (u[i]) to_new[i] = c++;
+    std::vector<int> inv2; inv2.reserve(c);
+    for (size_t i = 0; i < u.size(); ++i) if (u[i]) inv2.push_back(inv[i] < 0 ? -1 : to_new[inv[i]]);
+    inv.swap(inv2);
+    std::vector<std::vector<uint8_t>> ed; ed.reserve(c);
+    for (size_t i = 0; i < u.size(); ++i) if (u[i]) ed.push_back(std::move(g.edges[i]));
+    g.edges.swap(ed);
+    std::vector<int> newv(NV, -1);
+    int nv = 0;
+    for (size_t v = 0; v < NV; ++v) if (!g.frm[v].empty() || !g.to[v].empty()) newv[v] = nv++;
+    HostGraph h; h.K = g.K;
+    h.frm.resize(nv); h.frm_e.resize(nv); h.to.resize(nv); h.to_e.resize(nv);
+    for (size_t v = 0; v < NV; ++v) {
+        if (newv[v] < 0) continue;
+        const int x = newv[v];
+        h.frm[x].swap(g.frm[v]); h.frm_e[x].swap(g.frm_e[v]); h.to[x].swap(g.to[v]); h.to_e[x].swap(g.to_e[v]);
+        for (auto& w : h.frm[x]) w = newv[w];
+        for (auto& w : h.to[x]) w = newv[w];
+        for (auto& e : h.frm_e[x]) e = to_new[e];
+        for (auto& e : h.to_e[x]) e = to_new[e];
+    }
+    h.edges.swap(g.edges);
+    g = std::move(h);
+    map.assign(E0, -1); add.assign(E0, 0);
+    for (size_t e = 0; e < E0; ++e) if (alive[e]) { map[e] = to_new[renum[e]]; add[e] = offsets[e]; }
+}
+
+void pack_edges(const HostGraph& g, std::vector<uint8_t>& packed, std::vector<uint64_t>& boff, std::vector<uint32_t>& len) {
+    const size_t E = g.edges.size();
+    boff.assign(E + 1, 0); len.resize(E);
+    for (size_t e = 0; e < E; ++e) { len[e] = (uint32_t)g.edges[e].size(); boff[e + 1] = boff[e] + (g.edges[e].size() + 3) / 4; }
+    packed.assign(boff[E], 0);
+    for (size_t e = 0; e < E; ++e) {
+        uint8_t* d = packed.data() + boff[e];
+        const auto& s = g.edges[e];
+        for (size_t i = 0; i < s.size(); ++i) d[i >> 2] |= (uint8_t)(s[i] << (2 * (i & 3)));
+    }
+}
+
+struct Csr { std::vector<uint64_t> from_off, to_off; std::vector<int32_t> from_v, from_e, to_v, to_e, vleft, vright; };
+void make_csr(const HostGraph& g, Csr& c) {
+    const size_t NV = g.frm.size(), E = g.edges.size();
+    c.from_off.assign(NV + 1, 0); c.to_off.assign(NV + 1, 0);
+    c.from_v.clear(); c.from_e.clear(); c.to_v.clear(); c.to_e.clear();
+    c.vleft.assign(E, -1); c.vright.assign(E, -1);
+    for (size_t v = 0; v < NV; ++v) {
+        for (size_t i = 0; i < g.frm[v].size(); ++i) { c.from_v.push_back(g.frm[v][i]); c.from_e.push_back(g.frm_e[v][i]); c.vleft[g.frm_e[v][i]] = (int32_t)v; }
+        for (size_t i = 0; i < g.to[v].size(); ++i) { c.to_v.push_back(g.to[v][i]); c.to_e.push_back(g.to_e[v][i]); c.vright[g.to_e[v][i]] = (int32_t)v; }
+        c.from_off[v + 1] = c.from_v.size(); c.to_off[v + 1] = c.to_v.size();
+    }
+}
+
+template <class T> T* host_copy(const std::vector<T>& v) {
+    T* p = (T*)host_result_alloc((v.size() ? v.size() : 1) * sizeof(T));
+    if (p && !v.empty()) std::memcpy(p, v.data(), v.size() * sizeof(T));
+    return p;
+}
+
+std::string g_profile4;
+
+struct Ms { float index = 0, vote = 0, paths = 0, host = 0; };
+
+int step4(Ctx& c, const w2rap_step4_in& in, const w2rap_step4_params& P, w2rap_step4_out& out) {
+    const bool vote_only = (P.flags & W2RAP_STEP4_VOTE_ONLY) != 0;
+    const unsigned K = (unsigned)in.K;
+    const uint64_t n = in.n_paths;
+    // ---- the graph on the host
+    HostGraph g; g.K = in.K;
+    {
+        const uint64_t NV = in.n_vertices, E = in.n_edge_objs;
+        g.frm.resize(NV); g.frm_e.resize(NV); g.to.resize(NV); g.to_e.resize(NV); g.edges.resize(E);
+        for (uint64_t e = 0; e < E; ++e) {
+            g.edges[e].resize(in.edge_len[e]);
+            const uint8_t* s = in.edge_packed + in.edge_byte_off[e];
+            for (uint32_t i = 0; i < in.edge_len[e]; ++i) g.edges[e][i] = (s[i >> 2] >> (2 * (i & 3))) & 3u;
+        }
+        std::vector<int> left(E, -1);
+        for (uint64_t v = 0; v < NV; ++v)
+            for (uint64_t i = in.from_off[v]; i < in.from_off[v + 1]; ++i) { g.frm[v].push_back(in.from_v[i]); g.frm_e[v].push_back(in.from_e[i]); left[in.from_e[i]] = (int)v; }
+        for (uint64_t v = 0; v < NV; ++v)
+            for (uint64_t i = in.to_off[v]; i < in.to_off[v + 1]; ++i) { g.to_e[v].push_back(in.to_e[i]); g.to[v].push_back(left[in.to_e[i]]); }
+    }
+    std::vector<int> inv;
+    if (in.inv) inv.assign(in.inv, in.inv + in.n_edge_objs);
+    else W2_TRY(host_involution(g, inv, c.err));
+    // ---- reads and paths on the device
+    ReadsDev R{};
+    {
+        uint8_t* b = nullptr; uint64_t* bo = nullptr; uint32_t* ln = nullptr; uint8_t* q = nullptr; uint64_t* qo = nullptr;
+        W2_TRY(up_pooled(c, &b, in.read_packed, n ? in.read_byte_off[n] : 0, 16));
+        W2_TRY(up_pooled(c, &bo, in.read_byte_off, in.read_byte_off ? n + 1 : 0));
+        W2_TRY(up_pooled(c, &ln, in.read_len, n));
+        W2_TRY(up_pooled(c, &q, in.quals, n ? in.qual_off[n] : 0, 16));
+        W2_TRY(up_pooled(c, &qo, in.qual_off, in.qual_off ? n + 1 : 0));
+        R = ReadsDev{b, bo, ln, q, qo};
+    }
+    int32_t* p_offset = nullptr; uint64_t* p_off = nullptr; int32_t* p_edges = nullptr;
+    uint64_t npe = n ? in.path_off[n] : 0;
+    W2_TRY(up_pooled(c, &p_offset, in.path_offset, n));
+    W2_TRY(up_pooled(c, &p_off, in.path_off, in.path_off ? n + 1 : 0));
+    W2_TRY(up_pooled(c, &p_edges, in.path_edges, npe));
+
+    std::vector<int32_t> deleted[2];
+    Ms ms[2];
+    const unsigned Lmax = (MAX_RL + K - 1 + 3) & ~3u;
+    for (int pass = 0; pass < (vote_only ? 1 : 2); ++pass) {
+        const uint64_t E = g.edges.size(), NV = g.frm.size();
+        std::vector<char> dead(E, 0);
+        // ---- this pass's graph on the device
+        std::vector<uint8_t> packed; std::vector<uint64_t> boff; std::vector<uint32_t> elen;
+        Csr csr;
+        std::vector<int32_t> bvert, boutdeg;
+        std::vector<Task> tasks;
+        pack_edges(g, packed, boff, elen);
+        make_csr(g, csr);
+        for (uint64_t v = 0; v < NV; ++v) {
+            if (g.to[v].empty() || g.frm[v].size() <= 1) continue;
+            const uint32_t b = (uint32_t)bvert.size();
+            bvert.push_back((int32_t)v); boutdeg.push_back((int32_t)g.frm[v].size());
+            for (int e : g.to_e[v]) tasks.push_back(Task{b, 0u, e, 0u});
+            for (int e : g.frm_e[v]) tasks.push_back(Task{b, 1u, e, 0u});
+            for (int e : g.to_e[v]) tasks.push_back(Task{b, 2u, inv[e], 0u});
+            for (int e : g.frm_e[v]) tasks.push_back(Task{b, 3u, inv[e], 0u});
+        }
+        const uint64_t B = bvert.size(), T = tasks.size();
+        if (B >= (1ull << 27)) { c.err = "more than 2^27 branch vertices"; return W2RAP_E_LIMIT; }
+        out.n_branch_vertices += B;
+        const size_t mark = c.owned.size();
+        uint64_t n_places = 0;
+        if (B) {
+            uint8_t* d_ebits = nullptr; uint64_t* d_ebyte = nullptr; uint32_t* d_elen = nullptr;
+            uint64_t *d_from_off = nullptr, *d_to_off = nullptr; int32_t *d_from_e = nullptr, *d_to_e = nullptr, *d_vright = nullptr, *d_inv = nullptr, *d_bvert = nullptr, *d_outdeg = nullptr;
+            Task* d_tasks = nullptr;
+            std::vector<int32_t> inv32(inv.begin(), inv.end());
+            W2_TRY(up_pooled(c, &d_ebits, packed.data(), packed.size(), 16));
+            W2_TRY(up_pooled(c, &d_ebyte, boff.data(), boff.size()));
+            W2_TRY(up_pooled(c, &d_elen, elen.data(), E));
+            W2_TRY(up_pooled(c, &d_from_off, csr.from_off.data(), NV + 1));
+            W2_TRY(up_pooled(c, &d_to_off, csr.to_off.data(), NV + 1));
+            W2_TRY(up_pooled(c, &d_from_e, csr.from_e.data(), csr.from_e.size()));
+            W2_TRY(up_pooled(c, &d_to_e, csr.to_e.data(), csr.to_e.size()));
+            W2_TRY(up_pooled(c, &d_vright, csr.vright.data(), E));
+            W2_TRY(up_pooled(c, &d_inv, inv32.data(), E));
+            W2_TRY(up_pooled(c, &d_bvert, bvert.data(), B));
+            W2_TRY(up_pooled(c, &d_outdeg, boutdeg.data(), B));
+            W2_TRY(up_pooled(c, &d_tasks, tasks.data(), T));
+            const GraphDev G{K, E, NV, d_elen, d_ebyte, d_ebits, d_from_off, d_from_e, d_to_off, d_to_e, d_vright, d_inv};
+            // ---- paths index
+            uint32_t *d_icnt = nullptr, *d_cursor = nullptr, *d_ilist = nullptr; uint64_t* d_ioff = nullptr;
+            {
+                Timer t(c.stream);
+                W2_ALLOC(d_icnt, uint32_t, E + 1); W2_ALLOC(d_cursor, uint32_t, E + 1); W2_ALLOC(d_ioff, uint64_t, E + 2); W2_ALLOC(d_ilist, uint32_t, npe + 1);
+                W2_HIP(hipMemsetAsync(d_icnt, 0, (E + 1) * 4, c.stream));
+                W2_HIP(hipMemsetAsync(d_cursor, 0, (E + 1) * 4, c.stream));
+                if (npe) LAUNCH(c, "k4_index_count", k4_index_count, dim3(grid4(npe)), dim3(256), 0, npe, (const int32_t*)p_edges, d_icnt);
+                W2_TRY(exclusive_scan_u32_to_u64(c, d_icnt, d_ioff, E));
+                if (npe) LAUNCH(c, "k4_index_fill", k4_index_fill, dim3(grid4(n)), dim3(256), 0, n, (const uint64_t*)p_off, (const int32_t*)p_edges, (const uint64_t*)d_ioff, d_cursor, d_ilist);
+                ms[pass].index = t.stop();
+            }
+            // ---- the vote
+            Timer tv(c.stream);
+            uint8_t *d_tabs = nullptr, *d_ei = nullptr, *d_dead = nullptr; int32_t *d_nwalks = nullptr, *d_depth = nullptr;
+            W2_ALLOC(d_tabs, uint8_t, B * (uint64_t)Lmax * WSLOTS + 16); W2_ALLOC(d_ei, uint8_t, B * WSLOTS); W2_ALLOC(d_nwalks, int32_t, B); W2_ALLOC(d_depth, int32_t, B);
+            W2_ALLOC(d_dead, uint8_t, E + 1);
+            W2_HIP(hipMemsetAsync(d_dead, 0, E + 1, c.stream));
+            W2_HIP(hipMemsetAsync(d_tabs, 0, B * (uint64_t)Lmax * WSLOTS + 16, c.stream));
+            W2_HIP(hipMemsetAsync(d_ei, 0xFF, B * WSLOTS, c.stream));
+            LAUNCH(c, "k4_walks", k4_walks, dim3((unsigned)B), dim3(64), 0, (uint32_t)B, (const int32_t*)d_bvert, G, Lmax, d_tabs, d_nwalks, d_depth, d_ei);
+            uint32_t* d_tcnt = nullptr; uint64_t* d_toff = nullptr;
+            W2_ALLOC(d_tcnt, uint32_t, T + 1); W2_ALLOC(d_toff, uint64_t, T + 2);
+            LAUNCH(c, "k4_item_count", k4_item_count, dim3(grid4(T)), dim3(256), 0, T, (const Task*)d_tasks, (const int32_t*)d_nwalks, (const uint32_t*)d_icnt, d_tcnt);
+            W2_TRY(exclusive_scan_u32_to_u64(c, d_tcnt, d_toff, T));
+            uint64_t n_items = 0;
+            W2_HIP(hipMemcpyAsync(&n_items, d_toff + T, 8, hipMemcpyDeviceToHost, c.stream));
+            W2_HIP(hipStreamSynchronize(c.stream));
+            if (n_items >= (1ull << 32) * 200) { c.err = "too many (vertex, read) pairs for one vote"; return W2RAP_E_LIMIT; }
+            if (n_items) {
+                uint32_t* d_pcnt = nullptr; uint64_t* d_poff = nullptr;
+                W2_ALLOC(d_pcnt, uint32_t, n_items + 1); W2_ALLOC(d_poff, uint64_t, n_items + 2);
+                const PlaceArgs A{T, n_items, d_tasks, d_toff, d_ioff, d_ilist, p_offset, p_off, p_edges, d_bvert};
+                LAUNCH(c, "k4_place_count", k4_place_count, dim3(grid4(n_items)), dim3(256), 0, A, G, d_pcnt);
+                W2_TRY(exclusive_scan_u32_to_u64(c, d_pcnt, d_poff, n_items));
+                W2_HIP(hipMemcpyAsync(&n_places, d_poff + n_items, 8, hipMemcpyDeviceToHost, c.stream));
+                W2_HIP(hipStreamSynchronize(c.stream));
+                if (n_places) {
+                    Place* d_places = nullptr; uint2* d_sc = nullptr; unsigned long long* d_qsum = nullptr;
+                    W2_ALLOC(d_places, Place, n_places); W2_ALLOC(d_sc, uint2, n_places); W2_ALLOC(d_qsum, unsigned long long, B * NSUM);
+                    W2_HIP(hipMemsetAsync(d_qsum, 0, B * NSUM * 8, c.stream));
+                    LAUNCH(c, "k4_place_fill", k4_place_fill, dim3(grid4(n_items)), dim3(256), 0, A, G, (const uint64_t*)d_poff, d_places);
+                    LAUNCH(c, "k4_score", k4_score, dim3(grid4(n_places)), dim3(256), 0, n_places, (const Place*)d_places, R, K, Lmax, (const uint8_t*)d_tabs,
+                           (const int32_t*)d_nwalks, (const int32_t*)d_depth, (const uint8_t*)d_ei, (const int32_t*)d_outdeg, d_sc);
+                    LAUNCH(c, "k4_reduce", k4_reduce, dim3(grid4(n_places)), dim3(256), 0, n_places, (const uint2*)d_sc, d_qsum);
+                    LAUNCH(c, "k4_verdict", k4_verdict, dim3(grid4(B)), dim3(256), 0, (uint32_t)B, (const int32_t*)d_bvert, G, (const int32_t*)d_nwalks,
+                           (const unsigned long long*)d_qsum, d_dead);
+                }
+            }
+            std::vector<int32_t> nw(B);
+            W2_HIP(hipMemcpyAsync(nw.data(), d_nwalks, B * 4, hipMemcpyDeviceToHost, c.stream));
+            W2_HIP(hipMemcpyAsync(dead.data(), d_dead, E, hipMemcpyDeviceToHost, c.stream));
+            ms[pass].vote = tv.stop();
+            W2_HIP(hipStreamSynchronize(c.stream));
+            for (int32_t x : nw) if (x > MAX_EXTS) ++out.n_skipped_too_many_exts;
+        }
+        out.n_placements += n_places;
+        // ---- the graph edit (host)
+        std::vector<int32_t> map, add;
+        uint64_t merged = 0;
+        {
+            const auto t0 = std::chrono::steady_clock::now();
+            edit_graph(g, inv, dead, P.min_size, !vote_only, deleted[pass], map, add, merged);
+            ms[pass].host = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        }
+        out.n_runs_merged[pass] = merged;
+        // ---- the read paths
+        if (!vote_only && n) {
+            Timer t(c.stream);
+            int32_t *d_map = nullptr, *d_add = nullptr, *n_offset = nullptr, *n_edges = nullptr; uint32_t* d_nlen = nullptr; uint64_t* n_off = nullptr;
+            W2_TRY(up_pooled(c, &d_map, map.data(), E));
+            W2_TRY(up_pooled(c, &d_add, add.data(), E));
+            W2_ALLOC(d_nlen, uint32_t, n + 1); W2_ALLOC(n_off, uint64_t, n + 2); W2_ALLOC(n_offset, int32_t, n + 1); W2_ALLOC(n_edges, int32_t, npe + 1);
+            LAUNCH(c, "k4_path_len", k4_path_len, dim3(grid4(n)), dim3(256), 0, n, (const uint64_t*)p_off, (const int32_t*)p_edges, (const int32_t*)d_map, d_nlen);
+            W2_TRY(exclusive_scan_u32_to_u64(c, d_nlen, n_off, n));
+            LAUNCH(c, "k4_path_write", k4_path_write, dim3(grid4(n)), dim3(256), 0, n, (const uint64_t*)p_off, (const int32_t*)p_edges, (const int32_t*)p_offset,
+                   (const int32_t*)d_map, (const int32_t*)d_add, (const uint64_t*)n_off, n_edges, n_offset);
+            W2_HIP(hipMemcpyAsync(&npe, n_off + n, 8, hipMemcpyDeviceToHost, c.stream));
+            ms[pass].paths = t.stop();
+            W2_HIP(hipStreamSynchronize(c.stream));
+            // the new paths replace the old ones; everything else of this pass goes back to the pool
+            std::vector<void*> keep = {n_offset, n_off, n_edges};
+            c.release(p_offset); c.release(p_off); c.release(p_edges);
+            p_offset = n_offset; p_off = n_off; p_edges = n_edges;
+            std::vector<void*> rest;
+            while (c.owned.size() > mark) { void* p = c.owned.back(); c.owned.pop_back(); if (std::find(keep.begin(), keep.end(), p) != keep.end()) rest.push_back(p); else c.park(p); }
+            for (void* p : rest) c.owned.push_back(p);
+        } else {
+            W2_HIP(hipStreamSynchronize(c.stream));
+            while (c.owned.size() > mark) { void* p = c.owned.back(); c.owned.pop_back(); c.park(p); }
+        }
+    }
+    // ---- results
+    out.K = in.K;
+    std::vector<uint8_t> packed; std::vector<uint64_t> boff; std::vector<uint32_t> elen;
+    Csr csr;
+    pack_edges(g, packed, boff, elen);
+    make_csr(g, csr);
+    out.n_vertices = g.frm.size(); out.n_edge_objs = g.edges.size();
+    out.edge_packed = host_copy(packed); out.edge_byte_off = host_copy(boff); out.edge_len = host_copy(elen);
+    out.vleft = host_copy(csr.vleft); out.vright = host_copy(csr.vright);
+    out.from_off = host_copy(csr.from_off); out.from_v = host_copy(csr.from_v); out.from_e = host_copy(csr.from_e);
+    out.to_off = host_copy(csr.to_off); out.to_v = host_copy(csr.to_v); out.to_e = host_copy(csr.to_e);
+    std::vector<int32_t> inv32(inv.begin(), inv.end());
+    out.inv = host_copy(inv32);
+    for (int k = 0; k < 2; ++k) {
+        out.n_deleted[k] = deleted[k].size(); out.deleted[k] = host_copy(deleted[k]);
+        out.ms_index[k] = ms[k].index; out.ms_vote[k] = ms[k].vote; out.ms_paths[k] = ms[k].paths; out.ms_graph_edit_host[k] = ms[k].host;
+    }
+    out.n_paths = n;
+    W2_TRY(dl(c, &out.path_offset, (const int32_t*)p_offset, n));
+    if (n) { W2_TRY(dl(c, &out.path_off, (const uint64_t*)p_off, n + 1)); }
+    else { out.path_off = (uint64_t*)host_result_alloc(8); if (out.path_off) out.path_off[0] = 0; }
+    W2_TRY(dl(c, &out.path_edges, (const int32_t*)p_edges, npe));
+    W2_HIP(hipStreamSynchronize(c.stream));
+    if (!out.edge_packed || !out.path_off || !out.inv) { c.err = "out of host memory"; return W2RAP_E_HIP; }
+    return 0;
+}
+
+}  // namespace
+}  // namespace w2
+
+using namespace w2;
+
+extern "C" {
+
+int w2rap_step4_run(const w2rap_step4_in* in, const w2rap_step4_params* P, w2rap_step4_out* out, char* err, size_t errlen) {
+    auto fail = [&](int code, const std::string& m) { if (err && errlen) std::snprintf(err, errlen, "%s", m.c_str()); return code; };
+    if (!in || !P || !out) return fail(W2RAP_E_ARG, "null argument");
+    std::memset(out, 0, sizeof(*out));
+    if (in->K < 16 || in->K > 640) return fail(W2RAP_E_ARG, "K must be in [16, 640] (the reference runs Step 4 at the large K, 200 by default)");
+    if (P->flags & ~W2RAP_STEP4_VOTE_ONLY) return fail(W2RAP_E_ARG, "unknown flag");
+    const uint64_t E = in->n_edge_objs, NV = in->n_vertices, n = in->n_paths;
+    if (E >= (1ull << 31) || NV >= (1ull << 31) || n >= (1ull << 32) - 2) return fail(W2RAP_E_LIMIT, "more than 2^31 edge objects or vertices, or 2^32 reads");
+    if (in->n_reads != n) return fail(W2RAP_E_ARG, "n_reads differs from n_paths: Step 4 needs the bases and qualities of every pathed read");
+    if (E && (!in->edge_packed || !in->edge_byte_off || !in->edge_len || !in->from_v || !in->from_e || !in->to_e)) return fail(W2RAP_E_ARG, "null graph array");
+    if (NV && (!in->from_off || !in->to_off)) return fail(W2RAP_E_ARG, "null adjacency offsets");
+    if (E && !NV) return fail(W2RAP_E_ARG, "edge objects without vertices");
+    if (n && (!in->path_offset || !in->path_off || !in->read_byte_off || !in->read_len || !in->qual_off)) return fail(W2RAP_E_ARG, "null input array");
+    if (E && in->edge_byte_off[0] != 0) return fail(W2RAP_E_ARG, "edge_byte_off must start at 0");
+    for (uint64_t o = 0; o < E; ++o) {
+        if (in->edge_len[o] < (uint32_t)in->K) return fail(W2RAP_E_ARG, "an edge object shorter than K bases");
+        if (in->edge_byte_off[o + 1] < in->edge_byte_off[o] || in->edge_byte_off[o + 1] - in->edge_byte_off[o] != ((uint64_t)in->edge_len[o] + 3) / 4)
+            return fail(W2RAP_E_ARG, "edge_byte_off does not match edge_len");
+    }
+    if (NV) {
+        if (in->from_off[0] != 0 || in->to_off[0] != 0) return fail(W2RAP_E_ARG, "from_off / to_off must start at 0");
+        for (uint64_t v = 0; v < NV; ++v) if (in->from_off[v + 1] < in->from_off[v] || in->to_off[v + 1] < in->to_off[v]) return fail(W2RAP_E_ARG, "from_off / to_off is not ascending");
+        if (in->from_off[NV] != E || in->to_off[NV] != E) return fail(W2RAP_E_ARG, "the adjacency lists do not hold every edge object once");
+        std::vector<char> sf(E, 0), st(E, 0);
+        for (uint64_t i = 0; i < E; ++i) {
+            if (in->from_v[i] < 0 || (uint64_t)in->from_v[i] >= NV) return fail(W2RAP_E_ARG, "from_v names a vertex that does not exist");
+            if (in->from_e[i] < 0 || (uint64_t)in->from_e[i] >= E || in->to_e[i] < 0 || (uint64_t)in->to_e[i] >= E) return fail(W2RAP_E_ARG, "the adjacency lists name an edge object that does not exist");
+            if (sf[in->from_e[i]]++ || st[in->to_e[i]]++) return fail(W2RAP_E_ARG, "the adjacency lists do not hold every edge object once");
+        }
+        std::vector<int32_t> right(E, -1);
+        for (uint64_t v = 0; v < NV; ++v) for (uint64_t i = in->to_off[v]; i < in->to_off[v + 1]; ++i) right[in->to_e[i]] = (int32_t)v;
+        for (uint64_t i = 0; i < E; ++i) if (right[in->from_e[i]] != in->from_v[i]) return fail(W2RAP_E_ARG, "from_v and to_e disagree about the vertex an edge enters");
+    }
+    if (in->inv) for (uint64_t e = 0; e < E; ++e) {
+        if (in->inv[e] < 0 || (uint64_t)in->inv[e] >= E || in->inv[in->inv[e]] != (int32_t)e) return fail(W2RAP_E_ARG, "inv is not an involution of the edge objects");
+        if (in->edge_len[in->inv[e]] != in->edge_len[e]) return fail(W2RAP_E_ARG, "inv pairs edge objects of different lengths");
+    }
+    if (n) {
+        if (in->path_off[0] != 0 || in->read_byte_off[0] != 0 || in->qual_off[0] != 0) return fail(W2RAP_E_ARG, "path_off, read_byte_off and qual_off must start at 0");
+        for (uint64_t r = 0; r < n; ++r) {
+            if (in->path_off[r + 1] < in->path_off[r]) return fail(W2RAP_E_ARG, "path_off is not ascending");
+            if (in->read_byte_off[r + 1] < in->read_byte_off[r] || in->read_byte_off[r + 1] - in->read_byte_off[r] != ((uint64_t)in->read_len[r] + 3) / 4)
+                return fail(W2RAP_E_ARG, "read_byte_off does not match read_len");
+            if (in->qual_off[r + 1] < in->qual_off[r] || in->qual_off[r + 1] - in->qual_off[r] != in->read_len[r]) return fail(W2RAP_E_ARG, "qual_off does not match read_len");
+        }
+        const uint64_t npe = in->path_off[n];
+        if (npe && !in->path_edges) return fail(W2RAP_E_ARG, "null path_edges");
+        if (in->read_byte_off[n] && !in->read_packed) return fail(W2RAP_E_ARG, "null read_packed");
+        if (in->qual_off[n] && !in->quals) return fail(W2RAP_E_ARG, "null quals");
+        for (uint64_t i = 0; i < npe; ++i) if (in->path_edges[i] < 0 || (uint64_t)in->path_edges[i] >= E) return fail(W2RAP_E_ARG, "a path names an edge object that does not exist");
+    }
+    char ebuf[512] = {0};
+    w2rap_step2_ctx* h = w2rap_step2_acquire(P->device, ebuf, sizeof ebuf);
+    if (!h) return fail(W2RAP_E_NO_DEVICE, ebuf);
+    Ctx& c = h->c;
+    c.prof_sums.clear();
+    int rc = step4(c, *in, *P, *out);
+    std::string msg = c.err;
+    (void)hipStreamSynchronize(c.stream);
+    c.presolve();
+    g_profile4.clear();
+    for (auto& s : c.prof_sums) { char line[256]; std::snprintf(line, sizeof line, "%s %.4f %llu\n", s.name.c_str(), s.ms, (unsigned long long)s.launches); g_profile4 += line; }
+    if (rc) w2rap_step2_destroy(h); else w2rap_step2_release(h);     // (a failed context is not cached)
+    if (rc) { w2rap_step4_free(out); return fail(rc, msg); }
+    return 0;
+}
+
+void w2rap_step4_free(w2rap_step4_out* o) {
+    if (!o) return;
+    for (void* p : {(void*)o->edge_packed, (void*)o->edge_byte_off, (void*)o->edge_len, (void*)o->vleft, (void*)o->vright, (void*)o->from_off, (void*)o->from_v,
+                    (void*)o->from_e, (void*)o->to_off, (void*)o->to_v, (void*)o->to_e, (void*)o->inv, (void*)o->path_offset, (void*)o->path_off, (void*)o->path_edges,
+                    (void*)o->deleted[0], (void*)o->deleted[1]})
+        std::free(p);
+    std::memset(o, 0, sizeof(*o));
+}
+
+size_t w2rap_step4_profile(char* buf, size_t len) {
+    if (buf && len) std::snprintf(buf, len, "%s", g_profile4.c_str());
+    return g_profile4.size() + 1;
+}
+
+}  // extern "C"

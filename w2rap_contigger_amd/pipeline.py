@@ -1,14 +1,15 @@
-"""Steps 1 to 3 of w2rap-contigger with the reference's flags and file names, on the GPU.
+"""Steps 1 to 4 of w2rap-contigger with the reference's flags and file names, on the GPU.
 
 Mirrors ``w2rap-contigger -r r1.fastq,r2.fastq -o OUT -p PREFIX [-K 200] [--min_freq 4] [--min_qual 7] --from_step A --to_step B`` for
-1 <= A <= B <= 3 (src/modules/w2rap-contigger.cc:300-383): consecutive steps run in one process hand their data over in HBM
+1 <= A <= B <= 4 (src/modules/w2rap-contigger.cc:300-409): consecutive steps run in one process hand their data over in HBM
 (w2rap_step1_run_into_step2, the staged Step-2 entry points, w2rap_step3_run_after_step2), a run that starts at step 2 or 3 loads the
 files the previous step wrote, and every step writes what the reference writes:
     step 1: OUT/frag_reads_orig.fastb, .qualp  -- ALWAYS (the reference writes them when `dump_all || to_step < 6`,
             w2rap-contigger.cc:312-318, and its steps 2..6 load them again, :322-328: a hand-over to `--from_step 4` needs them)
     step 2: OUT/PREFIX.small_K.hbv, .paths (last step or dump_all, :343-347), OUT/small_K.freqs (always, BuildReadQGraph.cc:1108)
-    step 3: OUT/PREFIX.large_K.hbv, .paths, OUT/PREFIX.first.frags.dist
-Steps 4-7 are the reference's (``w2rap-contigger ... --from_step 4``).  The HIP library is the only implementation (no CPU fallback).
+    step 3: OUT/PREFIX.large_K.hbv, .paths (last step or dump_all, :373-378), OUT/PREFIX.first.frags.dist
+    step 4: OUT/PREFIX.large_K.clean.hbv, .paths (-s / --min_size as in the reference; the graph edit of this step runs on the host, step4.py)
+Steps 5-7 are the reference's (``w2rap-contigger ... --from_step 5``).  The HIP library is the only implementation (no CPU fallback).
 
     python -m w2rap_contigger_amd.pipeline -r r1.fastq.gz,r2.fastq.gz -o OUT -p asm --from_step 1 --to_step 3
 """
@@ -18,12 +19,12 @@ import argparse
 import os
 import sys
 
-from . import formats as F, step1, step2, step3
+from . import formats as F, step1, step2, step3, step4
 
 
-def run(read_files, out_dir, prefix, large_k=200, min_freq=4, min_qual=7, from_step=1, to_step=3, dump_all=False, device=0, log=print, extend_paths=False):
-    if not (1 <= from_step <= to_step <= 3):
-        raise ValueError("steps 1..3 only (from_step <= to_step); steps 4-7 are the reference's")
+def run(read_files, out_dir, prefix, large_k=200, min_freq=4, min_qual=7, from_step=1, to_step=3, dump_all=False, device=0, log=print, extend_paths=False, min_size=0):
+    if not (1 <= from_step <= to_step <= 4):
+        raise ValueError("steps 1..4 only (from_step <= to_step); steps 5-7 are the reference's")
     os.makedirs(out_dir, exist_ok=True)
     pre = os.path.join(out_dir, prefix)
     out = {}
@@ -44,7 +45,7 @@ def run(read_files, out_dir, prefix, large_k=200, min_freq=4, min_qual=7, from_s
                 if not last:
                     ctx.set_reads_host(s1.packed, s1.byte_off, s1.read_len, quals=s1.quals, qual_off=s1.qual_off)
             out["step1"] = s1
-            # to_step <= 3 < 6: the reference always writes the read files here (w2rap-contigger.cc:312-318)
+            # to_step <= 4 < 6: the reference always writes the read files here (w2rap-contigger.cc:312-318)
             if True:
                 F.write_fastb(os.path.join(out_dir, "frag_reads_orig.fastb"), s1.packed, s1.byte_off, s1.read_len)
                 F.write_qualp_blobs(os.path.join(out_dir, "frag_reads_orig.qualp"), s1.pq, s1.pq_off)
@@ -66,23 +67,39 @@ def run(read_files, out_dir, prefix, large_k=200, min_freq=4, min_qual=7, from_s
                 F.write_hbv(pre + ".small_K.hbv", r2.hbv)
                 F.write_paths(pre + ".small_K.paths", r2.path_offset, r2.path_off, r2.path_edges)
             log(f"Building first graph DONE: {st['M']} k-mer instances, {st['S']} solid, {ctx.counts()['edge_objects']} edge objects")
-        if to_step == 3:
+        if from_step <= 3 <= to_step:
             log("--== Step 3: Repathing to second (large K) graph ==--")
             if from_step == 3:
                 r3 = step3.run_step3_files(out_dir, prefix, large_k, device, extend_paths=extend_paths)
             else:
                 r3 = step3.repath_after_step2(ctx, large_k, extend_paths=extend_paths)
-                F.write_hbv(pre + ".large_K.hbv", r3.hbv)
-                F.write_paths(pre + ".large_K.paths", r3.path_offset, r3.path_off, r3.path_edges)
+                if to_step == 3 or dump_all:                        # w2rap-contigger.cc:373
+                    F.write_hbv(pre + ".large_K.hbv", r3.hbv)
+                    F.write_paths(pre + ".large_K.paths", r3.path_offset, r3.path_off, r3.path_edges)
                 with open(pre + ".first.frags.dist", "w") as f:
                     f.write(step3.frags_text(r3.frag_count))
             out["step3"] = r3
             log(f"Repathing to second graph DONE: {r3.n_unique_places} unique places, {r3.hbv.n_edges} large-K edge objects")
+    if to_step == 4:
+        log("--== Step 4: Cleaning graph ==--")
+        if from_step == 4:
+            r4 = step4.run_step4_files(out_dir, prefix, min_size, device)
+        else:                                                       # the large-K graph and paths come back to the host between steps 3 and 4
+            r3 = out["step3"]
+            pk, bo, ln = F.read_fastb(os.path.join(out_dir, "frag_reads_orig.fastb"))
+            pq, po = F.read_qualp(os.path.join(out_dir, "frag_reads_orig.qualp"))
+            quals, qoff = F.qualp_to_raw(pq, po)
+            r4 = step4.clean200x(r3.hbv, (r3.path_offset, r3.path_off, r3.path_edges), pk, bo, ln, quals, qoff, min_size=min_size, device=device, inv=r3.inv2)
+            F.write_hbv(pre + ".large_K.clean.hbv", r4.hbv)
+            F.write_paths(pre + ".large_K.clean.paths", r4.path_offset, r4.path_off, r4.path_edges)
+        out["step4"] = r4
+        log(f"Cleaning graph DONE: {sum(r4.n_deleted)} edges deleted, {sum(r4.n_runs_merged)} runs merged, {r4.hbv.n_edges} edge objects "
+            f"(graph edit on the host: {sum(r4.ms_graph_edit_host):.1f} ms)")
     return out
 
 
 def main(argv=None) -> int:
-    ap = argparse.ArgumentParser(prog="python -m w2rap_contigger_amd.pipeline", description="w2rap-contigger steps 1-3 on the GPU")
+    ap = argparse.ArgumentParser(prog="python -m w2rap_contigger_amd.pipeline", description="w2rap-contigger steps 1-4 on the GPU")
     ap.add_argument("-r", "--read_files", default="")
     ap.add_argument("-o", "--out_dir", required=True)
     ap.add_argument("-p", "--prefix", required=True)
@@ -94,14 +111,15 @@ def main(argv=None) -> int:
     ap.add_argument("--dump_all", type=int, default=0)
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--extend_paths", default="0", help="the reference's --extend_paths (TCLAP bool: 0/1/true/false), Repath.cc:72-96")
-    for ignored in ("-t", "-m", "-d", "--tmp_dir", "-s", "--pair_sample"):       # the reference's resource flags: accepted, not needed here
+    ap.add_argument("-s", "--min_size", type=int, default=0, help="Step 4: delete components of one edge of at most this many K-mers")
+    for ignored in ("-t", "-m", "-d", "--tmp_dir", "--pair_sample"):       # the reference's resource flags: accepted, not needed here
         ap.add_argument(ignored, default=None, help=argparse.SUPPRESS)
     a = ap.parse_args(argv)
     if a.from_step == 1 and not a.read_files:
         ap.error("-r is required from step 1")
     try:
         run(a.read_files, a.out_dir, a.prefix, a.large_k, a.min_freq, a.min_qual, a.from_step, a.to_step, bool(a.dump_all), a.device,
-            extend_paths=str(a.extend_paths).lower() in ("1", "true"))
+            extend_paths=str(a.extend_paths).lower() in ("1", "true"), min_size=a.min_size)
     except (step2.Step2Error, ValueError, OSError) as e:
         print(f"w2rap pipeline: {e}", file=sys.stderr)
         return 1
