@@ -9,11 +9,16 @@
  * frag_reads_orig.fastb / .qualp hold (:322-328, :388-389); outputs are what BinaryWriter::writeFile(<prefix>.large_K.clean.hbv, hbvr)
  * and WriteReadPathVec(pathsr, <prefix>.large_K.clean.paths) serialise (:404-405).
  *
- * What runs where.  Everything proportional to the reads -- the paths index (invert(), VecUtilities.h:693-719), the placements of
- * reads on branch vertices, the quality-weighted vote, the verdict (AnalyzeScores) and the rewrite of the read paths -- runs in HIP
- * kernels for gfx950; there is no CPU fallback (W2RAP_E_NO_DEVICE).  The edit of the graph itself (DeleteEdges,
- * RemoveUnneededVertices2, CleanupCore: O(edges), serial in the reference, numbering defined by its stack order) runs on the host
- * inside the library; its time is reported separately (ms_graph_edit_host).
+ * What runs where.  Everything runs in HIP kernels for gfx950; there is no CPU fallback (W2RAP_E_NO_DEVICE).  The reads' side: the paths
+ * index (invert(), VecUtilities.h:693-719), the placements of reads on branch vertices, the quality-weighted vote, the verdict
+ * (AnalyzeScores) and the rewrite of the read paths.  The graph's side: min_size, DeleteEdges, RemoveUnneededVertices2 and CleanupCore
+ * (the k4e_* kernels), which reproduce the numbering the reference's two stacks define, and the branch-vertex and task lists of each
+ * pass.  The graph is uploaded once and downloaded once; between the two nothing of it crosses PCIe (the per-pass deleted lists, which
+ * are results, and a handful of counts come down).  Only the involution for in.inv == NULL is computed on the host, before the upload.
+ * The same edit exists on the host inside the library: W2RAP_STEP4_EDIT_ON_HOST forces it (the cross-check), and a call whose graph does
+ * not meet a precondition of the device edit -- adjacency lists sorted by neighbour vertex, as AddEdge keeps them; every merged run's
+ * mirror image is itself a run with the mirrored ends -- or has no edges falls back to it silently, with the same result.
+ * w2rap_step4_profile tells which one ran.
  *
  * Plain pointers and sizes; never throws; returns 0 or a W2RAP_E_* code (w2rap_step2.h) with a message in `err`.  Integer arithmetic
  * throughout: results are exact, byte for byte the reference's.
@@ -63,6 +68,7 @@ typedef struct w2rap_step4_params {
     uint32_t flags;
 } w2rap_step4_params;
 #define W2RAP_STEP4_VOTE_ONLY 1u     /* run pass 1's vote (and min_size), return its deleted list, edit nothing: the outputs hold the input graph and paths */
+#define W2RAP_STEP4_EDIT_ON_HOST 2u  /* edit the graph on the host (one pack, CSR and upload per pass, as before the device edit existed) */
 
 /* ---- outputs (library-allocated HOST memory; free with w2rap_step4_free) ---------------------------------------------------- */
 typedef struct w2rap_step4_out {
@@ -95,14 +101,17 @@ typedef struct w2rap_step4_out {
     uint64_t n_skipped_too_many_exts;/* of those: more than 10 walks (Clean200.cc:246) */
     uint64_t n_placements;           /* (read, start) placements scored, both passes */
     float ms_index[2], ms_vote[2], ms_paths[2];      /* device time per pass, milliseconds */
-    float ms_graph_edit_host[2];                     /* HOST time of the graph edit per pass, milliseconds */
+    float ms_graph_edit_host[2];                     /* HOST clock spent in the graph edit phase per pass, milliseconds: the edit itself with
+                                                        EDIT_ON_HOST; launching the k4e_* kernels and waiting for their counts without */
     void* _owner;                    /* internal */
 } w2rap_step4_out;
 
 int  w2rap_step4_run(const w2rap_step4_in* in, const w2rap_step4_params* params, w2rap_step4_out* out, char* err, size_t errlen);
 void w2rap_step4_free(w2rap_step4_out* out);
 
-/* per-kernel device time of the last w2rap_step4_run in this process: "kernel_name total_ms launches\n" lines; returns the bytes needed */
+/* per-kernel device time of the last w2rap_step4_run in this process: "kernel_name total_ms launches\n" lines; returns the bytes needed.
+ * The device edit's time is the sum of the k4e_* lines.  The last line, in the same format, is "edit_path_device <0|1> <passes>": 1 and
+ * the number of passes edited on the device, or 0 0 when the host edit ran (EDIT_ON_HOST, the fallback) or nothing was edited (VOTE_ONLY) */
 size_t w2rap_step4_profile(char* buf, size_t len);
 
 #ifdef __cplusplus

@@ -1,0 +1,107 @@
+"""Step 4's graph edit on the GPU (the k4e_* kernels): byte equality with the recorded runs of the unmodified reference, equality with the
+library's host edit in everything it returns, and the CPU model (tests/step4_model.py) as the judge on hand-made graphs, one rule of the
+reference's numbering each (tests/step4_edit_cases.py).  No comparison has a tolerance."""
+import os
+
+import numpy as np
+import pytest
+
+import step4_cases as S
+import step4_edit_cases as EC
+import step4_model as M
+from conftest import planted_reads
+from w2rap_contigger_amd import formats as F, step2, step3, step4
+
+pytestmark = pytest.mark.gpu
+
+
+def _k4e():
+    return {k: v for k, v in step4.profile().items() if k.startswith("k4e_")}
+
+
+def _same(res, m, vote_only=False):
+    assert F.hbv_to_bytes(res.hbv, zero_padding=True) == F.hbv_to_bytes(m.hbv, zero_padding=True), "graph differs from the model"
+    assert F.paths_to_bytes(res.path_offset, res.path_off, res.path_edges) == F.paths_to_bytes(m.path_offset, m.path_off, m.path_edges), "paths differ"
+    assert np.array_equal(res.inv, m.inv)
+    assert [list(x) for x in res.deleted] == m.deleted
+    c = m.counters
+    assert (res.n_branch_vertices, res.n_skipped_too_many_exts, res.n_placements) == (c.n_branch_vertices, c.n_skipped_too_many_exts, c.n_placements)
+    assert list(res.n_deleted[:1 if vote_only else 2]) == c.n_deleted
+    if not vote_only:
+        assert list(res.n_runs_merged) == c.n_runs_merged
+
+
+def _same_results(a, b):
+    """everything two runs of the library return, but the timings"""
+    assert F.hbv_to_bytes(a.hbv) == F.hbv_to_bytes(b.hbv), "graph bytes differ"
+    assert F.paths_to_bytes(a.path_offset, a.path_off, a.path_edges) == F.paths_to_bytes(b.path_offset, b.path_off, b.path_edges), "paths differ"
+    for f in ("vleft", "vright", "to_v", "inv"):
+        assert np.array_equal(getattr(a, f), getattr(b, f)), f
+    assert [list(x) for x in a.deleted] == [list(x) for x in b.deleted]
+    for f in ("n_deleted", "n_runs_merged", "n_branch_vertices", "n_skipped_too_many_exts", "n_placements"):
+        assert getattr(a, f) == getattr(b, f), f
+
+
+@pytest.mark.parametrize("name,min_size", S.CASES)
+def test_device_edit_equals_the_recorded_reference_and_the_host_edit(name, min_size, tmp_path):
+    d = str(tmp_path)
+    S.reference_run(name, min_size, d)
+    h, paths, (pk, bo, ln), quals = S.load(name)
+    dev = step4.clean200x(h, paths, pk, bo, ln, quals, min_size=min_size, edit="device")
+    k4e = _k4e()
+    assert dev.edit_on_device is True and k4e and all(v[1] >= 1 for v in k4e.values()), k4e
+    assert F.hbv_to_bytes(dev.hbv, zero_padding=True) == F.hbv_to_bytes(F.read_hbv(os.path.join(d, "t.large_K.clean.hbv")), zero_padding=True)
+    assert F.paths_to_bytes(dev.path_offset, dev.path_off, dev.path_edges) == open(os.path.join(d, "t.large_K.clean.paths"), "rb").read()
+    host = step4.clean200x(h, paths, pk, bo, ln, quals, min_size=min_size, edit="host")
+    assert host.edit_on_device is False and not _k4e()
+    _same_results(dev, host)
+
+
+@pytest.mark.parametrize("name", sorted(S.hand_cases()))
+def test_existing_hand_made_graphs_on_the_device(name):
+    h, paths, (pk, bo, ln), quals, ms = S.hand_cases()[name]
+    res = step4.clean200x(h, paths, pk, bo, ln, quals, min_size=ms, edit="device")
+    assert res.edit_on_device is True
+    _same(res, M.clean200x(h, None, paths, M.reads_of(pk, bo, ln, quals), ms))
+
+
+_EDIT_CASES = EC.edit_cases()
+
+
+@pytest.mark.parametrize("name", sorted(_EDIT_CASES))
+def test_edit_rules_on_both_paths(name):
+    h, paths, (pk, bo, ln), quals, ms = _EDIT_CASES[name].inputs
+    m = M.clean200x(h, None, paths, M.reads_of(pk, bo, ln, quals), ms)
+    dev = step4.clean200x(h, paths, pk, bo, ln, quals, min_size=ms, edit="device")
+    assert dev.edit_on_device is (not _EDIT_CASES[name].expect.get("unsorted", False))
+    _same(dev, m)
+    host = step4.clean200x(h, paths, pk, bo, ln, quals, min_size=ms, edit="host")
+    assert host.edit_on_device is False
+    _same(host, m)
+    _same_results(dev, host)
+
+
+def test_generated_reads_device_host_model():
+    """Steps 2 and 3 of this library on the planted workload with sequencing errors, then Step 4: device edit == host edit == model"""
+    r = planted_reads(40_000, 5)
+    r2 = step2.build_read_qgraph(r["pk"], r["bo"], r["ln"], quals=r["quals"], qual_off=r["off"], min_freq=2)
+    r3 = step3.repath_in_memory(r2.hbv, (r2.path_offset, r2.path_off, r2.path_edges), 200)
+    paths = (r3.path_offset, r3.path_off, r3.path_edges)
+    dev = step4.clean200x(r3.hbv, paths, r["pk"], r["bo"], r["ln"], r["quals"], inv=r3.inv2, edit="device")
+    assert dev.edit_on_device is True and _k4e()
+    host = step4.clean200x(r3.hbv, paths, r["pk"], r["bo"], r["ln"], r["quals"], inv=r3.inv2, edit="host")
+    m = M.clean200x(r3.hbv, r3.inv2, paths, M.Reads(r["codes"], r["quals"], r["off"].astype(np.int64)), 0)
+    print(f"generated: {r3.hbv.n_edges} edges, deleted {m.counters.n_deleted}, merged {m.counters.n_runs_merged}; k4e_* {sum(v[0] for v in _k4e().values()):.3f} ms")
+    assert sum(m.counters.n_runs_merged) > 0
+    _same(dev, m)
+    _same_results(dev, host)
+
+
+def test_vote_only_edits_nothing_on_the_device_path():
+    h, paths, (pk, bo, ln), quals = S.load("errs2")
+    res = step4.clean200x(h, paths, pk, bo, ln, quals, vote_only=True, edit="device")
+    m = M.clean200x(h, None, paths, M.reads_of(pk, bo, ln, quals), 0, vote_only=True)
+    assert len(m.deleted[0]) > 0
+    _same(res, m, vote_only=True)
+    assert F.hbv_to_bytes(res.hbv, zero_padding=True) == F.hbv_to_bytes(h, zero_padding=True)
+    assert F.paths_to_bytes(res.path_offset, res.path_off, res.path_edges) == F.paths_to_bytes(*paths)

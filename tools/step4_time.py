@@ -1,8 +1,9 @@
 """Times Step 4 (Clean200x) behind Steps 2 and 3 on the planted workload and prints one JSON line.
 
-    python tools/step4_time.py [--reads 4000000] [--seed 77] [--min_freq 4] [--min_size 0] [--repeats 3] [--reference]
+    python tools/step4_time.py [--reads 4000000] [--seed 77] [--min_freq 4] [--min_size 0] [--repeats 3] [--reference] [--host_edit]
 
-Per pass: ms_index, ms_vote, ms_paths (device events) and ms_graph_edit_host (host clock, NOT device time); placements per second of the
+Per pass: ms_index, ms_vote, ms_paths (device events) and ms_graph_edit_host (host clock, NOT device time); ms_k4e_sum, the device
+time of the graph edit's kernels (the k4e_* lines of the profile, both passes; 0 with --host_edit); placements per second of the
 scoring kernel; the per-kernel table of w2rap_step4_profile; the scoring kernel's bytes per second, loaded (mostly from L2) and compulsory
 (against the 8 TB/s HBM roof).  The figures are
 those of the LAST of --repeats runs (the first ones warm the context's memory pool).  --reference: the wall time of the reference's
@@ -33,6 +34,7 @@ def main():
     ap.add_argument("--min_size", type=int, default=0)
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--reference", action="store_true")
+    ap.add_argument("--host_edit", action="store_true", help="edit the graph on the host (W2RAP_STEP4_EDIT_ON_HOST)")
     a = ap.parse_args()
     import torch
     d = bench.planted_reads(a.reads, a.seed, torch.device("cuda", 0))
@@ -46,11 +48,16 @@ def main():
     r2 = step2.build_read_qgraph(pk, bo, ln, quals=quals, qual_off=off, min_freq=a.min_freq)
     r3 = step3.repath_in_memory(r2.hbv, (r2.path_offset, r2.path_off, r2.path_edges), 200)
     paths = (r3.path_offset, r3.path_off, r3.path_edges)
+    walls, k4e = [], []
     for _ in range(max(1, a.repeats)):
         t0 = time.perf_counter()
-        r4 = step4.clean200x(r3.hbv, paths, pk, bo, ln, quals, off, min_size=a.min_size, inv=r3.inv2)
+        r4 = step4.clean200x(r3.hbv, paths, pk, bo, ln, quals, off, min_size=a.min_size, inv=r3.inv2, edit="host" if a.host_edit else "device")
         wall = time.perf_counter() - t0
+        walls.append(round(wall, 4))
+        k4e.append(round(sum(v[0] for k, v in step4.profile().items() if k.startswith("k4e_")), 4))
+        print(f"call {len(walls)}: wall {wall:.4f} s, k4e_* {k4e[-1]:.4f} ms", file=sys.stderr)
     prof = step4.profile()
+    edit_path = prof.pop("edit_path_device", (0.0, 0))
     score_ms = prof.get("k4_score", (0.0, 0))[0]
     L = 250 + 200 - 1
     # Two byte counts for k4_score over both passes.  LOADED: what its threads ask for -- per scored position 16 B of walk table, 1 B of quality,
@@ -66,6 +73,8 @@ def main():
            "n_deleted": list(r4.n_deleted), "n_runs_merged": list(r4.n_runs_merged),
            "ms_index": [round(x, 3) for x in r4.ms_index], "ms_vote": [round(x, 3) for x in r4.ms_vote], "ms_paths": [round(x, 3) for x in r4.ms_paths],
            "ms_graph_edit_host": [round(x, 3) for x in r4.ms_graph_edit_host], "wall_s_call": round(wall, 4),
+           "wall_s_calls": walls, "ms_k4e_sum": k4e[-1], "ms_k4e_sum_calls": k4e, "edit_on_device": bool(r4.edit_on_device),
+           "edit_passes_on_device": int(edit_path[1]),
            "placements_per_s_k4_score": round(r4.n_placements / (score_ms * 1e-3), 1) if score_ms else None,
            "k4_score_loaded_bytes_per_s_mostly_L2": round(bytes_loaded / (score_ms * 1e-3), 1) if score_ms else None,
            "k4_score_compulsory_hbm_bytes_per_s": round(bytes_compulsory / (score_ms * 1e-3), 1) if score_ms else None,

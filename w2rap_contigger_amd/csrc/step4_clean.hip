@@ -9,8 +9,11 @@
 //   device  k4_score            per placement <= 10 running sums over <= 250 + K - 1 positions (:292-309, :341-359) -> (out-edge, margin)
 //   device  k4_reduce           the 16 threshold sums per (vertex, out-edge): a segmented reduction per tile of placements
 //   device  k4_verdict          AnalyzeScores (:391-443) -> a dead flag per edge object
-//   host    edit_graph          min_size (:370-380), DeleteEdges, RemoveUnneededVertices2 (GapToyTools3.cc:87-294), CleanupCore
-//                               (GapToyTools.cc:417-453): O(edges), the reference's numbering follows from its stack order
+//   device  k4e_*               the graph edit (step4_edit.hip): min_size (:370-380), DeleteEdges, RemoveUnneededVertices2
+//                               (GapToyTools3.cc:87-294), CleanupCore (GapToyTools.cc:417-453); the next pass's graph, branch vertices
+//                               and tasks are made on the device, nothing of the graph crosses PCIe between the upload and the download
+//   host    edit_graph          the same edit on the host: W2RAP_STEP4_EDIT_ON_HOST, and the fallback when a precondition of the device
+//                               edit does not hold (adjacency lists not sorted by neighbour, a run whose mirror is not a run)
 //   device  k4_path_len / scan / k4_path_write       Cleanup's truncation + both renumberings of the read paths in one go
 // Integer arithmetic throughout; the order in which placements are listed does not matter (only sums of margins are used).
 #include <algorithm>
@@ -19,7 +22,7 @@
 #include <string>
 #include <unordered_map>
 #include <vector>
-#include "ctx.h"
+#include "step4_edit.h"
 #include "../../include/w2rap_step4.h"
 
 namespace w2 {
@@ -31,7 +34,6 @@ constexpr unsigned NSUM = MAX_EXTS * (MAX_DEL + 1);   // threshold sums per bran
 
 inline unsigned grid4(uint64_t n, unsigned b = 256) { return (unsigned)((n + b - 1) / b); }
 
-struct Task { uint32_t bv; uint32_t role; int32_t edge; uint32_t pad; };     // role 0: in-edge, 1: out-edge, 2: inv[in-edge], 3: inv[out-edge]
 struct Place { uint32_t bv; uint32_t rid; int32_t start; uint32_t rc; };
 
 // ---- paths index ---------------------------------------------------------------------------------------------------------
@@ -489,11 +491,117 @@ template <class T> T* host_copy(const std::vector<T>& v) {
 std::string g_profile4;
 
 struct Ms { float index = 0, vote = 0, paths = 0, host = 0; };
+struct PathsDev { uint64_t n = 0, npe = 0; int32_t* offset = nullptr; uint64_t* off = nullptr; int32_t* edges = nullptr; };
 
+int upload_reads(Ctx& c, const w2rap_step4_in& in, ReadsDev& R, PathsDev& P) {
+    const uint64_t n = in.n_paths;
+    uint8_t* b = nullptr; uint64_t* bo = nullptr; uint32_t* ln = nullptr; uint8_t* q = nullptr; uint64_t* qo = nullptr;
+    W2_TRY(up_pooled(c, &b, in.read_packed, n ? in.read_byte_off[n] : 0, 16));
+    W2_TRY(up_pooled(c, &bo, in.read_byte_off, in.read_byte_off ? n + 1 : 0));
+    W2_TRY(up_pooled(c, &ln, in.read_len, n));
+    W2_TRY(up_pooled(c, &q, in.quals, n ? in.qual_off[n] : 0, 16));
+    W2_TRY(up_pooled(c, &qo, in.qual_off, in.qual_off ? n + 1 : 0));
+    R = ReadsDev{b, bo, ln, q, qo};
+    P.n = n; P.npe = n ? in.path_off[n] : 0;
+    W2_TRY(up_pooled(c, &P.offset, in.path_offset, n));
+    W2_TRY(up_pooled(c, &P.off, in.path_off, in.path_off ? n + 1 : 0));
+    W2_TRY(up_pooled(c, &P.edges, in.path_edges, P.npe));
+    return 0;
+}
+
+// one pass's paths index and vote: d_dead[e] (zeroed by the caller) is set for the edge objects the vote deletes
+int vote_pass(Ctx& c, const GraphDev& G, uint64_t B, uint64_t T, const int32_t* d_bvert, const int32_t* d_outdeg, const Task* d_tasks, const ReadsDev& R,
+              const PathsDev& P, unsigned Lmax, uint8_t* d_dead, Ms& ms, w2rap_step4_out& out) {
+    const uint64_t E = G.E, n = P.n, npe = P.npe;
+    const unsigned K = G.K;
+    uint64_t n_places = 0;
+    // ---- paths index
+    uint32_t *d_icnt = nullptr, *d_cursor = nullptr, *d_ilist = nullptr; uint64_t* d_ioff = nullptr;
+    {
+        Timer t(c.stream);
+        W2_ALLOC(d_icnt, uint32_t, E + 1); W2_ALLOC(d_cursor, uint32_t, E + 1); W2_ALLOC(d_ioff, uint64_t, E + 2); W2_ALLOC(d_ilist, uint32_t, npe + 1);
+        W2_HIP(hipMemsetAsync(d_icnt, 0, (E + 1) * 4, c.stream));
+        W2_HIP(hipMemsetAsync(d_cursor, 0, (E + 1) * 4, c.stream));
+        if (npe) LAUNCH(c, "k4_index_count", k4_index_count, dim3(grid4(npe)), dim3(256), 0, npe, (const int32_t*)P.edges, d_icnt);
+        W2_TRY(exclusive_scan_u32_to_u64(c, d_icnt, d_ioff, E));
+        if (npe) LAUNCH(c, "k4_index_fill", k4_index_fill, dim3(grid4(n)), dim3(256), 0, n, (const uint64_t*)P.off, (const int32_t*)P.edges, (const uint64_t*)d_ioff, d_cursor, d_ilist);
+        ms.index = t.stop();
+    }
+    // ---- the vote
+    Timer tv(c.stream);
+    uint8_t *d_tabs = nullptr, *d_ei = nullptr; int32_t *d_nwalks = nullptr, *d_depth = nullptr;
+    W2_ALLOC(d_tabs, uint8_t, B * (uint64_t)Lmax * WSLOTS + 16); W2_ALLOC(d_ei, uint8_t, B * WSLOTS); W2_ALLOC(d_nwalks, int32_t, B); W2_ALLOC(d_depth, int32_t, B);
+    W2_HIP(hipMemsetAsync(d_tabs, 0, B * (uint64_t)Lmax * WSLOTS + 16, c.stream));
+    W2_HIP(hipMemsetAsync(d_ei, 0xFF, B * WSLOTS, c.stream));
+    LAUNCH(c, "k4_walks", k4_walks, dim3((unsigned)B), dim3(64), 0, (uint32_t)B, d_bvert, G, Lmax, d_tabs, d_nwalks, d_depth, d_ei);
+    uint32_t* d_tcnt = nullptr; uint64_t* d_toff = nullptr;
+    W2_ALLOC(d_tcnt, uint32_t, T + 1); W2_ALLOC(d_toff, uint64_t, T + 2);
+    LAUNCH(c, "k4_item_count", k4_item_count, dim3(grid4(T)), dim3(256), 0, T, d_tasks, (const int32_t*)d_nwalks, (const uint32_t*)d_icnt, d_tcnt);
+    W2_TRY(exclusive_scan_u32_to_u64(c, d_tcnt, d_toff, T));
+    uint64_t n_items = 0;
+    W2_HIP(hipMemcpyAsync(&n_items, d_toff + T, 8, hipMemcpyDeviceToHost, c.stream));
+    W2_HIP(hipStreamSynchronize(c.stream));
+    if (n_items >= (1ull << 32) * 200) { c.err = "too many (vertex, read) pairs for one vote"; return W2RAP_E_LIMIT; }
+    if (n_items) {
+        uint32_t* d_pcnt = nullptr; uint64_t* d_poff = nullptr;
+        W2_ALLOC(d_pcnt, uint32_t, n_items + 1); W2_ALLOC(d_poff, uint64_t, n_items + 2);
+        const PlaceArgs A{T, n_items, d_tasks, d_toff, d_ioff, d_ilist, P.offset, P.off, P.edges, d_bvert};
+        LAUNCH(c, "k4_place_count", k4_place_count, dim3(grid4(n_items)), dim3(256), 0, A, G, d_pcnt);
+        W2_TRY(exclusive_scan_u32_to_u64(c, d_pcnt, d_poff, n_items));
+        W2_HIP(hipMemcpyAsync(&n_places, d_poff + n_items, 8, hipMemcpyDeviceToHost, c.stream));
+        W2_HIP(hipStreamSynchronize(c.stream));
+        if (n_places) {
+            Place* d_places = nullptr; uint2* d_sc = nullptr; unsigned long long* d_qsum = nullptr;
+            W2_ALLOC(d_places, Place, n_places); W2_ALLOC(d_sc, uint2, n_places); W2_ALLOC(d_qsum, unsigned long long, B * NSUM);
+            W2_HIP(hipMemsetAsync(d_qsum, 0, B * NSUM * 8, c.stream));
+            LAUNCH(c, "k4_place_fill", k4_place_fill, dim3(grid4(n_items)), dim3(256), 0, A, G, (const uint64_t*)d_poff, d_places);
+            LAUNCH(c, "k4_score", k4_score, dim3(grid4(n_places)), dim3(256), 0, n_places, (const Place*)d_places, R, K, Lmax, (const uint8_t*)d_tabs,
+                   (const int32_t*)d_nwalks, (const int32_t*)d_depth, (const uint8_t*)d_ei, d_outdeg, d_sc);
+            LAUNCH(c, "k4_reduce", k4_reduce, dim3(grid4(n_places)), dim3(256), 0, n_places, (const uint2*)d_sc, d_qsum);
+            LAUNCH(c, "k4_verdict", k4_verdict, dim3(grid4(B)), dim3(256), 0, (uint32_t)B, d_bvert, G, (const int32_t*)d_nwalks,
+                   (const unsigned long long*)d_qsum, d_dead);
+        }
+    }
+    std::vector<int32_t> nw(B);
+    W2_HIP(hipMemcpyAsync(nw.data(), d_nwalks, B * 4, hipMemcpyDeviceToHost, c.stream));
+    ms.vote = tv.stop();
+    W2_HIP(hipStreamSynchronize(c.stream));
+    for (int32_t x : nw) if (x > MAX_EXTS) ++out.n_skipped_too_many_exts;
+    out.n_placements += n_places;
+    return 0;
+}
+
+// the read paths of one pass through map[] / add[] (ids of that pass's input graph): fresh blocks in `np`
+int rewrite_paths(Ctx& c, const PathsDev& P, const int32_t* d_map, const int32_t* d_add, Ms& ms, PathsDev& np) {
+    const uint64_t n = P.n;
+    Timer t(c.stream);
+    uint32_t* d_nlen = nullptr;
+    np = PathsDev{}; np.n = n;
+    W2_ALLOC(d_nlen, uint32_t, n + 1); W2_ALLOC(np.off, uint64_t, n + 2); W2_ALLOC(np.offset, int32_t, n + 1); W2_ALLOC(np.edges, int32_t, P.npe + 1);
+    LAUNCH(c, "k4_path_len", k4_path_len, dim3(grid4(n)), dim3(256), 0, n, (const uint64_t*)P.off, (const int32_t*)P.edges, d_map, d_nlen);
+    W2_TRY(exclusive_scan_u32_to_u64(c, d_nlen, np.off, n));
+    LAUNCH(c, "k4_path_write", k4_path_write, dim3(grid4(n)), dim3(256), 0, n, (const uint64_t*)P.off, (const int32_t*)P.edges, (const int32_t*)P.offset,
+           d_map, d_add, (const uint64_t*)np.off, np.edges, np.offset);
+    W2_HIP(hipMemcpyAsync(&np.npe, np.off + n, 8, hipMemcpyDeviceToHost, c.stream));
+    ms.paths = t.stop();
+    W2_HIP(hipStreamSynchronize(c.stream));
+    return 0;
+}
+
+int download_paths(Ctx& c, const PathsDev& P, w2rap_step4_out& out) {
+    const uint64_t n = P.n;
+    out.n_paths = n;
+    W2_TRY(dl(c, &out.path_offset, (const int32_t*)P.offset, n));
+    if (n) { W2_TRY(dl(c, &out.path_off, (const uint64_t*)P.off, n + 1)); }
+    else { out.path_off = (uint64_t*)host_result_alloc(8); if (out.path_off) out.path_off[0] = 0; }
+    W2_TRY(dl(c, &out.path_edges, (const int32_t*)P.edges, P.npe));
+    return 0;
+}
+
+// ---- Step 4 with the graph edit on the host (W2RAP_STEP4_EDIT_ON_HOST, VOTE_ONLY, and the fallback of the device edit)
 int step4(Ctx& c, const w2rap_step4_in& in, const w2rap_step4_params& P, w2rap_step4_out& out) {
     const bool vote_only = (P.flags & W2RAP_STEP4_VOTE_ONLY) != 0;
     const unsigned K = (unsigned)in.K;
-    const uint64_t n = in.n_paths;
     // ---- the graph on the host
     HostGraph g; g.K = in.K;
     {
@@ -515,20 +623,9 @@ int step4(Ctx& c, const w2rap_step4_in& in, const w2rap_step4_params& P, w2rap_s
     else W2_TRY(host_involution(g, inv, c.err));
     // ---- reads and paths on the device
     ReadsDev R{};
-    {
-        uint8_t* b = nullptr; uint64_t* bo = nullptr; uint32_t* ln = nullptr; uint8_t* q = nullptr; uint64_t* qo = nullptr;
-        W2_TRY(up_pooled(c, &b, in.read_packed, n ? in.read_byte_off[n] : 0, 16));
-        W2_TRY(up_pooled(c, &bo, in.read_byte_off, in.read_byte_off ? n + 1 : 0));
-        W2_TRY(up_pooled(c, &ln, in.read_len, n));
-        W2_TRY(up_pooled(c, &q, in.quals, n ? in.qual_off[n] : 0, 16));
-        W2_TRY(up_pooled(c, &qo, in.qual_off, in.qual_off ? n + 1 : 0));
-        R = ReadsDev{b, bo, ln, q, qo};
-    }
-    int32_t* p_offset = nullptr; uint64_t* p_off = nullptr; int32_t* p_edges = nullptr;
-    uint64_t npe = n ? in.path_off[n] : 0;
-    W2_TRY(up_pooled(c, &p_offset, in.path_offset, n));
-    W2_TRY(up_pooled(c, &p_off, in.path_off, in.path_off ? n + 1 : 0));
-    W2_TRY(up_pooled(c, &p_edges, in.path_edges, npe));
+    PathsDev pd;
+    W2_TRY(upload_reads(c, in, R, pd));
+    const uint64_t n = pd.n;
 
     std::vector<int32_t> deleted[2];
     Ms ms[2];
@@ -556,7 +653,6 @@ int step4(Ctx& c, const w2rap_step4_in& in, const w2rap_step4_params& P, w2rap_s
         if (B >= (1ull << 27)) { c.err = "more than 2^27 branch vertices"; return W2RAP_E_LIMIT; }
         out.n_branch_vertices += B;
         const size_t mark = c.owned.size();
-        uint64_t n_places = 0;
         if (B) {
             uint8_t* d_ebits = nullptr; uint64_t* d_ebyte = nullptr; uint32_t* d_elen = nullptr;
             uint64_t *d_from_off = nullptr, *d_to_off = nullptr; int32_t *d_from_e = nullptr, *d_to_e = nullptr, *d_vright = nullptr, *d_inv = nullptr, *d_bvert = nullptr, *d_outdeg = nullptr;
@@ -575,63 +671,13 @@ int step4(Ctx& c, const w2rap_step4_in& in, const w2rap_step4_params& P, w2rap_s
             W2_TRY(up_pooled(c, &d_outdeg, boutdeg.data(), B));
             W2_TRY(up_pooled(c, &d_tasks, tasks.data(), T));
             const GraphDev G{K, E, NV, d_elen, d_ebyte, d_ebits, d_from_off, d_from_e, d_to_off, d_to_e, d_vright, d_inv};
-            // ---- paths index
-            uint32_t *d_icnt = nullptr, *d_cursor = nullptr, *d_ilist = nullptr; uint64_t* d_ioff = nullptr;
-            {
-                Timer t(c.stream);
-                W2_ALLOC(d_icnt, uint32_t, E + 1); W2_ALLOC(d_cursor, uint32_t, E + 1); W2_ALLOC(d_ioff, uint64_t, E + 2); W2_ALLOC(d_ilist, uint32_t, npe + 1);
-                W2_HIP(hipMemsetAsync(d_icnt, 0, (E + 1) * 4, c.stream));
-                W2_HIP(hipMemsetAsync(d_cursor, 0, (E + 1) * 4, c.stream));
-                if (npe) LAUNCH(c, "k4_index_count", k4_index_count, dim3(grid4(npe)), dim3(256), 0, npe, (const int32_t*)p_edges, d_icnt);
-                W2_TRY(exclusive_scan_u32_to_u64(c, d_icnt, d_ioff, E));
-                if (npe) LAUNCH(c, "k4_index_fill", k4_index_fill, dim3(grid4(n)), dim3(256), 0, n, (const uint64_t*)p_off, (const int32_t*)p_edges, (const uint64_t*)d_ioff, d_cursor, d_ilist);
-                ms[pass].index = t.stop();
-            }
-            // ---- the vote
-            Timer tv(c.stream);
-            uint8_t *d_tabs = nullptr, *d_ei = nullptr, *d_dead = nullptr; int32_t *d_nwalks = nullptr, *d_depth = nullptr;
-            W2_ALLOC(d_tabs, uint8_t, B * (uint64_t)Lmax * WSLOTS + 16); W2_ALLOC(d_ei, uint8_t, B * WSLOTS); W2_ALLOC(d_nwalks, int32_t, B); W2_ALLOC(d_depth, int32_t, B);
+            uint8_t* d_dead = nullptr;
             W2_ALLOC(d_dead, uint8_t, E + 1);
             W2_HIP(hipMemsetAsync(d_dead, 0, E + 1, c.stream));
-            W2_HIP(hipMemsetAsync(d_tabs, 0, B * (uint64_t)Lmax * WSLOTS + 16, c.stream));
-            W2_HIP(hipMemsetAsync(d_ei, 0xFF, B * WSLOTS, c.stream));
-            LAUNCH(c, "k4_walks", k4_walks, dim3((unsigned)B), dim3(64), 0, (uint32_t)B, (const int32_t*)d_bvert, G, Lmax, d_tabs, d_nwalks, d_depth, d_ei);
-            uint32_t* d_tcnt = nullptr; uint64_t* d_toff = nullptr;
-            W2_ALLOC(d_tcnt, uint32_t, T + 1); W2_ALLOC(d_toff, uint64_t, T + 2);
-            LAUNCH(c, "k4_item_count", k4_item_count, dim3(grid4(T)), dim3(256), 0, T, (const Task*)d_tasks, (const int32_t*)d_nwalks, (const uint32_t*)d_icnt, d_tcnt);
-            W2_TRY(exclusive_scan_u32_to_u64(c, d_tcnt, d_toff, T));
-            uint64_t n_items = 0;
-            W2_HIP(hipMemcpyAsync(&n_items, d_toff + T, 8, hipMemcpyDeviceToHost, c.stream));
-            W2_HIP(hipStreamSynchronize(c.stream));
-            if (n_items >= (1ull << 32) * 200) { c.err = "too many (vertex, read) pairs for one vote"; return W2RAP_E_LIMIT; }
-            if (n_items) {
-                uint32_t* d_pcnt = nullptr; uint64_t* d_poff = nullptr;
-                W2_ALLOC(d_pcnt, uint32_t, n_items + 1); W2_ALLOC(d_poff, uint64_t, n_items + 2);
-                const PlaceArgs A{T, n_items, d_tasks, d_toff, d_ioff, d_ilist, p_offset, p_off, p_edges, d_bvert};
-                LAUNCH(c, "k4_place_count", k4_place_count, dim3(grid4(n_items)), dim3(256), 0, A, G, d_pcnt);
-                W2_TRY(exclusive_scan_u32_to_u64(c, d_pcnt, d_poff, n_items));
-                W2_HIP(hipMemcpyAsync(&n_places, d_poff + n_items, 8, hipMemcpyDeviceToHost, c.stream));
-                W2_HIP(hipStreamSynchronize(c.stream));
-                if (n_places) {
-                    Place* d_places = nullptr; uint2* d_sc = nullptr; unsigned long long* d_qsum = nullptr;
-                    W2_ALLOC(d_places, Place, n_places); W2_ALLOC(d_sc, uint2, n_places); W2_ALLOC(d_qsum, unsigned long long, B * NSUM);
-                    W2_HIP(hipMemsetAsync(d_qsum, 0, B * NSUM * 8, c.stream));
-                    LAUNCH(c, "k4_place_fill", k4_place_fill, dim3(grid4(n_items)), dim3(256), 0, A, G, (const uint64_t*)d_poff, d_places);
-                    LAUNCH(c, "k4_score", k4_score, dim3(grid4(n_places)), dim3(256), 0, n_places, (const Place*)d_places, R, K, Lmax, (const uint8_t*)d_tabs,
-                           (const int32_t*)d_nwalks, (const int32_t*)d_depth, (const uint8_t*)d_ei, (const int32_t*)d_outdeg, d_sc);
-                    LAUNCH(c, "k4_reduce", k4_reduce, dim3(grid4(n_places)), dim3(256), 0, n_places, (const uint2*)d_sc, d_qsum);
-                    LAUNCH(c, "k4_verdict", k4_verdict, dim3(grid4(B)), dim3(256), 0, (uint32_t)B, (const int32_t*)d_bvert, G, (const int32_t*)d_nwalks,
-                           (const unsigned long long*)d_qsum, d_dead);
-                }
-            }
-            std::vector<int32_t> nw(B);
-            W2_HIP(hipMemcpyAsync(nw.data(), d_nwalks, B * 4, hipMemcpyDeviceToHost, c.stream));
+            W2_TRY(vote_pass(c, G, B, T, d_bvert, d_outdeg, d_tasks, R, pd, Lmax, d_dead, ms[pass], out));
             W2_HIP(hipMemcpyAsync(dead.data(), d_dead, E, hipMemcpyDeviceToHost, c.stream));
-            ms[pass].vote = tv.stop();
             W2_HIP(hipStreamSynchronize(c.stream));
-            for (int32_t x : nw) if (x > MAX_EXTS) ++out.n_skipped_too_many_exts;
         }
-        out.n_placements += n_places;
         // ---- the graph edit (host)
         std::vector<int32_t> map, add;
         uint64_t merged = 0;
@@ -643,22 +689,15 @@ int step4(Ctx& c, const w2rap_step4_in& in, const w2rap_step4_params& P, w2rap_s
         out.n_runs_merged[pass] = merged;
         // ---- the read paths
         if (!vote_only && n) {
-            Timer t(c.stream);
-            int32_t *d_map = nullptr, *d_add = nullptr, *n_offset = nullptr, *n_edges = nullptr; uint32_t* d_nlen = nullptr; uint64_t* n_off = nullptr;
+            int32_t *d_map = nullptr, *d_add = nullptr;
             W2_TRY(up_pooled(c, &d_map, map.data(), E));
             W2_TRY(up_pooled(c, &d_add, add.data(), E));
-            W2_ALLOC(d_nlen, uint32_t, n + 1); W2_ALLOC(n_off, uint64_t, n + 2); W2_ALLOC(n_offset, int32_t, n + 1); W2_ALLOC(n_edges, int32_t, npe + 1);
-            LAUNCH(c, "k4_path_len", k4_path_len, dim3(grid4(n)), dim3(256), 0, n, (const uint64_t*)p_off, (const int32_t*)p_edges, (const int32_t*)d_map, d_nlen);
-            W2_TRY(exclusive_scan_u32_to_u64(c, d_nlen, n_off, n));
-            LAUNCH(c, "k4_path_write", k4_path_write, dim3(grid4(n)), dim3(256), 0, n, (const uint64_t*)p_off, (const int32_t*)p_edges, (const int32_t*)p_offset,
-                   (const int32_t*)d_map, (const int32_t*)d_add, (const uint64_t*)n_off, n_edges, n_offset);
-            W2_HIP(hipMemcpyAsync(&npe, n_off + n, 8, hipMemcpyDeviceToHost, c.stream));
-            ms[pass].paths = t.stop();
-            W2_HIP(hipStreamSynchronize(c.stream));
+            PathsDev np;
+            W2_TRY(rewrite_paths(c, pd, d_map, d_add, ms[pass], np));
             // the new paths replace the old ones; everything else of this pass goes back to the pool
-            std::vector<void*> keep = {n_offset, n_off, n_edges};
-            c.release(p_offset); c.release(p_off); c.release(p_edges);
-            p_offset = n_offset; p_off = n_off; p_edges = n_edges;
+            std::vector<void*> keep = {np.offset, np.off, np.edges};
+            c.release(pd.offset); c.release(pd.off); c.release(pd.edges);
+            pd = np;
             std::vector<void*> rest;
             while (c.owned.size() > mark) { void* p = c.owned.back(); c.owned.pop_back(); if (std::find(keep.begin(), keep.end(), p) != keep.end()) rest.push_back(p); else c.park(p); }
             for (void* p : rest) c.owned.push_back(p);
@@ -684,11 +723,121 @@ int step4(Ctx& c, const w2rap_step4_in& in, const w2rap_step4_params& P, w2rap_s
         out.n_deleted[k] = deleted[k].size(); out.deleted[k] = host_copy(deleted[k]);
         out.ms_index[k] = ms[k].index; out.ms_vote[k] = ms[k].vote; out.ms_paths[k] = ms[k].paths; out.ms_graph_edit_host[k] = ms[k].host;
     }
-    out.n_paths = n;
-    W2_TRY(dl(c, &out.path_offset, (const int32_t*)p_offset, n));
-    if (n) { W2_TRY(dl(c, &out.path_off, (const uint64_t*)p_off, n + 1)); }
-    else { out.path_off = (uint64_t*)host_result_alloc(8); if (out.path_off) out.path_off[0] = 0; }
-    W2_TRY(dl(c, &out.path_edges, (const int32_t*)p_edges, npe));
+    W2_TRY(download_paths(c, pd, out));
+    W2_HIP(hipStreamSynchronize(c.stream));
+    if (!out.edge_packed || !out.path_off || !out.inv) { c.err = "out of host memory"; return W2RAP_E_HIP; }
+    return 0;
+}
+
+// ---- Step 4 with the graph edit on the device: one upload, two passes in HBM, one download.  EDIT4_FALLBACK: a precondition of the
+// device edit does not hold (nothing of `out` is to be used; the caller runs step4() instead)
+int step4_device(Ctx& c, const w2rap_step4_in& in, const w2rap_step4_params& P, w2rap_step4_out& out) {
+    const unsigned K = (unsigned)in.K;
+    const uint64_t E0 = in.n_edge_objs, NV0 = in.n_vertices;
+    // ---- the involution and both ends of every edge (host, once, before the upload)
+    std::vector<int32_t> inv32, vleft(E0, -1), vright(E0, -1), to_v(E0, -1);
+    if (in.inv) inv32.assign(in.inv, in.inv + E0);
+    else {
+        HostGraph hg; hg.K = in.K; hg.edges.resize(E0);
+        for (uint64_t e = 0; e < E0; ++e) {
+            hg.edges[e].resize(in.edge_len[e]);
+            const uint8_t* s = in.edge_packed + in.edge_byte_off[e];
+            for (uint32_t i = 0; i < in.edge_len[e]; ++i) hg.edges[e][i] = (s[i >> 2] >> (2 * (i & 3))) & 3u;
+        }
+        std::vector<int> inv;
+        W2_TRY(host_involution(hg, inv, c.err));
+        inv32.assign(inv.begin(), inv.end());
+    }
+    for (uint64_t v = 0; v < NV0; ++v) {
+        for (uint64_t i = in.from_off[v]; i < in.from_off[v + 1]; ++i) vleft[in.from_e[i]] = (int32_t)v;
+        for (uint64_t i = in.to_off[v]; i < in.to_off[v + 1]; ++i) vright[in.to_e[i]] = (int32_t)v;
+    }
+    for (uint64_t i = 0; i < E0; ++i) to_v[i] = vleft[in.to_e[i]];
+    Graph4 g; g.K = K; g.E = E0; g.NV = NV0; g.ebytes_cap = E0 ? in.edge_byte_off[E0] : 0;
+    W2_TRY(up_pooled(c, &g.ebits, in.edge_packed, g.ebytes_cap, 32));
+    W2_TRY(up_pooled(c, &g.ebyte, in.edge_byte_off, in.edge_byte_off ? E0 + 1 : 0));
+    W2_TRY(up_pooled(c, &g.elen, in.edge_len, E0));
+    W2_TRY(up_pooled(c, &g.from_off, in.from_off, in.from_off ? NV0 + 1 : 0));
+    W2_TRY(up_pooled(c, &g.from_v, in.from_v, E0));
+    W2_TRY(up_pooled(c, &g.from_e, in.from_e, E0));
+    W2_TRY(up_pooled(c, &g.to_off, in.to_off, in.to_off ? NV0 + 1 : 0));
+    W2_TRY(up_pooled(c, &g.to_v, (const int32_t*)to_v.data(), E0));
+    W2_TRY(up_pooled(c, &g.to_e, in.to_e, E0));
+    W2_TRY(up_pooled(c, &g.vleft, (const int32_t*)vleft.data(), E0));
+    W2_TRY(up_pooled(c, &g.vright, (const int32_t*)vright.data(), E0));
+    W2_TRY(up_pooled(c, &g.inv, (const int32_t*)inv32.data(), E0));
+    ReadsDev R{};
+    PathsDev pd;
+    W2_TRY(upload_reads(c, in, R, pd));
+    W2_HIP(hipStreamSynchronize(c.stream));                     // (the host vectors above have been read)
+
+    std::vector<int32_t> deleted[2];
+    Ms ms[2];
+    const unsigned Lmax = (MAX_RL + K - 1 + 3) & ~3u;
+    for (int pass = 0; pass < 2; ++pass) {
+        const std::vector<void*> before = c.owned;
+        const uint64_t E = g.E, NV = g.NV;
+        int32_t *d_bvert = nullptr, *d_outdeg = nullptr; Task* d_tasks = nullptr;
+        uint64_t B = 0, T = 0; bool sorted = true;
+        W2_TRY(edit4_tasks(c, g, &d_bvert, &d_outdeg, &d_tasks, &B, &T, &sorted));
+        if (!sorted) return EDIT4_FALLBACK;
+        if (B >= (1ull << 27)) { c.err = "more than 2^27 branch vertices"; return W2RAP_E_LIMIT; }
+        out.n_branch_vertices += B;
+        uint8_t* d_dead = nullptr;
+        W2_ALLOC(d_dead, uint8_t, E + 1);
+        W2_HIP(hipMemsetAsync(d_dead, 0, E + 1, c.stream));
+        if (B) {
+            const GraphDev G{K, E, NV, g.elen, g.ebyte, g.ebits, g.from_off, g.from_e, g.to_off, g.to_e, g.vright, g.inv};
+            W2_TRY(vote_pass(c, G, B, T, d_bvert, d_outdeg, d_tasks, R, pd, Lmax, d_dead, ms[pass], out));
+        }
+        // ---- the graph edit (device)
+        Graph4 next;
+        int32_t *d_map = nullptr, *d_add = nullptr;
+        uint64_t merged = 0;
+        {
+            const auto t0 = std::chrono::steady_clock::now();
+            W2_TRY(edit4_pass(c, g, d_dead, P.min_size, &next, &d_map, &d_add, &deleted[pass], &merged));
+            ms[pass].host = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        }
+        out.n_runs_merged[pass] = merged;
+        // ---- the read paths
+        std::vector<void*> gone = {g.ebits, g.ebyte, g.elen, g.from_off, g.from_v, g.from_e, g.to_off, g.to_v, g.to_e, g.vleft, g.vright, g.inv};
+        std::vector<void*> keep = {next.ebits, next.ebyte, next.elen, next.from_off, next.from_v, next.from_e, next.to_off, next.to_v, next.to_e, next.vleft, next.vright, next.inv};
+        if (pd.n) {
+            PathsDev np;
+            W2_TRY(rewrite_paths(c, pd, d_map, d_add, ms[pass], np));
+            gone.insert(gone.end(), {(void*)pd.offset, (void*)pd.off, (void*)pd.edges});
+            keep.insert(keep.end(), {(void*)np.offset, (void*)np.off, (void*)np.edges});
+            pd = np;
+        }
+        W2_HIP(hipStreamSynchronize(c.stream));
+        g = next;
+        // the new graph and paths replace the old ones; everything else of this pass goes back to the pool
+        std::vector<void*> owned;
+        for (void* p : c.owned) {
+            const bool was = std::find(before.begin(), before.end(), p) != before.end();
+            const bool stays = was ? std::find(gone.begin(), gone.end(), p) == gone.end() : std::find(keep.begin(), keep.end(), p) != keep.end();
+            if (stays) owned.push_back(p); else c.park(p);
+        }
+        c.owned.swap(owned);
+    }
+    // ---- results: the one download of the graph
+    out.K = in.K;
+    const uint64_t E = g.E, NV = g.NV;
+    out.n_vertices = NV; out.n_edge_objs = E;
+    W2_TRY(dl(c, &out.edge_byte_off, (const uint64_t*)g.ebyte, E + 1));
+    W2_TRY(dl(c, &out.edge_len, (const uint32_t*)g.elen, E));
+    W2_TRY(dl(c, &out.vleft, (const int32_t*)g.vleft, E)); W2_TRY(dl(c, &out.vright, (const int32_t*)g.vright, E));
+    W2_TRY(dl(c, &out.from_off, (const uint64_t*)g.from_off, NV + 1)); W2_TRY(dl(c, &out.from_v, (const int32_t*)g.from_v, E)); W2_TRY(dl(c, &out.from_e, (const int32_t*)g.from_e, E));
+    W2_TRY(dl(c, &out.to_off, (const uint64_t*)g.to_off, NV + 1)); W2_TRY(dl(c, &out.to_v, (const int32_t*)g.to_v, E)); W2_TRY(dl(c, &out.to_e, (const int32_t*)g.to_e, E));
+    W2_TRY(dl(c, &out.inv, (const int32_t*)g.inv, E));
+    W2_HIP(hipStreamSynchronize(c.stream));
+    W2_TRY(dl(c, &out.edge_packed, (const uint8_t*)g.ebits, out.edge_byte_off[E]));
+    for (int k = 0; k < 2; ++k) {
+        out.n_deleted[k] = deleted[k].size(); out.deleted[k] = host_copy(deleted[k]);
+        out.ms_index[k] = ms[k].index; out.ms_vote[k] = ms[k].vote; out.ms_paths[k] = ms[k].paths; out.ms_graph_edit_host[k] = ms[k].host;
+    }
+    W2_TRY(download_paths(c, pd, out));
     W2_HIP(hipStreamSynchronize(c.stream));
     if (!out.edge_packed || !out.path_off || !out.inv) { c.err = "out of host memory"; return W2RAP_E_HIP; }
     return 0;
@@ -706,7 +855,7 @@ int w2rap_step4_run(const w2rap_step4_in* in, const w2rap_step4_params* P, w2rap
     if (!in || !P || !out) return fail(W2RAP_E_ARG, "null argument");
     std::memset(out, 0, sizeof(*out));
     if (in->K < 16 || in->K > 640) return fail(W2RAP_E_ARG, "K must be in [16, 640] (the reference runs Step 4 at the large K, 200 by default)");
-    if (P->flags & ~W2RAP_STEP4_VOTE_ONLY) return fail(W2RAP_E_ARG, "unknown flag");
+    if (P->flags & ~(W2RAP_STEP4_VOTE_ONLY | W2RAP_STEP4_EDIT_ON_HOST)) return fail(W2RAP_E_ARG, "unknown flag");
     const uint64_t E = in->n_edge_objs, NV = in->n_vertices, n = in->n_paths;
     if (E >= (1ull << 31) || NV >= (1ull << 31) || n >= (1ull << 32) - 2) return fail(W2RAP_E_LIMIT, "more than 2^31 edge objects or vertices, or 2^32 reads");
     if (in->n_reads != n) return fail(W2RAP_E_ARG, "n_reads differs from n_paths: Step 4 needs the bases and qualities of every pathed read");
@@ -757,12 +906,28 @@ int w2rap_step4_run(const w2rap_step4_in* in, const w2rap_step4_params* P, w2rap
     if (!h) return fail(W2RAP_E_NO_DEVICE, ebuf);
     Ctx& c = h->c;
     c.prof_sums.clear();
-    int rc = step4(c, *in, *P, *out);
+    // VOTE_ONLY edits nothing, on either path
+    bool on_device = !(P->flags & (W2RAP_STEP4_EDIT_ON_HOST | W2RAP_STEP4_VOTE_ONLY));
+    int rc = 0;
+    if (on_device) {
+        rc = step4_device(c, *in, *P, *out);
+        if (rc == EDIT4_FALLBACK) {                              // start over with the host edit: same result, nothing kept from this attempt
+            on_device = false;
+            (void)hipStreamSynchronize(c.stream);
+            c.presolve();
+            c.prof_sums.clear();
+            c.free_all();
+            c.err.clear();
+            w2rap_step4_free(out);
+        }
+    }
+    if (!on_device) rc = step4(c, *in, *P, *out);
     std::string msg = c.err;
     (void)hipStreamSynchronize(c.stream);
     c.presolve();
     g_profile4.clear();
     for (auto& s : c.prof_sums) { char line[256]; std::snprintf(line, sizeof line, "%s %.4f %llu\n", s.name.c_str(), s.ms, (unsigned long long)s.launches); g_profile4 += line; }
+    { char line[64]; std::snprintf(line, sizeof line, "edit_path_device %d %d\n", on_device ? 1 : 0, on_device ? 2 : 0); g_profile4 += line; }
     if (rc) w2rap_step2_destroy(h); else w2rap_step2_release(h);     // (a failed context is not cached)
     if (rc) { w2rap_step4_free(out); return fail(rc, msg); }
     return 0;

@@ -2,10 +2,10 @@
 //
 // Drop-in for `w2rap-contigger --from_step 4 --to_step 4` (src/modules/w2rap-contigger.cc:386-409): reads
 // <out_dir>/<prefix>.large_K.{hbv,paths} written by Step 3 and <out_dir>/frag_reads_orig.{fastb,qualp} written by Step 1, writes
-// <out_dir>/<prefix>.large_K.clean.{hbv,paths} that Step 5 (`--from_step 5`) loads.  The vote and the path rewrite run in
-// libw2rap_step2.so (HIP); the graph edit runs on the host inside the library (include/w2rap_step4.h).
+// <out_dir>/<prefix>.large_K.clean.{hbv,paths} that Step 5 (`--from_step 5`) loads.  The vote, the graph edit and the path rewrite
+// run in libw2rap_step2.so (HIP); --host_edit runs the library's host edit instead (include/w2rap_step4.h).
 //
-//   w2rap-step4 -o <out_dir> -p <prefix> [-s min_size] [--device 0]
+//   w2rap-step4 -o <out_dir> -p <prefix> [-s min_size] [--device 0] [--host_edit]
 //
 // File layouts: include/w2rap_step4.h and w2rap_contigger_amd/formats.py.  Every count in the inputs is checked against the bytes
 // that are there.
@@ -111,10 +111,11 @@ int main(int argc, char** argv) {
         else if (a == "-p" || a == "--prefix") prefix = next();
         else if (a == "-s" || a == "--min_size") P.min_size = (uint32_t)std::atoi(next());
         else if (a == "--device") P.device = std::atoi(next());
+        else if (a == "--host_edit") P.flags |= W2RAP_STEP4_EDIT_ON_HOST;
         else if (a == "-t" || a == "-m" || a == "-d" || a == "--disk_batches" || a == "--tmp_dir" || a == "-r" || a == "-K" || a == "--large_k") next();   // accepted, unused
         else { std::fprintf(stderr, "unknown option %s\n", a.c_str()); return 2; }
     }
-    if (out_dir.empty() || prefix.empty()) { std::fprintf(stderr, "usage: w2rap-step4 -o out_dir -p prefix [-s min_size] [--device d]\n"); return 2; }
+    if (out_dir.empty() || prefix.empty()) { std::fprintf(stderr, "usage: w2rap-step4 -o out_dir -p prefix [-s min_size] [--device d] [--host_edit]\n"); return 2; }
     std::string err;
     Hbv hb;
     if (!hb.load(out_dir + "/" + prefix + ".large_K.hbv", err)) { std::fprintf(stderr, "%s\n", err.c_str()); return 1; }
@@ -182,7 +183,7 @@ int main(int argc, char** argv) {
     int rc = w2rap_step4_run(&I, &P, &O, ebuf, sizeof ebuf);
     if (rc) { std::fprintf(stderr, "w2rap_step4_run failed (%d): %s\n", rc, ebuf); return 1; }
     for (int k = 0; k < 2; ++k)
-        std::printf("pass %d: %llu edges deleted, %llu runs merged; GPU ms: index %.2f vote %.2f paths %.2f; host ms: graph edit %.2f\n", k + 1, (unsigned long long)O.n_deleted[k],
+        std::printf("pass %d: %llu edges deleted, %llu runs merged; GPU ms: index %.2f vote %.2f paths %.2f; host ms in the graph edit: %.2f\n", k + 1, (unsigned long long)O.n_deleted[k],
                     (unsigned long long)O.n_runs_merged[k], O.ms_index[k], O.ms_vote[k], O.ms_paths[k], O.ms_graph_edit_host[k]);
     std::printf("%llu branch vertices, %llu skipped (too many walks), %llu placements\n", (unsigned long long)O.n_branch_vertices, (unsigned long long)O.n_skipped_too_many_exts,
                 (unsigned long long)O.n_placements);

@@ -8,7 +8,7 @@ files the previous step wrote, and every step writes what the reference writes:
             w2rap-contigger.cc:312-318, and its steps 2..6 load them again, :322-328: a hand-over to `--from_step 4` needs them)
     step 2: OUT/PREFIX.small_K.hbv, .paths (last step or dump_all, :343-347), OUT/small_K.freqs (always, BuildReadQGraph.cc:1108)
     step 3: OUT/PREFIX.large_K.hbv, .paths (last step or dump_all, :373-378), OUT/PREFIX.first.frags.dist
-    step 4: OUT/PREFIX.large_K.clean.hbv, .paths (-s / --min_size as in the reference; the graph edit of this step runs on the host, step4.py)
+    step 4: OUT/PREFIX.large_K.clean.hbv, .paths (-s / --min_size as in the reference; the vote, the graph edit and the path rewrite of this step run on the GPU, step4.py)
 Steps 5-7 are the reference's (``w2rap-contigger ... --from_step 5``).  The HIP library is the only implementation (no CPU fallback).
 
     python -m w2rap_contigger_amd.pipeline -r r1.fastq.gz,r2.fastq.gz -o OUT -p asm --from_step 1 --to_step 3
@@ -94,7 +94,7 @@ def run(read_files, out_dir, prefix, large_k=200, min_freq=4, min_qual=7, from_s
             F.write_paths(pre + ".large_K.clean.paths", r4.path_offset, r4.path_off, r4.path_edges)
         out["step4"] = r4
         log(f"Cleaning graph DONE: {sum(r4.n_deleted)} edges deleted, {sum(r4.n_runs_merged)} runs merged, {r4.hbv.n_edges} edge objects "
-            f"(graph edit on the host: {sum(r4.ms_graph_edit_host):.1f} ms)")
+            f"(host clock in the graph edit: {sum(r4.ms_graph_edit_host):.1f} ms)")
     return out
 
 

@@ -6,8 +6,11 @@ reference's Step-4 interface.
 ``--from_step 4 --to_step 4`` run on an output directory (w2rap-contigger.cc:386-409): reads <prefix>.large_K.{hbv,paths} and
 frag_reads_orig.{fastb,qualp}, writes <prefix>.large_K.clean.{hbv,paths}.
 
-The vote over the reads and the rewrite of the read paths run in HIP kernels; the edit of the graph itself runs on the host inside the
-library (its time is reported apart: ms_graph_edit_host).  The HIP library is the only implementation (no CPU fallback)."""
+The vote over the reads, the rewrite of the read paths and the edit of the graph itself (delete, merge runs, renumber: the k4e_*
+kernels) run in HIP kernels: the graph goes up once and comes down once.  ``edit="host"`` (EDIT_ON_HOST) runs the library's host edit
+instead, the cross-check; a graph that misses a precondition of the device edit (adjacency lists not sorted by neighbour, a run whose
+mirror image is not a run) takes it silently, with the same result.  `Step4Result.edit_on_device` tells which one ran.  The HIP library
+is the only implementation (no CPU fallback)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -33,6 +36,7 @@ class Step4Params(C.Structure):
 
 
 VOTE_ONLY = 1
+EDIT_ON_HOST = 2
 
 
 class Step4Out(C.Structure):
@@ -83,12 +87,17 @@ class Step4Result:
     ms_vote: tuple
     ms_paths: tuple
     ms_graph_edit_host: tuple     # HOST milliseconds per pass
+    edit_on_device: bool = False  # the graph edit ran in the k4e_* kernels (False: the host edit ran, or vote_only edited nothing)
 
 
-def clean200x(hbv: F.HBV, paths, read_packed, read_byte_off, read_len, quals, qual_off=None, min_size=0, device=0, vote_only=False, inv=None) -> Step4Result:
+def clean200x(hbv: F.HBV, paths, read_packed, read_byte_off, read_len, quals, qual_off=None, min_size=0, device=0, vote_only=False, inv=None,
+              edit="device") -> Step4Result:
     """Involution + Clean200x through the one-shot C entry point (w2rap_step4_run).
     paths = (offset i32[n], path_off u64[n+1], edges i32[]); quals = the unpacked .qualp values, one byte per base (formats.qualp_to_raw);
-    qual_off None = the running sum of read_len; inv = the graph's involution if the caller has it (Step 3's inv2), else computed."""
+    qual_off None = the running sum of read_len; inv = the graph's involution if the caller has it (Step 3's inv2), else computed;
+    edit = "device" (the default) or "host": where the graph edit runs."""
+    if edit not in ("device", "host"):
+        raise ValueError(f"edit must be 'device' or 'host', not {edit!r}")
     L = lib()
     ln = np.ascontiguousarray(read_len, np.uint32)
     if qual_off is None:
@@ -105,7 +114,7 @@ def clean200x(hbv: F.HBV, paths, read_packed, read_byte_off, read_len, quals, qu
     i = Step4In(hbv.K, len(keep[2]), p(keep[0]), p(keep[1]), p(keep[2]), hbv.n_vertices, p(keep[3]), p(keep[4]), p(keep[5]), p(keep[6]), p(keep[7]),
                 None if inv_a is None or not len(inv_a) else _ptr(inv_a),
                 len(keep[8]), p(keep[8]), p(keep[9]), p(keep[10]), len(ln), p(keep[11]), p(keep[12]), p(keep[13]), p(keep[14]), p(keep[15]))
-    prm = Step4Params(device, int(min_size), VOTE_ONLY if vote_only else 0)
+    prm = Step4Params(device, int(min_size), (VOTE_ONLY if vote_only else 0) | (EDIT_ON_HOST if edit == "host" else 0))
     o = Step4Out()
     err = C.create_string_buffer(1024)
     rc = L.w2rap_step4_run(C.byref(i), C.byref(prm), C.byref(o), err, 1024)
@@ -122,13 +131,15 @@ def clean200x(hbv: F.HBV, paths, read_packed, read_byte_off, read_len, quals, qu
                            _np_from(o.path_offset, np.int32, NP), po, _np_from(o.path_edges, np.int32, int(po[-1])),
                            [_np_from(o.deleted[k], np.int32, o.n_deleted[k]) for k in range(1 if vote_only else 2)],
                            tuple(o.n_deleted), tuple(o.n_runs_merged), o.n_branch_vertices, o.n_skipped_too_many_exts, o.n_placements,
-                           tuple(o.ms_index), tuple(o.ms_vote), tuple(o.ms_paths), tuple(o.ms_graph_edit_host))
+                           tuple(o.ms_index), tuple(o.ms_vote), tuple(o.ms_paths), tuple(o.ms_graph_edit_host),
+                           edit_on_device=profile().get("edit_path_device", (0.0, 0))[0] == 1.0)
     finally:
         L.w2rap_step4_free(C.byref(o))
 
 
 def profile():
-    """-> {kernel name: (total ms, launches)} of the last clean200x in this process"""
+    """-> {kernel name: (total ms, launches)} of the last clean200x in this process; the entry "edit_path_device" is not a kernel:
+    (1.0, passes edited on the device) or (0.0, 0)"""
     L = lib()
     n = L.w2rap_step4_profile(None, 0)
     buf = C.create_string_buffer(int(n) + 16)
@@ -140,14 +151,16 @@ def profile():
     return out
 
 
-def run_step4_files(out_dir, prefix, min_size=0, device=0) -> Step4Result:
+def run_step4_files(out_dir, prefix, min_size=0, device=0, edit="device") -> Step4Result:
     """The reference's Step 4 on an output directory (w2rap-contigger.cc:386-409)."""
+    if edit not in ("device", "host"):
+        raise ValueError(f"edit must be 'device' or 'host', not {edit!r}")
     hbv = F.read_hbv(os.path.join(out_dir, f"{prefix}.large_K.hbv"))
     paths = F.read_paths(os.path.join(out_dir, f"{prefix}.large_K.paths"))
     pk, bo, ln = F.read_fastb(os.path.join(out_dir, "frag_reads_orig.fastb"))
     pq, po = F.read_qualp(os.path.join(out_dir, "frag_reads_orig.qualp"))
     quals, qoff = F.qualp_to_raw(pq, po)
-    res = clean200x(hbv, paths, pk, bo, ln, quals, qoff, min_size=min_size, device=device)
+    res = clean200x(hbv, paths, pk, bo, ln, quals, qoff, min_size=min_size, device=device, edit=edit)
     F.write_hbv(os.path.join(out_dir, f"{prefix}.large_K.clean.hbv"), res.hbv)
     F.write_paths(os.path.join(out_dir, f"{prefix}.large_K.clean.paths"), res.path_offset, res.path_off, res.path_edges)
     return res
