@@ -101,8 +101,9 @@ typedef struct w2rap_step4_out {
     uint64_t n_skipped_too_many_exts;/* of those: more than 10 walks (Clean200.cc:246) */
     uint64_t n_placements;           /* (read, start) placements scored, both passes */
     float ms_index[2], ms_vote[2], ms_paths[2];      /* device time per pass, milliseconds */
-    float ms_graph_edit_host[2];                     /* HOST clock spent in the graph edit phase per pass, milliseconds: the edit itself with
-                                                        EDIT_ON_HOST; launching the k4e_* kernels and waiting for their counts without */
+    float ms_graph_edit_host[2];                     /* HOST clock spent in the graph edit phase per pass, milliseconds: the edit itself and the
+                                                        upload of the next pass's graph with EDIT_ON_HOST (HostEditor4::pass); launching the
+                                                        k4e_* kernels and waiting for their counts without (DeviceEditor4::pass) */
     void* _owner;                    /* internal */
 } w2rap_step4_out;
 

@@ -3,12 +3,16 @@ Each is the smallest graph that exercises one rule of RemoveUnneededVertices2 / 
 it; `edit_cases()` also returns, per case, what test_step4_edit_model.py asserts about the model's output so that a green test means
 the rule was really exercised.
 
-    edit_cases() -> name -> Case(inputs = (hbv, paths, (packed, byte_off, read_len), quals, min_size), expect = {...})"""
+    edit_cases() -> name -> Case(inputs = (hbv, paths, (packed, byte_off, read_len), quals, min_size), expect = {...})
+
+`empty_cases()` and `no_reads_case()` are the shapes at which the driver around the edit, not the edit, can go wrong: a graph without an
+edge (nothing to run a kernel on: the device edit declines) and a graph that changes while there is no read path to rewrite."""
 from dataclasses import dataclass, field
 
 import numpy as np
 
 import step4_cases as S
+from w2rap_contigger_amd import formats as F
 from step4_cases import Hand, _rc, _seq
 
 
@@ -124,3 +128,21 @@ def edit_cases():
     hb.from_v[[fo, fo + 1]] = hb.from_v[[fo + 1, fo]]; hb.from_e[[fo, fo + 1]] = hb.from_e[[fo + 1, fo]]
     out["i_unsorted_lists"] = Case((hb, paths, reads, quals, 0), {"merged": [2, 0], "unsorted": True})
     return out
+
+
+def empty_cases():
+    """name -> (hbv, paths, (packed, byte_off, read_len), quals): a graph without an edge, with no vertex and with three isolated
+    vertices, and two reads (30 and 45 bases) whose paths are empty"""
+    rng = np.random.default_rng(39)
+    ro = np.array([0, 30, 75], np.uint64)
+    reads = F.pack_bases(_seq(rng, 75), ro)
+    paths = (np.zeros(2, np.int32), np.zeros(3, np.uint64), np.zeros(0, np.int32))
+    i32, u8 = np.zeros(0, np.int32), np.zeros(0, np.uint8)
+    return {f"nv{nv}": (F.HBV(20, np.zeros(nv + 1, np.uint64), i32, i32, np.zeros(nv + 1, np.uint64), i32, u8, np.zeros(1, np.uint64), np.zeros(0, np.uint32)),
+                        paths, reads, np.full(75, 30, np.uint8)) for nv in (0, 3)}
+
+
+def no_reads_case():
+    """-> (hbv, paths, (packed, byte_off, read_len), quals, min_size): the graph of b_long_run without a read"""
+    h = edit_cases()["b_long_run"].inputs[0]
+    return (h, (np.zeros(0, np.int32), np.zeros(1, np.uint64), np.zeros(0, np.int32)), F.pack_bases(np.zeros(0, np.uint8), np.zeros(1, np.uint64)), np.zeros(0, np.uint8), 0)

@@ -97,11 +97,58 @@ def test_generated_reads_device_host_model():
     _same_results(dev, host)
 
 
-def test_vote_only_edits_nothing_on_the_device_path():
+def _vote_only_edits_nothing(edit):
     h, paths, (pk, bo, ln), quals = S.load("errs2")
-    res = step4.clean200x(h, paths, pk, bo, ln, quals, vote_only=True, edit="device")
+    res = step4.clean200x(h, paths, pk, bo, ln, quals, vote_only=True, edit=edit)
     m = M.clean200x(h, None, paths, M.reads_of(pk, bo, ln, quals), 0, vote_only=True)
     assert len(m.deleted[0]) > 0
     _same(res, m, vote_only=True)
     assert F.hbv_to_bytes(res.hbv, zero_padding=True) == F.hbv_to_bytes(h, zero_padding=True)
     assert F.paths_to_bytes(res.path_offset, res.path_off, res.path_edges) == F.paths_to_bytes(*paths)
+
+
+def test_vote_only_edits_nothing_on_the_device_path():
+    _vote_only_edits_nothing("device")
+
+
+def test_vote_only_hands_the_input_graph_on_with_the_host_edit():
+    """the editor that edits nothing returns the pass's input graph as the next one: its blocks must outlive the pass"""
+    _vote_only_edits_nothing("host")
+
+
+@pytest.mark.parametrize("edit", ["device", "host"])
+@pytest.mark.parametrize("min_size", [0, 40])
+@pytest.mark.parametrize("name", sorted(EC.empty_cases()))
+def test_a_graph_without_edges_takes_the_host_edit(name, min_size, edit):
+    """nothing to run a kernel on: the device edit declines, the call starts over on the host and returns the empty graph"""
+    h, paths, (pk, bo, ln), quals = EC.empty_cases()[name]
+    res = step4.clean200x(h, paths, pk, bo, ln, quals, min_size=min_size, edit=edit)
+    assert res.edit_on_device is False and not _k4e()
+    assert (res.hbv.n_vertices, res.hbv.n_edges) == (0, 0)
+    assert [list(x) for x in res.deleted] == [[], []] and res.n_deleted == (0, 0) and res.n_runs_merged == (0, 0)
+    assert F.paths_to_bytes(res.path_offset, res.path_off, res.path_edges) == F.paths_to_bytes(*paths)
+    _same(res, M.clean200x(h, None, paths, M.reads_of(pk, bo, ln, quals), min_size))
+
+
+def test_the_graph_changes_without_a_read_path_to_rewrite():
+    h, paths, (pk, bo, ln), quals, ms = EC.no_reads_case()
+    m = M.clean200x(h, None, paths, M.reads_of(pk, bo, ln, quals), ms)
+    dev = step4.clean200x(h, paths, pk, bo, ln, quals, min_size=ms, edit="device")
+    assert dev.edit_on_device is True and _k4e()
+    host = step4.clean200x(h, paths, pk, bo, ln, quals, min_size=ms, edit="host")
+    assert host.edit_on_device is False and not _k4e()
+    assert list(dev.n_runs_merged) == list(host.n_runs_merged) == _EDIT_CASES["b_long_run"].expect["merged"]
+    _same(dev, m)
+    _same(host, m)
+    _same_results(dev, host)
+
+
+def test_a_call_after_a_fallback_finds_a_clean_context():
+    """the restart on the host drops everything of the abandoned attempt: the next call in the process edits on the device again"""
+    h, paths, (pk, bo, ln), quals, ms = _EDIT_CASES["i_unsorted_lists"].inputs
+    first = step4.clean200x(h, paths, pk, bo, ln, quals, min_size=ms, edit="device")
+    assert first.edit_on_device is False and not _k4e()
+    h, paths, (pk, bo, ln), quals, ms = _EDIT_CASES["a_interleaved_runs"].inputs
+    second = step4.clean200x(h, paths, pk, bo, ln, quals, min_size=ms, edit="device")
+    assert second.edit_on_device is True and _k4e()
+    _same(second, M.clean200x(h, None, paths, M.reads_of(pk, bo, ln, quals), ms))

@@ -103,3 +103,22 @@ def test_circles_are_handled_as_the_model_says():
     # pass 1 keeps the six untouched edges in order and appends copies of 5, 4 (circle 1), 9, 8 (circle 2), 7, 6 (its mirror circle)
     assert _same_edges(after, [before[e] for e in (0, 1, 2, 3, 10, 11, 5, 4, 9, 8, 7, 6)])
     assert list(m.inv) == [1, 0, 3, 2, 5, 4, 7, 6, 9, 8, 11, 10]
+
+
+@pytest.mark.parametrize("name", sorted(EC.empty_cases()))
+@pytest.mark.parametrize("min_size", [0, 40])
+def test_the_model_returns_an_empty_graph_for_a_graph_without_edges(name, min_size):
+    h, paths, (pk, bo, ln), quals = EC.empty_cases()[name]
+    assert h.n_edges == 0 and len(paths[0]) == 2 and len(paths[2]) == 0
+    m = M.clean200x(h, None, paths, M.reads_of(pk, bo, ln, quals), min_size)
+    assert (m.hbv.n_vertices, m.hbv.n_edges, m.deleted, m.counters.n_runs_merged) == (0, 0, [[], []], [0, 0])
+    assert (list(m.path_offset), list(m.path_off), list(m.path_edges)) == ([0, 0], [0, 0, 0], [])
+
+
+def test_the_model_merges_the_long_run_without_reads():
+    h, paths, (pk, bo, ln), quals, ms = EC.no_reads_case()
+    M.RUN_SIZES.clear()
+    m = M.clean200x(h, None, paths, M.reads_of(pk, bo, ln, quals), ms)
+    x = CASES["b_long_run"].expect
+    assert m.counters.n_runs_merged == x["merged"] and max(M.RUN_SIZES) == x["run_size"] and _same_edges(_edges(m.hbv), x["edges"])
+    assert len(m.path_offset) == 0 and list(m.path_off) == [0]

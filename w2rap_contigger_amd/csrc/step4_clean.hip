@@ -12,15 +12,14 @@
 //   device  k4e_*               the graph edit (step4_edit.hip): min_size (:370-380), DeleteEdges, RemoveUnneededVertices2
 //                               (GapToyTools3.cc:87-294), CleanupCore (GapToyTools.cc:417-453); the next pass's graph, branch vertices
 //                               and tasks are made on the device, nothing of the graph crosses PCIe between the upload and the download
-//   host    edit_graph          the same edit on the host: W2RAP_STEP4_EDIT_ON_HOST, and the fallback when a precondition of the device
-//                               edit does not hold (adjacency lists not sorted by neighbour, a run whose mirror is not a run)
+//   host    edit_graph          the same edit on the host (step4_host.hip): W2RAP_STEP4_EDIT_ON_HOST, and the fallback when a precondition
+//                               of the device edit does not hold (adjacency lists not sorted by neighbour, a run whose mirror is not a run)
 //   device  k4_path_len / scan / k4_path_write       Cleanup's truncation + both renumberings of the read paths in one go
 // Integer arithmetic throughout; the order in which placements are listed does not matter (only sums of margins are used).
 #include <algorithm>
 #include <chrono>
 #include <cstring>
 #include <string>
-#include <unordered_map>
 #include <vector>
 #include "step4_edit.h"
 #include "../../include/w2rap_step4.h"
@@ -305,183 +304,6 @@ __global__ __launch_bounds__(256) void k4_path_write(uint64_t n, const uint64_t*
     noffs[r] = off;
 }
 
-// ---- the graph on the host (digraphE<basevector>: ordered adjacency lists, edge objects as base codes) -------------------------------
-struct HostGraph {
-    int K = 0;
-    std::vector<std::vector<int>> frm, frm_e, to, to_e;
-    std::vector<std::vector<uint8_t>> edges;
-    int kmers(int e) const { return (int)edges[e].size() - K + 1; }
-    void left_right(std::vector<int>& tl, std::vector<int>& tr) const {
-        tl.assign(edges.size(), -1); tr.assign(edges.size(), -1);
-        for (size_t v = 0; v < frm.size(); ++v) { for (int e : frm_e[v]) tl[e] = (int)v; for (int e : to_e[v]) tr[e] = (int)v; }
-    }
-    void used(std::vector<char>& u) const { u.assign(edges.size(), 0); for (auto& l : to_e) for (int e : l) u[e] = 1; }
-    void add_edge(int v, int w, std::vector<uint8_t>&& seq) {              // DigraphTemplate.h:1829-1839
-        const int n = (int)edges.size();
-        edges.push_back(std::move(seq));
-        const size_t i = std::upper_bound(frm[v].begin(), frm[v].end(), w) - frm[v].begin();
-        frm[v].insert(frm[v].begin() + i, w); frm_e[v].insert(frm_e[v].begin() + i, n);
-        const size_t j = std::upper_bound(to[w].begin(), to[w].end(), v) - to[w].begin();
-        to[w].insert(to[w].begin() + j, v); to_e[w].insert(to_e[w].begin() + j, n);
-    }
-    void delete_edges(const std::vector<char>& dead) {                     // DigraphTemplate.h:2017-2027: the lists keep their order
-        for (size_t v = 0; v < frm.size(); ++v) {
-            size_t k = 0;
-            for (size_t i = 0; i < frm_e[v].size(); ++i) if (!dead[frm_e[v][i]]) { frm[v][k] = frm[v][i]; frm_e[v][k] = frm_e[v][i]; ++k; }
-            frm[v].resize(k); frm_e[v].resize(k);
-            k = 0;
-            for (size_t i = 0; i < to_e[v].size(); ++i) if (!dead[to_e[v][i]]) { to[v][k] = to[v][i]; to_e[v][k] = to_e[v][i]; ++k; }
-            to[v].resize(k); to_e[v].resize(k);
-        }
-    }
-};
-
-// HyperBasevector::Involution (HyperBasevector.cc:648-660) for a graph whose edge sequences are distinct: the object holding the reverse complement
-int host_involution(const HostGraph& g, std::vector<int>& inv, std::string& err) {
-    std::unordered_map<std::string, int> where;
-    where.reserve(g.edges.size() * 2);
-    for (size_t e = 0; e < g.edges.size(); ++e) {
-        if (!where.emplace(std::string(g.edges[e].begin(), g.edges[e].end()), (int)e).second) { err = "Involution: two edge objects with the same sequence"; return W2RAP_E_GRAPH; }
-    }
-    inv.assign(g.edges.size(), -1);
-    std::string rc;
-    for (size_t e = 0; e < g.edges.size(); ++e) {
-        const auto& s = g.edges[e];
-        rc.resize(s.size());
-        for (size_t i = 0; i < s.size(); ++i) rc[i] = (char)(3 - s[s.size() - 1 - i]);
-        auto it = where.find(rc);
-        if (it == where.end()) { err = "Involution: an edge object has no reverse complement in the graph (HyperBasevector.cc:648-660 needs every edge's RC)"; return W2RAP_E_GRAPH; }
-        inv[e] = it->second;
-    }
-    return 0;
-}
-
-// one pass's edit.  in: dead[e] from the vote (ids of g).  out: the sorted unique deleted list, g and inv edited,
-// map[e] (old id -> final id, -1: deleted) and add[e] (offsets[e]) for the path kernels, the number of merged runs
-void edit_graph(HostGraph& g, std::vector<int>& inv, std::vector<char>& dead, unsigned min_size, bool edit, std::vector<int32_t>& deleted,
-                std::vector<int32_t>& map, std::vector<int32_t>& add, uint64_t& n_merged) {
-    const size_t NV = g.frm.size(), E0 = g.edges.size();
-    if (min_size > 0) {                                                      // Clean200.cc:370-380
-        for (size_t v = 0; v < NV; ++v) {
-            if (!g.to[v].empty() || g.frm[v].size() != 1) continue;
-            const int w = g.frm[v][0];
-            if ((int)v == w || g.to[w].size() != 1 || !g.frm[w].empty()) continue;
-            const int e = g.frm_e[v][0];
-            if (g.kmers(e) > (int)min_size) continue;
-            dead[e] = 1;
-        }
-    }
-    deleted.clear();
-    for (size_t e = 0; e < E0; ++e) if (dead[e]) deleted.push_back((int32_t)e);
-    n_merged = 0;
-    if (!edit) return;
-    g.delete_edges(dead);
-    // Cleanup: a path is cut at its first edge that is no longer in the graph (`alive` below)
-    std::vector<char> alive;
-    g.used(alive);
-    // RemoveUnneededVertices2
-    std::vector<int> to_left, to_right;
-    g.left_right(to_left, to_right);
-    std::vector<char> kill(NV, 0);
-    std::vector<int> queue;
-    for (size_t v = 0; v < NV; ++v)
-        if (g.frm[v].size() == 1 && g.to[v].size() == 1 && g.frm[v][0] != g.to[v][0] && !g.edges[g.frm_e[v][0]].empty() && !g.edges[g.to_e[v][0]].empty()) {
-            kill[v] = 1; queue.push_back((int)v);
-        }
-    std::vector<std::pair<int, int>> bound;
-    while (!queue.empty()) {
-        const int v = queue.back(); queue.pop_back();
-        if (!kill[v]) continue;
-        int eleft, vl = v;
-        do { kill[vl] = 0; eleft = g.to_e[vl][0]; vl = g.to[vl][0]; } while (kill[vl]);
-        int eright, vr = v;
-        do { kill[vr] = 0; eright = g.frm_e[vr][0]; vr = g.frm[vr][0]; } while (kill[vr]);
-        if (eleft < inv[eright]) { bound.emplace_back(eleft, eright); bound.emplace_back(inv[eright], inv[eleft]); }
-    }
-    std::vector<int> renum(E0), offsets(E0, 0), new_nos;
-    for (size_t e = 0; e < E0; ++e) renum[e] = (int)e;
-    std::vector<char> dead2(E0, 0);
-    while (!bound.empty()) {
-        const auto b = bound.back(); bound.pop_back();
-        const int new_no = (int)g.edges.size();
-        int off = g.kmers(b.first);
-        renum[b.first] = new_no; dead2[b.first] = 1;
-        for (int v = to_right[b.first]; v != to_right[b.second]; v = g.frm[v][0]) {
-            const int e = g.frm_e[v][0];
-            dead2[e] = 1; offsets[e] = off; renum[e] = new_no; off += g.kmers(e);
-        }
-        std::vector<uint8_t> ne(g.edges[b.first]);
-        ne.reserve((size_t)off + g.K - 1);
-        for (int v = to_right[b.first]; v != to_right[b.second]; v = g.frm[v][0]) {
-            const int e = g.frm_e[v][0];
-            ne.resize((size_t)offsets[e]);
-            ne.insert(ne.end(), g.edges[e].begin(), g.edges[e].end());
-        }
-        g.add_edge(to_left[b.first], to_right[b.second], std::move(ne));
-        new_nos.push_back(new_no);
-    }
-    n_merged = new_nos.size();
-    dead2.resize(g.edges.size(), 0);
-    g.delete_edges(dead2);
-    inv.resize(g.edges.size(), -1);
-    for (size_t k = 0; k + 1 < new_nos.size(); k += 2) { inv[new_nos[k]] = new_nos[k + 1]; inv[new_nos[k + 1]] = new_nos[k]; }
-    // CleanupCore
-    std::vector<char> u;
-    g.used(u);
-    std::vector<int> to_new(u.size(), -1);
-    int c = 0;
-    for (size_t i = 0; i < u.size(); ++i) if (u[i]) to_new[i] = c++;
-    std::vector<int> inv2; inv2.reserve(c);
-    for (size_t i = 0; i < u.size(); ++i) if (u[i]) inv2.push_back(inv[i] < 0 ? -1 : to_new[inv[i]]);
-    inv.swap(inv2);
-    std::vector<std::vector<uint8_t>> ed; ed.reserve(c);
-    for (size_t i = 0; i < u.size(); ++i) if (u[i]) ed.push_back(std::move(g.edges[i]));
-    g.edges.swap(ed);
-    std::vector<int> newv(NV, -1);
-    int nv = 0;
-    for (size_t v = 0; v < NV; ++v) if (!g.frm[v].empty() || !g.to[v].empty()) newv[v] = nv++;
-    HostGraph h; h.K = g.K;
-    h.frm.resize(nv); h.frm_e.resize(nv); h.to.resize(nv); h.to_e.resize(nv);
-    for (size_t v = 0; v < NV; ++v) {
-        if (newv[v] < 0) continue;
-        const int x = newv[v];
-        h.frm[x].swap(g.frm[v]); h.frm_e[x].swap(g.frm_e[v]); h.to[x].swap(g.to[v]); h.to_e[x].swap(g.to_e[v]);
-        for (auto& w : h.frm[x]) w = newv[w];
-        for (auto& w : h.to[x]) w = newv[w];
-        for (auto& e : h.frm_e[x]) e = to_new[e];
-        for (auto& e : h.to_e[x]) e = to_new[e];
-    }
-    h.edges.swap(g.edges);
-    g = std::move(h);
-    map.assign(E0, -1); add.assign(E0, 0);
-    for (size_t e = 0; e < E0; ++e) if (alive[e]) { map[e] = to_new[renum[e]]; add[e] = offsets[e]; }
-}
-
-void pack_edges(const HostGraph& g, std::vector<uint8_t>& packed, std::vector<uint64_t>& boff, std::vector<uint32_t>& len) {
-    const size_t E = g.edges.size();
-    boff.assign(E + 1, 0); len.resize(E);
-    for (size_t e = 0; e < E; ++e) { len[e] = (uint32_t)g.edges[e].size(); boff[e + 1] = boff[e] + (g.edges[e].size() + 3) / 4; }
-    packed.assign(boff[E], 0);
-    for (size_t e = 0; e < E; ++e) {
-        uint8_t* d = packed.data() + boff[e];
-        const auto& s = g.edges[e];
-        for (size_t i = 0; i < s.size(); ++i) d[i >> 2] |= (uint8_t)(s[i] << (2 * (i & 3)));
-    }
-}
-
-struct Csr { std::vector<uint64_t> from_off, to_off; std::vector<int32_t> from_v, from_e, to_v, to_e, vleft, vright; };
-void make_csr(const HostGraph& g, Csr& c) {
-    const size_t NV = g.frm.size(), E = g.edges.size();
-    c.from_off.assign(NV + 1, 0); c.to_off.assign(NV + 1, 0);
-    c.from_v.clear(); c.from_e.clear(); c.to_v.clear(); c.to_e.clear();
-    c.vleft.assign(E, -1); c.vright.assign(E, -1);
-    for (size_t v = 0; v < NV; ++v) {
-        for (size_t i = 0; i < g.frm[v].size(); ++i) { c.from_v.push_back(g.frm[v][i]); c.from_e.push_back(g.frm_e[v][i]); c.vleft[g.frm_e[v][i]] = (int32_t)v; }
-        for (size_t i = 0; i < g.to[v].size(); ++i) { c.to_v.push_back(g.to[v][i]); c.to_e.push_back(g.to_e[v][i]); c.vright[g.to_e[v][i]] = (int32_t)v; }
-        c.from_off[v + 1] = c.from_v.size(); c.to_off[v + 1] = c.to_v.size();
-    }
-}
-
 template <class T> T* host_copy(const std::vector<T>& v) {
     T* p = (T*)host_result_alloc((v.size() ? v.size() : 1) * sizeof(T));
     if (p && !v.empty()) std::memcpy(p, v.data(), v.size() * sizeof(T));
@@ -492,22 +314,6 @@ std::string g_profile4;
 
 struct Ms { float index = 0, vote = 0, paths = 0, host = 0; };
 struct PathsDev { uint64_t n = 0, npe = 0; int32_t* offset = nullptr; uint64_t* off = nullptr; int32_t* edges = nullptr; };
-
-int upload_reads(Ctx& c, const w2rap_step4_in& in, ReadsDev& R, PathsDev& P) {
-    const uint64_t n = in.n_paths;
-    uint8_t* b = nullptr; uint64_t* bo = nullptr; uint32_t* ln = nullptr; uint8_t* q = nullptr; uint64_t* qo = nullptr;
-    W2_TRY(up_pooled(c, &b, in.read_packed, n ? in.read_byte_off[n] : 0, 16));
-    W2_TRY(up_pooled(c, &bo, in.read_byte_off, in.read_byte_off ? n + 1 : 0));
-    W2_TRY(up_pooled(c, &ln, in.read_len, n));
-    W2_TRY(up_pooled(c, &q, in.quals, n ? in.qual_off[n] : 0, 16));
-    W2_TRY(up_pooled(c, &qo, in.qual_off, in.qual_off ? n + 1 : 0));
-    R = ReadsDev{b, bo, ln, q, qo};
-    P.n = n; P.npe = n ? in.path_off[n] : 0;
-    W2_TRY(up_pooled(c, &P.offset, in.path_offset, n));
-    W2_TRY(up_pooled(c, &P.off, in.path_off, in.path_off ? n + 1 : 0));
-    W2_TRY(up_pooled(c, &P.edges, in.path_edges, P.npe));
-    return 0;
-}
 
 // one pass's paths index and vote: d_dead[e] (zeroed by the caller) is set for the edge objects the vote deletes
 int vote_pass(Ctx& c, const GraphDev& G, uint64_t B, uint64_t T, const int32_t* d_bvert, const int32_t* d_outdeg, const Task* d_tasks, const ReadsDev& R,
@@ -588,222 +394,99 @@ int rewrite_paths(Ctx& c, const PathsDev& P, const int32_t* d_map, const int32_t
     return 0;
 }
 
-int download_paths(Ctx& c, const PathsDev& P, w2rap_step4_out& out) {
-    const uint64_t n = P.n;
-    out.n_paths = n;
-    W2_TRY(dl(c, &out.path_offset, (const int32_t*)P.offset, n));
-    if (n) { W2_TRY(dl(c, &out.path_off, (const uint64_t*)P.off, n + 1)); }
-    else { out.path_off = (uint64_t*)host_result_alloc(8); if (out.path_off) out.path_off[0] = 0; }
-    W2_TRY(dl(c, &out.path_edges, (const int32_t*)P.edges, P.npe));
-    return 0;
-}
-
-// ---- Step 4 with the graph edit on the host (W2RAP_STEP4_EDIT_ON_HOST, VOTE_ONLY, and the fallback of the device edit)
-int step4(Ctx& c, const w2rap_step4_in& in, const w2rap_step4_params& P, w2rap_step4_out& out) {
-    const bool vote_only = (P.flags & W2RAP_STEP4_VOTE_ONLY) != 0;
-    const unsigned K = (unsigned)in.K;
-    // ---- the graph on the host
-    HostGraph g; g.K = in.K;
-    {
-        const uint64_t NV = in.n_vertices, E = in.n_edge_objs;
-        g.frm.resize(NV); g.frm_e.resize(NV); g.to.resize(NV); g.to_e.resize(NV); g.edges.resize(E);
-        for (uint64_t e = 0; e < E; ++e) {
-            g.edges[e].resize(in.edge_len[e]);
-            const uint8_t* s = in.edge_packed + in.edge_byte_off[e];
-            for (uint32_t i = 0; i < in.edge_len[e]; ++i) g.edges[e][i] = (s[i >> 2] >> (2 * (i & 3))) & 3u;
-        }
-        std::vector<int> left(E, -1);
-        for (uint64_t v = 0; v < NV; ++v)
-            for (uint64_t i = in.from_off[v]; i < in.from_off[v + 1]; ++i) { g.frm[v].push_back(in.from_v[i]); g.frm_e[v].push_back(in.from_e[i]); left[in.from_e[i]] = (int)v; }
-        for (uint64_t v = 0; v < NV; ++v)
-            for (uint64_t i = in.to_off[v]; i < in.to_off[v + 1]; ++i) { g.to_e[v].push_back(in.to_e[i]); g.to[v].push_back(left[in.to_e[i]]); }
-    }
+// ---- the driver: upload, two passes on device-resident data, download.  The editor is the only part that differs between the device
+// path and the host path (W2RAP_STEP4_EDIT_ON_HOST, VOTE_ONLY, and what w2rap_step4_run starts over with after EDIT4_FALLBACK)
+// the one reader of `in`: its graph (with both ends of every edge and the involution, computed here if the caller gave none), reads and
+// paths on the device; host != null: the same graph as the host editor keeps it
+int upload(Ctx& c, const w2rap_step4_in& in, Graph4& g, ReadsDev& R, PathsDev& P, HostEditor4* host) {
+    const uint64_t E = in.n_edge_objs, NV = in.n_vertices;
+    HostGraph tmp; HostGraph& hg = host ? host->g : tmp;        // the edges a byte per base: for the host editor, and for the involution
+    hg.K = in.K;
+    if (host || !in.inv) unpack_edges(E, in.edge_packed, in.edge_byte_off, in.edge_len, hg.edges);
     std::vector<int> inv;
-    if (in.inv) inv.assign(in.inv, in.inv + in.n_edge_objs);
-    else W2_TRY(host_involution(g, inv, c.err));
-    // ---- reads and paths on the device
-    ReadsDev R{};
-    PathsDev pd;
-    W2_TRY(upload_reads(c, in, R, pd));
-    const uint64_t n = pd.n;
-
-    std::vector<int32_t> deleted[2];
-    Ms ms[2];
-    const unsigned Lmax = (MAX_RL + K - 1 + 3) & ~3u;
-    for (int pass = 0; pass < (vote_only ? 1 : 2); ++pass) {
-        const uint64_t E = g.edges.size(), NV = g.frm.size();
-        std::vector<char> dead(E, 0);
-        // ---- this pass's graph on the device
-        std::vector<uint8_t> packed; std::vector<uint64_t> boff; std::vector<uint32_t> elen;
-        Csr csr;
-        std::vector<int32_t> bvert, boutdeg;
-        std::vector<Task> tasks;
-        pack_edges(g, packed, boff, elen);
-        make_csr(g, csr);
-        for (uint64_t v = 0; v < NV; ++v) {
-            if (g.to[v].empty() || g.frm[v].size() <= 1) continue;
-            const uint32_t b = (uint32_t)bvert.size();
-            bvert.push_back((int32_t)v); boutdeg.push_back((int32_t)g.frm[v].size());
-            for (int e : g.to_e[v]) tasks.push_back(Task{b, 0u, e, 0u});
-            for (int e : g.frm_e[v]) tasks.push_back(Task{b, 1u, e, 0u});
-            for (int e : g.to_e[v]) tasks.push_back(Task{b, 2u, inv[e], 0u});
-            for (int e : g.frm_e[v]) tasks.push_back(Task{b, 3u, inv[e], 0u});
-        }
-        const uint64_t B = bvert.size(), T = tasks.size();
-        if (B >= (1ull << 27)) { c.err = "more than 2^27 branch vertices"; return W2RAP_E_LIMIT; }
-        out.n_branch_vertices += B;
-        const size_t mark = c.owned.size();
-        if (B) {
-            uint8_t* d_ebits = nullptr; uint64_t* d_ebyte = nullptr; uint32_t* d_elen = nullptr;
-            uint64_t *d_from_off = nullptr, *d_to_off = nullptr; int32_t *d_from_e = nullptr, *d_to_e = nullptr, *d_vright = nullptr, *d_inv = nullptr, *d_bvert = nullptr, *d_outdeg = nullptr;
-            Task* d_tasks = nullptr;
-            std::vector<int32_t> inv32(inv.begin(), inv.end());
-            W2_TRY(up_pooled(c, &d_ebits, packed.data(), packed.size(), 16));
-            W2_TRY(up_pooled(c, &d_ebyte, boff.data(), boff.size()));
-            W2_TRY(up_pooled(c, &d_elen, elen.data(), E));
-            W2_TRY(up_pooled(c, &d_from_off, csr.from_off.data(), NV + 1));
-            W2_TRY(up_pooled(c, &d_to_off, csr.to_off.data(), NV + 1));
-            W2_TRY(up_pooled(c, &d_from_e, csr.from_e.data(), csr.from_e.size()));
-            W2_TRY(up_pooled(c, &d_to_e, csr.to_e.data(), csr.to_e.size()));
-            W2_TRY(up_pooled(c, &d_vright, csr.vright.data(), E));
-            W2_TRY(up_pooled(c, &d_inv, inv32.data(), E));
-            W2_TRY(up_pooled(c, &d_bvert, bvert.data(), B));
-            W2_TRY(up_pooled(c, &d_outdeg, boutdeg.data(), B));
-            W2_TRY(up_pooled(c, &d_tasks, tasks.data(), T));
-            const GraphDev G{K, E, NV, d_elen, d_ebyte, d_ebits, d_from_off, d_from_e, d_to_off, d_to_e, d_vright, d_inv};
-            uint8_t* d_dead = nullptr;
-            W2_ALLOC(d_dead, uint8_t, E + 1);
-            W2_HIP(hipMemsetAsync(d_dead, 0, E + 1, c.stream));
-            W2_TRY(vote_pass(c, G, B, T, d_bvert, d_outdeg, d_tasks, R, pd, Lmax, d_dead, ms[pass], out));
-            W2_HIP(hipMemcpyAsync(dead.data(), d_dead, E, hipMemcpyDeviceToHost, c.stream));
-            W2_HIP(hipStreamSynchronize(c.stream));
-        }
-        // ---- the graph edit (host)
-        std::vector<int32_t> map, add;
-        uint64_t merged = 0;
-        {
-            const auto t0 = std::chrono::steady_clock::now();
-            edit_graph(g, inv, dead, P.min_size, !vote_only, deleted[pass], map, add, merged);
-            ms[pass].host = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-        }
-        out.n_runs_merged[pass] = merged;
-        // ---- the read paths
-        if (!vote_only && n) {
-            int32_t *d_map = nullptr, *d_add = nullptr;
-            W2_TRY(up_pooled(c, &d_map, map.data(), E));
-            W2_TRY(up_pooled(c, &d_add, add.data(), E));
-            PathsDev np;
-            W2_TRY(rewrite_paths(c, pd, d_map, d_add, ms[pass], np));
-            // the new paths replace the old ones; everything else of this pass goes back to the pool
-            std::vector<void*> keep = {np.offset, np.off, np.edges};
-            c.release(pd.offset); c.release(pd.off); c.release(pd.edges);
-            pd = np;
-            std::vector<void*> rest;
-            while (c.owned.size() > mark) { void* p = c.owned.back(); c.owned.pop_back(); if (std::find(keep.begin(), keep.end(), p) != keep.end()) rest.push_back(p); else c.park(p); }
-            for (void* p : rest) c.owned.push_back(p);
-        } else {
-            W2_HIP(hipStreamSynchronize(c.stream));
-            while (c.owned.size() > mark) { void* p = c.owned.back(); c.owned.pop_back(); c.park(p); }
-        }
-    }
-    // ---- results
-    out.K = in.K;
-    std::vector<uint8_t> packed; std::vector<uint64_t> boff; std::vector<uint32_t> elen;
-    Csr csr;
-    pack_edges(g, packed, boff, elen);
-    make_csr(g, csr);
-    out.n_vertices = g.frm.size(); out.n_edge_objs = g.edges.size();
-    out.edge_packed = host_copy(packed); out.edge_byte_off = host_copy(boff); out.edge_len = host_copy(elen);
-    out.vleft = host_copy(csr.vleft); out.vright = host_copy(csr.vright);
-    out.from_off = host_copy(csr.from_off); out.from_v = host_copy(csr.from_v); out.from_e = host_copy(csr.from_e);
-    out.to_off = host_copy(csr.to_off); out.to_v = host_copy(csr.to_v); out.to_e = host_copy(csr.to_e);
-    std::vector<int32_t> inv32(inv.begin(), inv.end());
-    out.inv = host_copy(inv32);
-    for (int k = 0; k < 2; ++k) {
-        out.n_deleted[k] = deleted[k].size(); out.deleted[k] = host_copy(deleted[k]);
-        out.ms_index[k] = ms[k].index; out.ms_vote[k] = ms[k].vote; out.ms_paths[k] = ms[k].paths; out.ms_graph_edit_host[k] = ms[k].host;
-    }
-    W2_TRY(download_paths(c, pd, out));
-    W2_HIP(hipStreamSynchronize(c.stream));
-    if (!out.edge_packed || !out.path_off || !out.inv) { c.err = "out of host memory"; return W2RAP_E_HIP; }
-    return 0;
-}
-
-// ---- Step 4 with the graph edit on the device: one upload, two passes in HBM, one download.  EDIT4_FALLBACK: a precondition of the
-// device edit does not hold (nothing of `out` is to be used; the caller runs step4() instead)
-int step4_device(Ctx& c, const w2rap_step4_in& in, const w2rap_step4_params& P, w2rap_step4_out& out) {
-    const unsigned K = (unsigned)in.K;
-    const uint64_t E0 = in.n_edge_objs, NV0 = in.n_vertices;
-    // ---- the involution and both ends of every edge (host, once, before the upload)
-    std::vector<int32_t> inv32, vleft(E0, -1), vright(E0, -1), to_v(E0, -1);
-    if (in.inv) inv32.assign(in.inv, in.inv + E0);
-    else {
-        HostGraph hg; hg.K = in.K; hg.edges.resize(E0);
-        for (uint64_t e = 0; e < E0; ++e) {
-            hg.edges[e].resize(in.edge_len[e]);
-            const uint8_t* s = in.edge_packed + in.edge_byte_off[e];
-            for (uint32_t i = 0; i < in.edge_len[e]; ++i) hg.edges[e][i] = (s[i >> 2] >> (2 * (i & 3))) & 3u;
-        }
-        std::vector<int> inv;
-        W2_TRY(host_involution(hg, inv, c.err));
-        inv32.assign(inv.begin(), inv.end());
-    }
-    for (uint64_t v = 0; v < NV0; ++v) {
+    if (!in.inv) W2_TRY(host_involution(hg, inv, c.err));
+    else if (host) inv.assign(in.inv, in.inv + E);
+    std::vector<int32_t> vleft(E, -1), vright(E, -1), to_v(E, -1);
+    for (uint64_t v = 0; v < NV; ++v) {
         for (uint64_t i = in.from_off[v]; i < in.from_off[v + 1]; ++i) vleft[in.from_e[i]] = (int32_t)v;
         for (uint64_t i = in.to_off[v]; i < in.to_off[v + 1]; ++i) vright[in.to_e[i]] = (int32_t)v;
     }
-    for (uint64_t i = 0; i < E0; ++i) to_v[i] = vleft[in.to_e[i]];
-    Graph4 g; g.K = K; g.E = E0; g.NV = NV0; g.ebytes_cap = E0 ? in.edge_byte_off[E0] : 0;
-    W2_TRY(up_pooled(c, &g.ebits, in.edge_packed, g.ebytes_cap, 32));
-    W2_TRY(up_pooled(c, &g.ebyte, in.edge_byte_off, in.edge_byte_off ? E0 + 1 : 0));
-    W2_TRY(up_pooled(c, &g.elen, in.edge_len, E0));
-    W2_TRY(up_pooled(c, &g.from_off, in.from_off, in.from_off ? NV0 + 1 : 0));
-    W2_TRY(up_pooled(c, &g.from_v, in.from_v, E0));
-    W2_TRY(up_pooled(c, &g.from_e, in.from_e, E0));
-    W2_TRY(up_pooled(c, &g.to_off, in.to_off, in.to_off ? NV0 + 1 : 0));
-    W2_TRY(up_pooled(c, &g.to_v, (const int32_t*)to_v.data(), E0));
-    W2_TRY(up_pooled(c, &g.to_e, in.to_e, E0));
-    W2_TRY(up_pooled(c, &g.vleft, (const int32_t*)vleft.data(), E0));
-    W2_TRY(up_pooled(c, &g.vright, (const int32_t*)vright.data(), E0));
-    W2_TRY(up_pooled(c, &g.inv, (const int32_t*)inv32.data(), E0));
-    ReadsDev R{};
-    PathsDev pd;
-    W2_TRY(upload_reads(c, in, R, pd));
+    for (uint64_t i = 0; i < E; ++i) to_v[i] = vleft[in.to_e[i]];
+    g = Graph4{}; g.K = (unsigned)in.K; g.E = E; g.NV = NV; g.ebytes_cap = E ? in.edge_byte_off[E] : 0;
+    W2_TRY(upload_graph4(c, g, in.edge_packed, in.edge_byte_off, in.edge_len, in.from_off, in.from_v, in.from_e, in.to_off, to_v.data(), in.to_e,
+                         vleft.data(), vright.data(), in.inv ? in.inv : inv.data()));
+    if (host) {
+        hg.frm.resize(NV); hg.frm_e.resize(NV); hg.to.resize(NV); hg.to_e.resize(NV);
+        for (uint64_t v = 0; v < NV; ++v) {
+            for (uint64_t i = in.from_off[v]; i < in.from_off[v + 1]; ++i) { hg.frm[v].push_back(in.from_v[i]); hg.frm_e[v].push_back(in.from_e[i]); }
+            for (uint64_t i = in.to_off[v]; i < in.to_off[v + 1]; ++i) { hg.to[v].push_back(to_v[i]); hg.to_e[v].push_back(in.to_e[i]); }
+        }
+        host->inv.swap(inv);
+    }
+    // ---- the reads and their paths
+    const uint64_t n = in.n_paths;
+    uint8_t* b = nullptr; uint64_t* bo = nullptr; uint32_t* ln = nullptr; uint8_t* q = nullptr; uint64_t* qo = nullptr;
+    W2_TRY(up_pooled(c, &b, in.read_packed, n ? in.read_byte_off[n] : 0, 16));
+    W2_TRY(up_pooled(c, &bo, in.read_byte_off, in.read_byte_off ? n + 1 : 0));
+    W2_TRY(up_pooled(c, &ln, in.read_len, n));
+    W2_TRY(up_pooled(c, &q, in.quals, n ? in.qual_off[n] : 0, 16));
+    W2_TRY(up_pooled(c, &qo, in.qual_off, in.qual_off ? n + 1 : 0));
+    R = ReadsDev{b, bo, ln, q, qo};
+    P.n = n; P.npe = n ? in.path_off[n] : 0;
+    W2_TRY(up_pooled(c, &P.offset, in.path_offset, n));
+    W2_TRY(up_pooled(c, &P.off, in.path_off, in.path_off ? n + 1 : 0));
+    W2_TRY(up_pooled(c, &P.edges, in.path_edges, P.npe));
     W2_HIP(hipStreamSynchronize(c.stream));                     // (the host vectors above have been read)
+    return 0;
+}
 
-    std::vector<int32_t> deleted[2];
-    Ms ms[2];
-    const unsigned Lmax = (MAX_RL + K - 1 + 3) & ~3u;
-    for (int pass = 0; pass < 2; ++pass) {
+std::vector<void*> blocks(const Graph4& g) {
+    return {g.ebits, g.ebyte, g.elen, g.from_off, g.from_v, g.from_e, g.to_off, g.to_v, g.to_e, g.vleft, g.vright, g.inv};
+}
+
+// the end of a pass that began with c.owned == before: every block allocated since goes back to the pool unless it is in `keep`, and so
+// does every block in `gone` (the pass's inputs) that is not in `keep` as well (an editor that edits nothing hands its input on)
+void retire(Ctx& c, const std::vector<void*>& before, const std::vector<void*>& gone, const std::vector<void*>& keep) {
+    auto has = [](const std::vector<void*>& v, void* p) { return std::find(v.begin(), v.end(), p) != v.end(); };
+    std::vector<void*> owned;
+    for (void* p : c.owned) {
+        if (has(keep, p) || (has(before, p) && !has(gone, p))) owned.push_back(p); else c.park(p);
+    }
+    c.owned.swap(owned);
+}
+
+// Clean200x's passes on device-resident data: g and pd are replaced by the clean graph and the paths on it, still on the device.
+// Of `out` only the counters are touched (n_branch_vertices, n_runs_merged, and what vote_pass counts)
+int passes(Ctx& c, Graph4& g, const ReadsDev& R, PathsDev& pd, const w2rap_step4_params& P, Editor4& ed, std::vector<int32_t> deleted[2], Ms ms[2],
+           w2rap_step4_out& out) {
+    const unsigned Lmax = (MAX_RL + g.K - 1 + 3) & ~3u;
+    for (int pass = 0; pass < ((P.flags & W2RAP_STEP4_VOTE_ONLY) ? 1 : 2); ++pass) {
         const std::vector<void*> before = c.owned;
-        const uint64_t E = g.E, NV = g.NV;
         int32_t *d_bvert = nullptr, *d_outdeg = nullptr; Task* d_tasks = nullptr;
-        uint64_t B = 0, T = 0; bool sorted = true;
-        W2_TRY(edit4_tasks(c, g, &d_bvert, &d_outdeg, &d_tasks, &B, &T, &sorted));
-        if (!sorted) return EDIT4_FALLBACK;
+        uint64_t B = 0, T = 0;
+        W2_TRY(ed.tasks(c, g, &d_bvert, &d_outdeg, &d_tasks, &B, &T));
         if (B >= (1ull << 27)) { c.err = "more than 2^27 branch vertices"; return W2RAP_E_LIMIT; }
         out.n_branch_vertices += B;
         uint8_t* d_dead = nullptr;
-        W2_ALLOC(d_dead, uint8_t, E + 1);
-        W2_HIP(hipMemsetAsync(d_dead, 0, E + 1, c.stream));
+        W2_ALLOC(d_dead, uint8_t, g.E + 1);
+        W2_HIP(hipMemsetAsync(d_dead, 0, g.E + 1, c.stream));
         if (B) {
-            const GraphDev G{K, E, NV, g.elen, g.ebyte, g.ebits, g.from_off, g.from_e, g.to_off, g.to_e, g.vright, g.inv};
+            const GraphDev G{g.K, g.E, g.NV, g.elen, g.ebyte, g.ebits, g.from_off, g.from_e, g.to_off, g.to_e, g.vright, g.inv};
             W2_TRY(vote_pass(c, G, B, T, d_bvert, d_outdeg, d_tasks, R, pd, Lmax, d_dead, ms[pass], out));
         }
-        // ---- the graph edit (device)
+        // ---- the graph edit
         Graph4 next;
         int32_t *d_map = nullptr, *d_add = nullptr;
         uint64_t merged = 0;
         {
             const auto t0 = std::chrono::steady_clock::now();
-            W2_TRY(edit4_pass(c, g, d_dead, P.min_size, &next, &d_map, &d_add, &deleted[pass], &merged));
+            W2_TRY(ed.pass(c, g, d_dead, P.min_size, &next, &d_map, &d_add, &deleted[pass], &merged));
             ms[pass].host = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
         }
         out.n_runs_merged[pass] = merged;
-        // ---- the read paths
-        std::vector<void*> gone = {g.ebits, g.ebyte, g.elen, g.from_off, g.from_v, g.from_e, g.to_off, g.to_v, g.to_e, g.vleft, g.vright, g.inv};
-        std::vector<void*> keep = {next.ebits, next.ebyte, next.elen, next.from_off, next.from_v, next.from_e, next.to_off, next.to_v, next.to_e, next.vleft, next.vright, next.inv};
-        if (pd.n) {
+        // ---- the read paths (no map: nothing was edited)
+        std::vector<void*> gone = blocks(g), keep = blocks(next);
+        if (d_map && pd.n) {
             PathsDev np;
             W2_TRY(rewrite_paths(c, pd, d_map, d_add, ms[pass], np));
             gone.insert(gone.end(), {(void*)pd.offset, (void*)pd.off, (void*)pd.edges});
@@ -813,17 +496,15 @@ int step4_device(Ctx& c, const w2rap_step4_in& in, const w2rap_step4_params& P, 
         W2_HIP(hipStreamSynchronize(c.stream));
         g = next;
         // the new graph and paths replace the old ones; everything else of this pass goes back to the pool
-        std::vector<void*> owned;
-        for (void* p : c.owned) {
-            const bool was = std::find(before.begin(), before.end(), p) != before.end();
-            const bool stays = was ? std::find(gone.begin(), gone.end(), p) == gone.end() : std::find(keep.begin(), keep.end(), p) != keep.end();
-            if (stays) owned.push_back(p); else c.park(p);
-        }
-        c.owned.swap(owned);
+        retire(c, before, gone, keep);
     }
-    // ---- results: the one download of the graph
-    out.K = in.K;
+    return 0;
+}
+
+// the one download of the graph and the paths
+int download(Ctx& c, const Graph4& g, const PathsDev& pd, const std::vector<int32_t> deleted[2], const Ms ms[2], w2rap_step4_out& out) {
     const uint64_t E = g.E, NV = g.NV;
+    out.K = (int32_t)g.K;
     out.n_vertices = NV; out.n_edge_objs = E;
     W2_TRY(dl(c, &out.edge_byte_off, (const uint64_t*)g.ebyte, E + 1));
     W2_TRY(dl(c, &out.edge_len, (const uint32_t*)g.elen, E));
@@ -837,10 +518,33 @@ int step4_device(Ctx& c, const w2rap_step4_in& in, const w2rap_step4_params& P, 
         out.n_deleted[k] = deleted[k].size(); out.deleted[k] = host_copy(deleted[k]);
         out.ms_index[k] = ms[k].index; out.ms_vote[k] = ms[k].vote; out.ms_paths[k] = ms[k].paths; out.ms_graph_edit_host[k] = ms[k].host;
     }
-    W2_TRY(download_paths(c, pd, out));
+    out.n_paths = pd.n;
+    W2_TRY(dl(c, &out.path_offset, (const int32_t*)pd.offset, pd.n));
+    if (pd.n) { W2_TRY(dl(c, &out.path_off, (const uint64_t*)pd.off, pd.n + 1)); }
+    else { out.path_off = (uint64_t*)host_result_alloc(8); if (out.path_off) out.path_off[0] = 0; }
+    W2_TRY(dl(c, &out.path_edges, (const int32_t*)pd.edges, pd.npe));
     W2_HIP(hipStreamSynchronize(c.stream));
     if (!out.edge_packed || !out.path_off || !out.inv) { c.err = "out of host memory"; return W2RAP_E_HIP; }
     return 0;
+}
+
+// Step 4 with the graph edit on the device or on the host.  EDIT4_FALLBACK (device only): a precondition of the device edit does not hold,
+// nothing of `out` is to be used
+int step4(Ctx& c, const w2rap_step4_in& in, const w2rap_step4_params& P, bool on_device, w2rap_step4_out& out) {
+    Graph4 g; ReadsDev R{}; PathsDev pd;
+    std::vector<int32_t> deleted[2];
+    Ms ms[2];
+    if (on_device) {
+        DeviceEditor4 ed;
+        W2_TRY(upload(c, in, g, R, pd, nullptr));
+        W2_TRY(passes(c, g, R, pd, P, ed, deleted, ms, out));
+    } else {
+        HostEditor4 ed;
+        ed.edit = !(P.flags & W2RAP_STEP4_VOTE_ONLY);
+        W2_TRY(upload(c, in, g, R, pd, &ed));
+        W2_TRY(passes(c, g, R, pd, P, ed, deleted, ms, out));
+    }
+    return download(c, g, pd, deleted, ms, out);
 }
 
 }  // namespace
@@ -908,20 +612,17 @@ int w2rap_step4_run(const w2rap_step4_in* in, const w2rap_step4_params* P, w2rap
     c.prof_sums.clear();
     // VOTE_ONLY edits nothing, on either path
     bool on_device = !(P->flags & (W2RAP_STEP4_EDIT_ON_HOST | W2RAP_STEP4_VOTE_ONLY));
-    int rc = 0;
-    if (on_device) {
-        rc = step4_device(c, *in, *P, *out);
-        if (rc == EDIT4_FALLBACK) {                              // start over with the host edit: same result, nothing kept from this attempt
-            on_device = false;
-            (void)hipStreamSynchronize(c.stream);
-            c.presolve();
-            c.prof_sums.clear();
-            c.free_all();
-            c.err.clear();
-            w2rap_step4_free(out);
-        }
+    int rc = step4(c, *in, *P, on_device, *out);
+    if (rc == EDIT4_FALLBACK) {                                  // start over with the host edit: same result, nothing kept from this attempt
+        on_device = false;
+        (void)hipStreamSynchronize(c.stream);
+        c.presolve();
+        c.prof_sums.clear();
+        c.free_all();
+        c.err.clear();
+        w2rap_step4_free(out);
+        rc = step4(c, *in, *P, false, *out);
     }
-    if (!on_device) rc = step4(c, *in, *P, *out);
     std::string msg = c.err;
     (void)hipStreamSynchronize(c.stream);
     c.presolve();

@@ -1,4 +1,4 @@
-// step4_edit.hip -- Step 4's graph edit on the device: what edit_graph() in step4_clean.hip does on the host, statement for statement in
+// step4_edit.hip -- Step 4's graph edit on the device: what edit_graph() in step4_host.hip does on the host, statement for statement in
 // effect, from one pass's Graph4 to the next one's without the graph leaving HBM.
 //
 //   k4e_min_size                        Clean200.cc:370-380, one thread per vertex
@@ -347,9 +347,9 @@ template <class T> void drop(Ctx& c, T*& p) { c.release(p); p = nullptr; }
 
 }  // namespace
 
-int edit4_tasks(Ctx& c, const Graph4& g, int32_t** d_bvert, int32_t** d_outdeg, Task** d_tasks, uint64_t* B, uint64_t* T, bool* sorted) {
+int DeviceEditor4::tasks(Ctx& c, const Graph4& g, int32_t** d_bvert, int32_t** d_outdeg, Task** d_tasks, uint64_t* B, uint64_t* T) {
     const uint64_t NV = g.NV;
-    *B = *T = 0; *sorted = true; *d_bvert = nullptr; *d_outdeg = nullptr; *d_tasks = nullptr;
+    *B = *T = 0; *d_bvert = nullptr; *d_outdeg = nullptr; *d_tasks = nullptr;
     if (!NV) return 0;
     const GV G = view(g);
     uint32_t *isb = nullptr, *ntask = nullptr, *fail = nullptr; uint64_t *bidx = nullptr, *toff = nullptr;
@@ -364,17 +364,16 @@ int edit4_tasks(Ctx& c, const Graph4& g, int32_t** d_bvert, int32_t** d_outdeg, 
     W2_HIP(hipMemcpyAsync(T, toff + NV, 8, hipMemcpyDeviceToHost, c.stream));
     W2_HIP(hipMemcpyAsync(&h_fail, fail, 4, hipMemcpyDeviceToHost, c.stream));
     W2_HIP(hipStreamSynchronize(c.stream));
-    *sorted = h_fail == 0;
     if (*B && *B < (1ull << 27)) {
         W2_ALLOC(*d_bvert, int32_t, *B + 1); W2_ALLOC(*d_outdeg, int32_t, *B + 1); W2_ALLOC(*d_tasks, Task, *T + 1);
         RUN4("k4e_branch_fill", k4e_branch_fill, NV, G, (const uint64_t*)bidx, (const uint64_t*)toff, *d_bvert, *d_outdeg, *d_tasks);
     }
     drop(c, isb); drop(c, ntask); drop(c, fail); drop(c, bidx); drop(c, toff);
-    return 0;
+    return h_fail ? EDIT4_FALLBACK : 0;
 }
 
-int edit4_pass(Ctx& c, const Graph4& g, uint8_t* d_dead, unsigned min_size, Graph4* next, int32_t** d_map, int32_t** d_add,
-               std::vector<int32_t>* deleted, uint64_t* n_merged) {
+int DeviceEditor4::pass(Ctx& c, const Graph4& g, uint8_t* d_dead, unsigned min_size, Graph4* next, int32_t** d_map, int32_t** d_add,
+                        std::vector<int32_t>* deleted, uint64_t* n_merged) {
     const uint64_t E = g.E, NV = g.NV;
     deleted->clear(); *n_merged = 0;
     if (!E || !NV) return EDIT4_FALLBACK;                      // nothing to run a kernel on: the host edit handles the empty graph
