@@ -56,7 +56,7 @@ typedef struct w2rap_step3_params {
                                         every unique place is also entered with the sole edge into its first vertex in front and the sole
                                         edge out of its last vertex behind.  Needs in->vleft / vright (W2RAP_E_ARG without them) */
     const w2rap_edge_hint* edge_order_hint;   /* NULL = canonical (lexicographic) order of the large-K unipaths */
-    uint32_t flags;                  /* W2RAP_STEP3_NO_FETCH: compute everything, copy only the counters back (timing runs) */
+    uint32_t flags;                  /* W2RAP_STEP3_NO_FETCH: compute everything, copy only the counters back (timing runs, and the chained Step 4) */
     /* multi-GPU (reads sharded by rank, graph replicated): read paths of OTHER ranks that stand for their unique places.  They take part
        in the places / large-K graph exactly like local reads (so every rank builds the same graph) and produce no output path. */
     uint64_t n_extra_paths;
@@ -71,6 +71,13 @@ typedef struct w2rap_step3_params {
                                         occurrence, and the dictionary (BigKPather.cc:40-55) leaves it out of the hashing: same result, ~78 % fewer keys.
                                         w2rap_step3_run_after_step2 sets it by itself (the graph is Step 2's own).  Without the flag every K2-mer is
                                         grouped by content, whatever the graph */
+#define W2RAP_STEP3_KEEP_DEVICE 8u   /* w2rap_step3_run_after_step2 only (W2RAP_E_ARG from w2rap_step3_run, with PLACES_ONLY, or with n_extra_paths != 0): the
+                                        large-K graph, its involution and the read paths on it are not parked at the end of the call but recorded in the
+                                        context as its kept large-K result, the input of w2rap_step2_run_step4_after_step3 (w2rap_step4.h).  Combines with
+                                        NO_FETCH: then nothing but the counters and frag_count comes down.  The kept result is given up -- its device
+                                        blocks go back to the context's pool -- when anything it was derived from changes (set_reads, count_kmers, the
+                                        dict_* / count_records / shard entry points, build_graph, path_reads), at the next w2rap_step3_run_after_step2 with
+                                        or without the flag, when a full chained Step 4 has consumed it, and at w2rap_step2_destroy */
 
 /* ---- outputs (library-allocated HOST memory; free with w2rap_step3_free) ------------------------------------------------- */
 typedef struct w2rap_step3_out {

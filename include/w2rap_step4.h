@@ -20,6 +20,12 @@
  * mirror image is itself a run with the mirrored ends -- or has no edges falls back to it silently, with the same result.
  * w2rap_step4_profile tells which one ran.
  *
+ * Behind Step 3 in one process.  w2rap_step2_run_step4_after_step3 replaces the same block of main in the reference's default flow, where hbvr,
+ * pathsr, bases and quals are the objects Steps 1-3 left in memory: its inputs are a Step-2 context's reads and qualities and the large-K
+ * result that w2rap_step3_run_after_step2 left in that context's HBM (W2RAP_STEP3_KEEP_DEVICE, w2rap_step3.h); inv is Step 3's inv2.
+ * Nothing is uploaded, validated on the host or rebuilt there; the vote and edit kernels are the same, and the clean graph and paths
+ * come down once.  The reads never come down.
+ *
  * Plain pointers and sizes; never throws; returns 0 or a W2RAP_E_* code (w2rap_step2.h) with a message in `err`.  Integer arithmetic
  * throughout: results are exact, byte for byte the reference's.
  */
@@ -110,9 +116,22 @@ typedef struct w2rap_step4_out {
 int  w2rap_step4_run(const w2rap_step4_in* in, const w2rap_step4_params* params, w2rap_step4_out* out, char* err, size_t errlen);
 void w2rap_step4_free(w2rap_step4_out* out);
 
-/* per-kernel device time of the last w2rap_step4_run in this process: "kernel_name total_ms launches\n" lines; returns the bytes needed.
+/* Step 4 straight behind Step 3, a call on the Step-2 context like w2rap_step2_fetch (hence its prefix: the w2rap_step4_* names are the
+ * three of the one-shot interface, and stay those three): `ctx` has run w2rap_step3_run_after_step2 with W2RAP_STEP3_KEEP_DEVICE and nothing since that gives the
+ * kept result up (w2rap_step3.h).  params->device must be the context's device (W2RAP_E_ARG).  W2RAP_E_STATE, with a message that names
+ * the missing step, when the context holds no kept result or its reads' raw qualities were never uploaded (a graph-only Step 2).
+ * A full run consumes the kept result -- pass 1's inputs go back to the context's pool as soon as pass 1 is through -- so a second call
+ * answers W2RAP_E_STATE; W2RAP_STEP4_VOTE_ONLY edits nothing and leaves it valid, so a vote can be followed by the full run.  With
+ * W2RAP_STEP4_EDIT_ON_HOST, VOTE_ONLY, or a graph that misses a precondition of the device edit (then from the pass that found it on),
+ * the host editor works on one download of the graph as it lies on the device.  On any failure the kept result is given up and every
+ * device block of the call goes back to the pool.  Whatever happens, the context's Step-2 state is not touched (w2rap_step2_fetch and
+ * another Step 3 work afterwards) and its live device bytes return to what they were before Step 3 kept anything. */
+int  w2rap_step2_run_step4_after_step3(w2rap_step2_ctx* ctx, const w2rap_step4_params* params, w2rap_step4_out* out, char* err, size_t errlen);
+
+/* per-kernel device time of the last w2rap_step4_run or w2rap_step2_run_step4_after_step3 in this process: "kernel_name total_ms launches\n" lines; returns the bytes needed.
  * The device edit's time is the sum of the k4e_* lines.  The last line, in the same format, is "edit_path_device <0|1> <passes>": 1 and
- * the number of passes edited on the device, or 0 0 when the host edit ran (EDIT_ON_HOST, the fallback) or nothing was edited (VOTE_ONLY) */
+ * the number of passes edited on the device, or 0 0 when the host edit ran (EDIT_ON_HOST, the fallback -- also one that the chained call
+ * took in pass 2 only) or nothing was edited (VOTE_ONLY) */
 size_t w2rap_step4_profile(char* buf, size_t len);
 
 #ifdef __cplusplus

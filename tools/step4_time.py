@@ -1,13 +1,15 @@
 """Times Step 4 (Clean200x) behind Steps 2 and 3 on the planted workload and prints one JSON line.
 
-    python tools/step4_time.py [--reads 4000000] [--seed 77] [--min_freq 4] [--min_size 0] [--repeats 3] [--reference] [--host_edit]
+    python tools/step4_time.py [--reads 4000000] [--seed 77] [--min_freq 4] [--min_size 0] [--repeats 3] [--reference] [--host_edit] [--chained]
 
 Per pass: ms_index, ms_vote, ms_paths (device events) and ms_graph_edit_host (host clock, NOT device time); ms_k4e_sum, the device
 time of the graph edit's kernels (the k4e_* lines of the profile, both passes; 0 with --host_edit); placements per second of the
 scoring kernel; the per-kernel table of w2rap_step4_profile; the scoring kernel's bytes per second, loaded (mostly from L2) and compulsory
 (against the 8 TB/s HBM roof).  The figures are
 those of the LAST of --repeats runs (the first ones warm the context's memory pool).  --reference: the wall time of the reference's
-own Step 4 (oracle/_ref/w2rap-contigger-gpu --from_step 4 --to_step 4) on the same files, with a same-output verdict."""
+own Step 4 (oracle/_ref/w2rap-contigger-gpu --from_step 4 --to_step 4) on the same files, with a same-output verdict.
+--chained: the same workload through the device-resident hand-over.  The reads go once into a Step2Context; every repeat runs count,
+graph, paths, Step 3 with keep_on_device and no fetch, then step4.clean200x_after_step3; wall_s_call is that last call alone."""
 import argparse
 import json
 import os
@@ -35,6 +37,7 @@ def main():
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--reference", action="store_true")
     ap.add_argument("--host_edit", action="store_true", help="edit the graph on the host (W2RAP_STEP4_EDIT_ON_HOST)")
+    ap.add_argument("--chained", action="store_true", help="Step 4 behind Step 3 in HBM (w2rap_step2_run_step4_after_step3), not on host arrays")
     a = ap.parse_args()
     import torch
     d = bench.planted_reads(a.reads, a.seed, torch.device("cuda", 0))
@@ -45,17 +48,33 @@ def main():
     del d
     torch.cuda.empty_cache()
     pk, bo, ln = F.pack_bases(codes, off)
-    r2 = step2.build_read_qgraph(pk, bo, ln, quals=quals, qual_off=off, min_freq=a.min_freq)
-    r3 = step3.repath_in_memory(r2.hbv, (r2.path_offset, r2.path_off, r2.path_edges), 200)
-    paths = (r3.path_offset, r3.path_off, r3.path_edges)
+    edit = "host" if a.host_edit else "device"
+    ctx = None
+    if a.chained:
+        if a.reference:
+            ap.error("--reference needs the large-K files, which --chained never brings down")
+        ctx = step2.Step2Context(0)
+        ctx.set_reads_host(pk, bo, ln, quals=quals, qual_off=off)
+    else:
+        r2 = step2.build_read_qgraph(pk, bo, ln, quals=quals, qual_off=off, min_freq=a.min_freq)
+        r3 = step3.repath_in_memory(r2.hbv, (r2.path_offset, r2.path_off, r2.path_edges), 200)
+        paths = (r3.path_offset, r3.path_off, r3.path_edges)
     walls, k4e = [], []
     for _ in range(max(1, a.repeats)):
+        if a.chained:
+            ctx.count_kmers(7, a.min_freq); ctx.build_graph(None); ctx.path_reads()
+            r3 = step3.repath_after_step2(ctx, 200, fetch=False, keep_on_device=True)
         t0 = time.perf_counter()
-        r4 = step4.clean200x(r3.hbv, paths, pk, bo, ln, quals, off, min_size=a.min_size, inv=r3.inv2, edit="host" if a.host_edit else "device")
+        if a.chained:
+            r4 = step4.clean200x_after_step3(ctx, min_size=a.min_size, edit=edit)
+        else:
+            r4 = step4.clean200x(r3.hbv, paths, pk, bo, ln, quals, off, min_size=a.min_size, inv=r3.inv2, edit=edit)
         wall = time.perf_counter() - t0
         walls.append(round(wall, 4))
         k4e.append(round(sum(v[0] for k, v in step4.profile().items() if k.startswith("k4e_")), 4))
         print(f"call {len(walls)}: wall {wall:.4f} s, k4e_* {k4e[-1]:.4f} ms", file=sys.stderr)
+    if ctx is not None:
+        ctx.close()
     prof = step4.profile()
     edit_path = prof.pop("edit_path_device", (0.0, 0))
     score_ms = prof.get("k4_score", (0.0, 0))[0]
@@ -67,8 +86,8 @@ def main():
     n_reads = len(ln)
     bytes_loaded = r4.n_placements * (synth.READ_LEN * (16 + 1 + 0.25) + 24)
     bytes_compulsory = r4.n_placements * 24 + 2 * n_reads * synth.READ_LEN * 1.25 + r4.n_branch_vertices * ((L + 3) // 4 * 4) * 16
-    out = {"workload": f"bench.planted_reads({a.reads}, {a.seed})", "min_freq": a.min_freq, "min_size": a.min_size, "walk_positions": L,
-           "large_K_edge_objects_in": int(r3.hbv.n_edges), "edge_objects_out": int(r4.hbv.n_edges),
+    out = {"workload": f"bench.planted_reads({a.reads}, {a.seed})", "entry": "w2rap_step2_run_step4_after_step3" if a.chained else "w2rap_step4_run", "min_freq": a.min_freq, "min_size": a.min_size, "walk_positions": L,
+           "large_K_edge_objects_in": int(r3.n_edge_objs), "edge_objects_out": int(r4.hbv.n_edges),
            "n_branch_vertices": r4.n_branch_vertices, "n_skipped_too_many_exts": r4.n_skipped_too_many_exts, "n_placements": r4.n_placements,
            "n_deleted": list(r4.n_deleted), "n_runs_merged": list(r4.n_runs_merged),
            "ms_index": [round(x, 3) for x in r4.ms_index], "ms_vote": [round(x, 3) for x in r4.ms_vote], "ms_paths": [round(x, 3) for x in r4.ms_paths],

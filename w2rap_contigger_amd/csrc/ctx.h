@@ -243,6 +243,31 @@ struct Ctx {
         for (void* p : owned) park(p);
         owned.clear();
     }
+
+    // ---- the large-K result a Step 3 run with W2RAP_STEP3_KEEP_DEVICE left in HBM for w2rap_step2_run_step4_after_step3.  Its blocks belong to
+    // this record and to nobody else (they are in neither `owned` nor `owned_reads`): the chained Step 4 takes them over, and drop_kept()
+    // parks them as soon as anything the result was derived from changes -- new reads, a new count, dictionary, graph or read paths, the
+    // sharded entry points, another Step 3 -- or the context is destroyed
+    struct Kept3 {
+        bool valid = false;
+        unsigned K2 = 0; uint64_t E = 0, NV = 0, n = 0, path_ints = 0, edge_bytes = 0;
+        uint8_t* ebits = nullptr;           // edge_bytes + 33 bytes, the last 33 zeroed: the slack k4_walks and k4e_gather read
+        uint64_t* ebyte = nullptr; uint32_t* elen = nullptr;
+        int32_t* left = nullptr; int32_t* right = nullptr;
+        uint64_t* from_off = nullptr; int32_t* from_v = nullptr; int32_t* from_e = nullptr;
+        uint64_t* to_off = nullptr; int32_t* to_v = nullptr; int32_t* to_e = nullptr;
+        int32_t* inv2 = nullptr;
+        int32_t* p_offset = nullptr; uint64_t* p_off = nullptr; int32_t* p_edges = nullptr;
+        std::vector<void*> blocks() const {
+            return {ebits, ebyte, elen, left, right, from_off, from_v, from_e, to_off, to_v, to_e, inv2, p_offset, p_off, p_edges};
+        }
+    };
+    Kept3 kept;
+    void drop_kept() {
+        if (!kept.valid) return;
+        for (void* p : kept.blocks()) release(p);
+        kept = Kept3{};
+    }
 };
 
 // Test switches read from the environment never act silently: a set hook is announced on stderr every time it is honoured.

@@ -65,6 +65,7 @@ void drop_results(Ctx& c) {
     if (c.stream) (void)hipStreamSynchronize(c.stream);
     if (c.stream2) (void)hipStreamSynchronize(c.stream2);
     shard_free(c);
+    c.drop_kept();                                     // (a large-K result kept for Step 4 was derived from what goes now)
     c.free_all();
     c.d_good = nullptr; c.d_bcount = nullptr; c.d_bbase = nullptr; c.d_recs = nullptr; c.d_shi = c.d_slo = nullptr; c.d_scc = nullptr;
     c.d_table = nullptr; c.d_filter32 = nullptr; c.f32words = 0; c.d_sctx = nullptr; c.d_nbr = nullptr; c.d_srec = nullptr; c.d_index = nullptr; c.index_cap = 0; c.d_xindex = nullptr; c.xindex_cap = 0; c.d_unres = nullptr; c.fused_prune = false; c.unfused_chunks.clear();
@@ -346,6 +347,7 @@ int w2rap_step2_partition_range(w2rap_step2_ctx* h, uint32_t n_buckets, uint32_t
                                 uint64_t* recs_per_part, uint64_t* kmers_per_part) {
     if (!h || !n_buckets || !n_parts || end_bucket > n_buckets || first_bucket >= end_bucket || (end_bucket - first_bucket) % n_parts) return W2RAP_E_ARG;
     Ctx& c = h->c;
+    c.drop_kept();
     W2_HIP(hipSetDevice(c.device));
     Timer t(c.stream);
     if (n_parts > 64) { c.err = "partition: more than 64 parts"; return W2RAP_E_LIMIT; }
@@ -374,6 +376,7 @@ int w2rap_step2_partition(w2rap_step2_ctx* h, uint32_t n_buckets, uint32_t n_par
 int w2rap_step2_count_pass(w2rap_step2_ctx* h, uint32_t pass, uint32_t n_passes) {
     if (!h || !n_passes || pass >= n_passes) return W2RAP_E_ARG;
     Ctx& c = h->c;
+    c.drop_kept();
     if (c.cs_planned) { c.err = "count_pass while a sliced count is pending"; return W2RAP_E_STATE; }
     if (pass && !c.pass_cnt) { c.err = "count_pass: passes go in order, each one counted before the next"; return W2RAP_E_STATE; }
     c.pass = pass; c.npass = n_passes;
@@ -394,6 +397,7 @@ int w2rap_step2_count_records_begin(w2rap_step2_ctx* h, uint32_t min_freq, uint3
                                     const void* d_counts, uint64_t total_kmers, uint32_t n_slices, int deferred) {
     if (!h || !n_local_buckets || !n_segments || !d_counts) return W2RAP_E_ARG;
     Ctx& c = h->c;
+    c.drop_kept();
     W2_HIP(hipSetDevice(c.device));
     return count_buckets_launch(c, min_freq, n_local_buckets, n_segments, (const uint32_t*)d_records, (const uint32_t*)d_counts, total_kmers,
                                 n_slices ? n_slices : 1, deferred != 0);
@@ -412,6 +416,7 @@ int w2rap_step2_count_records_bounds(w2rap_step2_ctx* h, uint32_t k, uint32_t* f
 int w2rap_step2_count_records_launch(w2rap_step2_ctx* h, uint32_t k) {
     if (!h) return W2RAP_E_ARG;
     Ctx& c = h->c;
+    c.drop_kept();
     W2_HIP(hipSetDevice(c.device));
     return count_buckets_launch_slice(c, k);
 }
@@ -419,6 +424,7 @@ int w2rap_step2_count_records_launch(w2rap_step2_ctx* h, uint32_t k) {
 int w2rap_step2_count_records_slice(w2rap_step2_ctx* h, uint32_t k, uint64_t* n_solid, uint64_t* n_chunks) {
     if (!h) return W2RAP_E_ARG;
     Ctx& c = h->c;
+    c.drop_kept();
     W2_HIP(hipSetDevice(c.device));
     return count_buckets_slice(c, k, n_solid, n_chunks);
 }
@@ -426,6 +432,7 @@ int w2rap_step2_count_records_slice(w2rap_step2_ctx* h, uint32_t k, uint64_t* n_
 int w2rap_step2_count_records_end(w2rap_step2_ctx* h, w2rap_step2_out* stats) {
     if (!h) return W2RAP_E_ARG;
     Ctx& c = h->c;
+    c.drop_kept();
     W2_HIP(hipSetDevice(c.device));
     int rc = count_buckets_finish(c);
     c.presolve();
@@ -438,6 +445,7 @@ int w2rap_step2_count_records(w2rap_step2_ctx* h, uint32_t min_freq, uint32_t n_
                               const void* d_counts, uint64_t total_kmers, w2rap_step2_out* stats) {
     if (!h || !n_local_buckets || !n_segments || !d_counts) return W2RAP_E_ARG;
     Ctx& c = h->c;
+    c.drop_kept();
     W2_HIP(hipSetDevice(c.device));
     Timer t(c.stream);
     int rc = count_buckets(c, min_freq, n_local_buckets, n_segments, (const uint32_t*)d_records, (const uint32_t*)d_counts, total_kmers);
@@ -472,6 +480,7 @@ int w2rap_step2_chunk_buffers(w2rap_step2_ctx* h, void** d_start, void** d_count
 int w2rap_step2_dict_begin(w2rap_step2_ctx* h, uint64_t kmer_capacity, uint64_t chunk_capacity) {
     if (!h) return W2RAP_E_ARG;
     Ctx& c = h->c;
+    c.drop_kept();
     W2_HIP(hipSetDevice(c.device));
     return dict_begin(c, kmer_capacity, chunk_capacity);
 }
@@ -480,6 +489,7 @@ int w2rap_step2_dict_append(w2rap_step2_ctx* h, const void* d_hi, const void* d_
                             const void* d_chunk_start, const void* d_chunk_count, uint64_t n_chunks) {
     if (!h || (n && (!d_hi || !d_lo || !d_cc)) || (n_chunks && (!d_chunk_start || !d_chunk_count))) return W2RAP_E_ARG;
     Ctx& c = h->c;
+    c.drop_kept();
     W2_HIP(hipSetDevice(c.device));
     return dict_append(c, (const uint64_t*)d_hi, (const uint64_t*)d_lo, (const uint32_t*)d_cc, n, (const uint64_t*)d_chunk_start,
                        (const uint32_t*)d_chunk_count, n_chunks);
@@ -490,6 +500,7 @@ int w2rap_step2_dict_append_slice(w2rap_step2_ctx* h, const void* d_hi, const vo
                                   const void* d_chunk_start, const void* d_chunk_count, uint64_t n_chunks, uint64_t chunk_bias) {
     if (!h || (n && (!d_hi || !d_lo || !d_cc)) || (n_chunks && (!d_chunk_start || !d_chunk_count))) return W2RAP_E_ARG;
     Ctx& c = h->c;
+    c.drop_kept();
     W2_HIP(hipSetDevice(c.device));
     return dict_append(c, (const uint64_t*)d_hi, (const uint64_t*)d_lo, (const uint32_t*)d_cc, n, (const uint64_t*)d_chunk_start,
                        (const uint32_t*)d_chunk_count, n_chunks, chunk_bias);
@@ -498,6 +509,7 @@ int w2rap_step2_dict_append_slice(w2rap_step2_ctx* h, const void* d_hi, const vo
 int w2rap_step2_dict_end(w2rap_step2_ctx* h, uint64_t M, uint64_t D, const uint64_t* hist101) {
     if (!h) return W2RAP_E_ARG;
     Ctx& c = h->c;
+    c.drop_kept();
     W2_HIP(hipSetDevice(c.device));
     Timer t(c.stream);
     c.M = M; c.D = D;
@@ -511,6 +523,7 @@ int w2rap_step2_dict_end(w2rap_step2_ctx* h, uint64_t M, uint64_t D, const uint6
 int w2rap_step2_dict_abort(w2rap_step2_ctx* h) {
     if (!h) return W2RAP_E_ARG;
     (void)hipSetDevice(h->c.device);
+    h->c.drop_kept();
     dict_abort(h->c);
     return 0;
 }
@@ -536,6 +549,7 @@ int w2rap_step2_set_solid(w2rap_step2_ctx* h, const void* d_hi, const void* d_lo
 int w2rap_step2_build_graph(w2rap_step2_ctx* h, const w2rap_edge_hint* hint) {
     if (!h) return W2RAP_E_ARG;
     Ctx& c = h->c;
+    c.drop_kept();
     W2_HIP(hipSetDevice(c.device));
     if (c.graphed) { c.err = "build_graph called twice; call count_kmers again"; return W2RAP_E_STATE; }
     if (hint) {                                       // the hint's arrays are read by kernels: their offsets must be what the lengths say
@@ -555,6 +569,7 @@ int w2rap_step2_build_graph(w2rap_step2_ctx* h, const w2rap_edge_hint* hint) {
 int w2rap_step2_path_reads(w2rap_step2_ctx* h) {
     if (!h) return W2RAP_E_ARG;
     Ctx& c = h->c;
+    c.drop_kept();
     W2_HIP(hipSetDevice(c.device));
     if (c.pathed_done) { c.err = "path_reads called twice"; return W2RAP_E_STATE; }
     if (c.quals_absent) { c.err = "path_reads: the reads were installed by a graph-only call, their qualities were not uploaded"; return W2RAP_E_STATE; }
@@ -792,6 +807,7 @@ int w2rap_step2_shard_begin(w2rap_step2_ctx* h, uint32_t rank, uint32_t world, c
                             const uint64_t* hist101, const w2rap_edge_hint* hint) {
     if (!h || !solid_per_rank) return W2RAP_E_ARG;
     Ctx& c = h->c;
+    c.drop_kept();
     W2_HIP(hipSetDevice(c.device));
     if (hint) {
         if (hint->n_edges && (!hint->packed || !hint->byte_off || !hint->len)) { c.err = "edge_order_hint: null array"; return W2RAP_E_HINT; }
@@ -807,12 +823,14 @@ int w2rap_step2_shard_begin(w2rap_step2_ctx* h, uint32_t rank, uint32_t world, c
 int w2rap_step2_local_dict_slice(w2rap_step2_ctx* h, uint64_t n_solid, uint64_t expected_total) {
     if (!h) return W2RAP_E_ARG;
     Ctx& c = h->c;
+    c.drop_kept();
     W2_HIP(hipSetDevice(c.device));
     return local_dict_slice(c, n_solid, expected_total);
 }
 int w2rap_step2_shard_next(w2rap_step2_ctx* h, w2rap_xchg* x) {
     if (!h || !x) return W2RAP_E_ARG;
     Ctx& c = h->c;
+    c.drop_kept();
     W2_HIP(hipSetDevice(c.device));
     Timer t(c.stream);
     const int rc = shard_next(c, x);
@@ -823,6 +841,7 @@ int w2rap_step2_shard_next(w2rap_step2_ctx* h, w2rap_xchg* x) {
 int w2rap_step2_shard_recv(w2rap_step2_ctx* h, const uint64_t* recv_count, uint32_t elem_bytes, void** d_recv) {
     if (!h || !recv_count || !d_recv || !elem_bytes) return W2RAP_E_ARG;
     (void)hipSetDevice(h->c.device);
+    h->c.drop_kept();
     return shard_recv(h->c, recv_count, elem_bytes, d_recv);
 }
 int w2rap_step2_shard_host_words(w2rap_step2_ctx* h, const uint64_t* words) { return h && words ? shard_host_words(h->c, words) : W2RAP_E_ARG; }

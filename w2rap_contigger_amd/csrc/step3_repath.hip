@@ -2000,7 +2000,10 @@ int step3(Ctx& c, const DevIn& in, const w2rap_step3_params& P, w2rap_step3_out&
     W2_TRY(exclusive_scan_u32_to_u64(c, d_nby, d_byoff, NO2));
     uint64_t total_bytes = 0;
     W2_HIP(hipMemcpy(&total_bytes, d_byoff + NO2, 8, hipMemcpyDeviceToHost));
-    W2_ALLOC(d_packed, uint8_t, total_bytes + 1);
+    // 32 zeroed bytes of slack behind the last edge (for every caller: they cost nothing): Step 4's k4_walks and k4e_gather read past it,
+    // and with W2RAP_STEP3_KEEP_DEVICE this block becomes Graph4::ebits as it stands, without a copy
+    W2_ALLOC(d_packed, uint8_t, total_bytes + 33);
+    W2_HIP(hipMemsetAsync(d_packed + total_bytes, 0, 33, st));
     if (total_bytes) {
         uint32_t* bblk = nullptr;
         W2_TRY(block_index(c, (const uint64_t*)d_byoff, NO2, total_bytes, &bblk));
@@ -2035,6 +2038,16 @@ int step3(Ctx& c, const DevIn& in, const w2rap_step3_params& P, w2rap_step3_out&
         for (uint32_t b : hb) out.n_place_bases += b;
     }
     out.n_kmer_instances = N2; out.n_kmers_distinct = D; out.n_unipaths = E;
+    if (P.flags & W2RAP_STEP3_KEEP_DEVICE) {     // the large-K result stays in HBM: its blocks leave `owned` (the caller parks what is left there)
+        Ctx::Kept3& k = c.kept;
+        k = Ctx::Kept3{};
+        k.K2 = K2; k.E = NO2; k.NV = NV; k.n = n; k.path_ints = npath_ints; k.edge_bytes = total_bytes;
+        k.ebits = d_packed; k.ebyte = d_byoff; k.elen = d_olen; k.left = left; k.right = right;
+        k.from_off = from_off; k.from_v = from_v; k.from_e = from_e; k.to_off = to_off; k.to_v = to_v; k.to_e = to_e; k.inv2 = inv2;
+        k.p_offset = o_offset; k.p_off = o_off; k.p_edges = o_edges;
+        for (void* p : k.blocks()) c.owned.erase(std::find(c.owned.begin(), c.owned.end(), p));
+        k.valid = true;
+    }
     return 0;
 }
 
@@ -2057,6 +2070,7 @@ int w2rap_step3_run(const w2rap_step3_in* in, const w2rap_step3_params* P, w2rap
     if (!in || !P || !out) return fail(W2RAP_E_ARG, "null argument");
     std::memset(out, 0, sizeof(*out));
     if (in->K < 16 || in->K > 64) return fail(W2RAP_E_ARG, "small K must be in [16, 64] (the reference runs Step 2 at K = 60)");
+    if (P->flags & W2RAP_STEP3_KEEP_DEVICE) return fail(W2RAP_E_ARG, "W2RAP_STEP3_KEEP_DEVICE needs a Step-2 context to keep the result in: w2rap_step3_run_after_step2 only");
     if (P->K2 & 1 || P->K2 <= (uint32_t)in->K || P->K2 > 32 * MAXW) return fail(W2RAP_E_ARG, "K2 must be even, larger than K and at most 640");
     if (P->extend_paths && in->n_edge_objs && (!in->vleft || !in->vright)) return fail(W2RAP_E_ARG, "extend_paths needs the vertices of the small-K graph (vleft, vright)");
     if (P->n_extra_paths && (!P->extra_path_off || (P->extra_path_off[P->n_extra_paths] && !P->extra_path_edges))) return fail(W2RAP_E_ARG, "null extra path array");
@@ -2115,9 +2129,12 @@ int w2rap_step3_run_after_step2(w2rap_step2_ctx* h, const w2rap_step3_params* P,
     if (P->n_extra_paths && (!P->extra_path_off || (P->extra_path_off[P->n_extra_paths] && !P->extra_path_edges))) return fail(W2RAP_E_ARG, "null extra path array");
     if (P->n_extra_paths && P->extra_path_off[0] != 0) return fail(W2RAP_E_ARG, "extra_path_off must start at 0");
     for (uint64_t r = 0; r < P->n_extra_paths; ++r) if (P->extra_path_off[r + 1] < P->extra_path_off[r]) return fail(W2RAP_E_ARG, "extra_path_off is not ascending");
+    if ((P->flags & W2RAP_STEP3_KEEP_DEVICE) && ((P->flags & W2RAP_STEP3_PLACES_ONLY) || P->n_extra_paths))
+        return fail(W2RAP_E_ARG, "W2RAP_STEP3_KEEP_DEVICE goes with neither PLACES_ONLY nor extra paths: the chained Step 4 is one GPU, all reads");
     Ctx& c = h->c;
     if (!c.graphed || !c.pathed_done) return fail(W2RAP_E_STATE, "w2rap_step3_run_after_step2: the context has not run build_graph and path_reads");
     if (hipSetDevice(c.device) != hipSuccess) return fail(W2RAP_E_HIP, "hipSetDevice failed");
+    c.drop_kept();                               // an earlier kept result dies here, whether this call keeps one or not
     c.prof_sums.clear();
     auto body = [&]() -> int {
         const uint64_t NO = c.NO;
@@ -2143,6 +2160,7 @@ int w2rap_step3_run_after_step2(w2rap_step2_ctx* h, const w2rap_step3_params* P,
     int rc = body();
     (void)hipStreamSynchronize(c.stream);
     while (c.owned.size() > mark) { void* p = c.owned.back(); c.owned.pop_back(); c.park(p); }
+    if (rc) c.drop_kept();
     std::string msg = c.err;
     save_profile(c);
     if (rc) { w2rap_step3_free(out); return fail(rc, msg); }

@@ -312,6 +312,15 @@ template <class T> T* host_copy(const std::vector<T>& v) {
 
 std::string g_profile4;
 
+// per-kernel times of this run and which editor ran -> w2rap_step4_profile
+void save_profile4(Ctx& c, bool on_device) {
+    (void)hipStreamSynchronize(c.stream);
+    c.presolve();
+    g_profile4.clear();
+    for (auto& s : c.prof_sums) { char line[256]; std::snprintf(line, sizeof line, "%s %.4f %llu\n", s.name.c_str(), s.ms, (unsigned long long)s.launches); g_profile4 += line; }
+    { char line[64]; std::snprintf(line, sizeof line, "edit_path_device %d %d\n", on_device ? 1 : 0, on_device ? 2 : 0); g_profile4 += line; }
+}
+
 struct Ms { float index = 0, vote = 0, paths = 0, host = 0; };
 struct PathsDev { uint64_t n = 0, npe = 0; int32_t* offset = nullptr; uint64_t* off = nullptr; int32_t* edges = nullptr; };
 
@@ -395,17 +404,30 @@ int rewrite_paths(Ctx& c, const PathsDev& P, const int32_t* d_map, const int32_t
 }
 
 // ---- the driver: upload, two passes on device-resident data, download.  The editor is the only part that differs between the device
-// path and the host path (W2RAP_STEP4_EDIT_ON_HOST, VOTE_ONLY, and what w2rap_step4_run starts over with after EDIT4_FALLBACK)
+// path and the host path (W2RAP_STEP4_EDIT_ON_HOST, VOTE_ONLY, and what a call goes on with after EDIT4_FALLBACK)
+// the host editor's graph and involution from host arrays: the host half of both entries (upload() for w2rap_step4_run, host_graph_of()
+// for w2rap_step2_run_step4_after_step3).  Edges already unpacked into ed.g.edges (upload() needs them for the involution) are taken as they are
+void host_graph(HostEditor4& ed, int K, uint64_t E, uint64_t NV, const uint8_t* packed, const uint64_t* boff, const uint32_t* elen, const uint64_t* from_off,
+                const int32_t* from_v, const int32_t* from_e, const uint64_t* to_off, const int32_t* to_v, const int32_t* to_e, const int32_t* inv) {
+    HostGraph& hg = ed.g;
+    hg.K = K;
+    if (hg.edges.size() != E) unpack_edges(E, packed, boff, elen, hg.edges);
+    hg.frm.assign(NV, {}); hg.frm_e.assign(NV, {}); hg.to.assign(NV, {}); hg.to_e.assign(NV, {});
+    for (uint64_t v = 0; v < NV; ++v) {
+        for (uint64_t i = from_off[v]; i < from_off[v + 1]; ++i) { hg.frm[v].push_back(from_v[i]); hg.frm_e[v].push_back(from_e[i]); }
+        for (uint64_t i = to_off[v]; i < to_off[v + 1]; ++i) { hg.to[v].push_back(to_v[i]); hg.to_e[v].push_back(to_e[i]); }
+    }
+    ed.inv.assign(inv, inv + E);
+}
+
 // the one reader of `in`: its graph (with both ends of every edge and the involution, computed here if the caller gave none), reads and
 // paths on the device; host != null: the same graph as the host editor keeps it
 int upload(Ctx& c, const w2rap_step4_in& in, Graph4& g, ReadsDev& R, PathsDev& P, HostEditor4* host) {
     const uint64_t E = in.n_edge_objs, NV = in.n_vertices;
     HostGraph tmp; HostGraph& hg = host ? host->g : tmp;        // the edges a byte per base: for the host editor, and for the involution
     hg.K = in.K;
-    if (host || !in.inv) unpack_edges(E, in.edge_packed, in.edge_byte_off, in.edge_len, hg.edges);
     std::vector<int> inv;
-    if (!in.inv) W2_TRY(host_involution(hg, inv, c.err));
-    else if (host) inv.assign(in.inv, in.inv + E);
+    if (!in.inv) { unpack_edges(E, in.edge_packed, in.edge_byte_off, in.edge_len, hg.edges); W2_TRY(host_involution(hg, inv, c.err)); }
     std::vector<int32_t> vleft(E, -1), vright(E, -1), to_v(E, -1);
     for (uint64_t v = 0; v < NV; ++v) {
         for (uint64_t i = in.from_off[v]; i < in.from_off[v + 1]; ++i) vleft[in.from_e[i]] = (int32_t)v;
@@ -415,15 +437,10 @@ int upload(Ctx& c, const w2rap_step4_in& in, Graph4& g, ReadsDev& R, PathsDev& P
     g = Graph4{}; g.K = (unsigned)in.K; g.E = E; g.NV = NV; g.ebytes_cap = E ? in.edge_byte_off[E] : 0;
     W2_TRY(upload_graph4(c, g, in.edge_packed, in.edge_byte_off, in.edge_len, in.from_off, in.from_v, in.from_e, in.to_off, to_v.data(), in.to_e,
                          vleft.data(), vright.data(), in.inv ? in.inv : inv.data()));
-    if (host) {
-        hg.frm.resize(NV); hg.frm_e.resize(NV); hg.to.resize(NV); hg.to_e.resize(NV);
-        for (uint64_t v = 0; v < NV; ++v) {
-            for (uint64_t i = in.from_off[v]; i < in.from_off[v + 1]; ++i) { hg.frm[v].push_back(in.from_v[i]); hg.frm_e[v].push_back(in.from_e[i]); }
-            for (uint64_t i = in.to_off[v]; i < in.to_off[v + 1]; ++i) { hg.to[v].push_back(to_v[i]); hg.to_e[v].push_back(in.to_e[i]); }
-        }
-        host->inv.swap(inv);
-    }
-    // ---- the reads and their paths
+    if (host) host_graph(*host, in.K, E, NV, in.edge_packed, in.edge_byte_off, in.edge_len, in.from_off, in.from_v, in.from_e, in.to_off, to_v.data(), in.to_e,
+                         in.inv ? in.inv : inv.data());
+    // ---- the reads and their paths.  (The 16 bytes of slack behind the bases and the qualities are a margin, not a need: k4_score reads both
+    // a byte at a time and only at positions inside the read, so the chained entry may hand it the context's read blocks whatever lies behind them)
     const uint64_t n = in.n_paths;
     uint8_t* b = nullptr; uint64_t* bo = nullptr; uint32_t* ln = nullptr; uint8_t* q = nullptr; uint64_t* qo = nullptr;
     W2_TRY(up_pooled(c, &b, in.read_packed, n ? in.read_byte_off[n] : 0, 16));
@@ -437,6 +454,29 @@ int upload(Ctx& c, const w2rap_step4_in& in, Graph4& g, ReadsDev& R, PathsDev& P
     W2_TRY(up_pooled(c, &P.off, in.path_off, in.path_off ? n + 1 : 0));
     W2_TRY(up_pooled(c, &P.edges, in.path_edges, P.npe));
     W2_HIP(hipStreamSynchronize(c.stream));                     // (the host vectors above have been read)
+    return 0;
+}
+
+// the host editor's graph from ONE download of a graph that lies on the device (the chained entry: EDIT_ON_HOST, VOTE_ONLY, and where it
+// goes on after EDIT4_FALLBACK)
+int host_graph_of(Ctx& c, const Graph4& g, HostEditor4& ed) {
+    const uint64_t E = g.E, NV = g.NV;
+    std::vector<uint64_t> boff(E + 1, 0), from_off(NV + 1, 0), to_off(NV + 1, 0);
+    std::vector<uint32_t> elen(E);
+    std::vector<int32_t> from_v(E), from_e(E), to_v(E), to_e(E), inv(E);
+    auto down = [&](void* hst, const void* dev, uint64_t bytes) { return bytes ? hipMemcpyAsync(hst, dev, bytes, hipMemcpyDeviceToHost, c.stream) : hipSuccess; };
+    W2_HIP(down(boff.data(), g.ebyte, (E + 1) * 8)); W2_HIP(down(elen.data(), g.elen, E * 4));
+    W2_HIP(down(from_off.data(), g.from_off, (NV + 1) * 8)); W2_HIP(down(from_v.data(), g.from_v, E * 4)); W2_HIP(down(from_e.data(), g.from_e, E * 4));
+    W2_HIP(down(to_off.data(), g.to_off, (NV + 1) * 8)); W2_HIP(down(to_v.data(), g.to_v, E * 4)); W2_HIP(down(to_e.data(), g.to_e, E * 4));
+    W2_HIP(down(inv.data(), g.inv, E * 4));
+    W2_HIP(hipStreamSynchronize(c.stream));
+    if (boff[E] > g.ebytes_cap) { c.err = "the edge bytes on the device exceed their block"; return W2RAP_E_GRAPH; }
+    std::vector<uint8_t> packed(boff[E]);
+    W2_HIP(down(packed.data(), g.ebits, boff[E]));
+    W2_HIP(hipStreamSynchronize(c.stream));
+    ed.g = HostGraph{};
+    host_graph(ed, (int)g.K, E, NV, packed.data(), boff.data(), elen.data(), from_off.data(), from_v.data(), from_e.data(), to_off.data(), to_v.data(), to_e.data(),
+               inv.data());
     return 0;
 }
 
@@ -456,47 +496,63 @@ void retire(Ctx& c, const std::vector<void*>& before, const std::vector<void*>& 
 }
 
 // Clean200x's passes on device-resident data: g and pd are replaced by the clean graph and the paths on it, still on the device.
-// Of `out` only the counters are touched (n_branch_vertices, n_runs_merged, and what vote_pass counts)
+// Of `out` only the counters are touched (n_branch_vertices, n_runs_merged, and what vote_pass counts).
+// at != null (the chained entry, whose input is gone once pass 1 has retired it): the passes start at *at, and when the editor answers
+// EDIT4_FALLBACK, *at is the pass it did so in, with g, pd, the counters and the pool as they were when that pass began -- the caller
+// goes on from there with the host editor.  at == null: all passes, EDIT4_FALLBACK leaves everything to the caller (who starts over)
 int passes(Ctx& c, Graph4& g, const ReadsDev& R, PathsDev& pd, const w2rap_step4_params& P, Editor4& ed, std::vector<int32_t> deleted[2], Ms ms[2],
-           w2rap_step4_out& out) {
+           w2rap_step4_out& out, int* at = nullptr) {
     const unsigned Lmax = (MAX_RL + g.K - 1 + 3) & ~3u;
-    for (int pass = 0; pass < ((P.flags & W2RAP_STEP4_VOTE_ONLY) ? 1 : 2); ++pass) {
+    for (int pass = at ? *at : 0; pass < ((P.flags & W2RAP_STEP4_VOTE_ONLY) ? 1 : 2); ++pass) {
         const std::vector<void*> before = c.owned;
-        int32_t *d_bvert = nullptr, *d_outdeg = nullptr; Task* d_tasks = nullptr;
-        uint64_t B = 0, T = 0;
-        W2_TRY(ed.tasks(c, g, &d_bvert, &d_outdeg, &d_tasks, &B, &T));
-        if (B >= (1ull << 27)) { c.err = "more than 2^27 branch vertices"; return W2RAP_E_LIMIT; }
-        out.n_branch_vertices += B;
-        uint8_t* d_dead = nullptr;
-        W2_ALLOC(d_dead, uint8_t, g.E + 1);
-        W2_HIP(hipMemsetAsync(d_dead, 0, g.E + 1, c.stream));
-        if (B) {
-            const GraphDev G{g.K, g.E, g.NV, g.elen, g.ebyte, g.ebits, g.from_off, g.from_e, g.to_off, g.to_e, g.vright, g.inv};
-            W2_TRY(vote_pass(c, G, B, T, d_bvert, d_outdeg, d_tasks, R, pd, Lmax, d_dead, ms[pass], out));
+        const uint64_t counted[3] = {out.n_branch_vertices, out.n_skipped_too_many_exts, out.n_placements};
+        auto one = [&]() -> int {
+            int32_t *d_bvert = nullptr, *d_outdeg = nullptr; Task* d_tasks = nullptr;
+            uint64_t B = 0, T = 0;
+            W2_TRY(ed.tasks(c, g, &d_bvert, &d_outdeg, &d_tasks, &B, &T));
+            if (B >= (1ull << 27)) { c.err = "more than 2^27 branch vertices"; return W2RAP_E_LIMIT; }
+            out.n_branch_vertices += B;
+            uint8_t* d_dead = nullptr;
+            W2_ALLOC(d_dead, uint8_t, g.E + 1);
+            W2_HIP(hipMemsetAsync(d_dead, 0, g.E + 1, c.stream));
+            if (B) {
+                const GraphDev G{g.K, g.E, g.NV, g.elen, g.ebyte, g.ebits, g.from_off, g.from_e, g.to_off, g.to_e, g.vright, g.inv};
+                W2_TRY(vote_pass(c, G, B, T, d_bvert, d_outdeg, d_tasks, R, pd, Lmax, d_dead, ms[pass], out));
+            }
+            // ---- the graph edit
+            Graph4 next;
+            int32_t *d_map = nullptr, *d_add = nullptr;
+            uint64_t merged = 0;
+            {
+                const auto t0 = std::chrono::steady_clock::now();
+                W2_TRY(ed.pass(c, g, d_dead, P.min_size, &next, &d_map, &d_add, &deleted[pass], &merged));
+                ms[pass].host = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+            }
+            out.n_runs_merged[pass] = merged;
+            // ---- the read paths (no map: nothing was edited)
+            std::vector<void*> gone = blocks(g), keep = blocks(next);
+            if (d_map && pd.n) {
+                PathsDev np;
+                W2_TRY(rewrite_paths(c, pd, d_map, d_add, ms[pass], np));
+                gone.insert(gone.end(), {(void*)pd.offset, (void*)pd.off, (void*)pd.edges});
+                keep.insert(keep.end(), {(void*)np.offset, (void*)np.off, (void*)np.edges});
+                pd = np;
+            }
+            W2_HIP(hipStreamSynchronize(c.stream));
+            g = next;
+            // the new graph and paths replace the old ones; everything else of this pass goes back to the pool
+            retire(c, before, gone, keep);
+            return 0;
+        };
+        const int rc = one();
+        if (rc == EDIT4_FALLBACK && at) {                        // (the editors answer it before they have changed g or pd)
+            W2_HIP(hipStreamSynchronize(c.stream));
+            out.n_branch_vertices = counted[0]; out.n_skipped_too_many_exts = counted[1]; out.n_placements = counted[2];
+            deleted[pass].clear(); ms[pass] = Ms{};
+            retire(c, before, {}, {});
+            *at = pass;
         }
-        // ---- the graph edit
-        Graph4 next;
-        int32_t *d_map = nullptr, *d_add = nullptr;
-        uint64_t merged = 0;
-        {
-            const auto t0 = std::chrono::steady_clock::now();
-            W2_TRY(ed.pass(c, g, d_dead, P.min_size, &next, &d_map, &d_add, &deleted[pass], &merged));
-            ms[pass].host = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-        }
-        out.n_runs_merged[pass] = merged;
-        // ---- the read paths (no map: nothing was edited)
-        std::vector<void*> gone = blocks(g), keep = blocks(next);
-        if (d_map && pd.n) {
-            PathsDev np;
-            W2_TRY(rewrite_paths(c, pd, d_map, d_add, ms[pass], np));
-            gone.insert(gone.end(), {(void*)pd.offset, (void*)pd.off, (void*)pd.edges});
-            keep.insert(keep.end(), {(void*)np.offset, (void*)np.off, (void*)np.edges});
-            pd = np;
-        }
-        W2_HIP(hipStreamSynchronize(c.stream));
-        g = next;
-        // the new graph and paths replace the old ones; everything else of this pass goes back to the pool
-        retire(c, before, gone, keep);
+        if (rc) return rc;
     }
     return 0;
 }
@@ -624,12 +680,72 @@ int w2rap_step4_run(const w2rap_step4_in* in, const w2rap_step4_params* P, w2rap
         rc = step4(c, *in, *P, false, *out);
     }
     std::string msg = c.err;
-    (void)hipStreamSynchronize(c.stream);
-    c.presolve();
-    g_profile4.clear();
-    for (auto& s : c.prof_sums) { char line[256]; std::snprintf(line, sizeof line, "%s %.4f %llu\n", s.name.c_str(), s.ms, (unsigned long long)s.launches); g_profile4 += line; }
-    { char line[64]; std::snprintf(line, sizeof line, "edit_path_device %d %d\n", on_device ? 1 : 0, on_device ? 2 : 0); g_profile4 += line; }
+    save_profile4(c, on_device);
     if (rc) w2rap_step2_destroy(h); else w2rap_step2_release(h);     // (a failed context is not cached)
+    if (rc) { w2rap_step4_free(out); return fail(rc, msg); }
+    return 0;
+}
+
+// Step 4 straight behind Step 3 in one process (the reference's default flow, w2rap-contigger.cc:395-399 on the objects Steps 1-3 left in
+// memory): the large-K graph, its involution and the read paths are the context's kept large-K result (W2RAP_STEP3_KEEP_DEVICE), the reads
+// and their qualities are the context's own.  Nothing goes up; the clean graph and paths come down once.  The context's Step-2 state is
+// not touched, whatever happens
+int w2rap_step2_run_step4_after_step3(w2rap_step2_ctx* h, const w2rap_step4_params* P, w2rap_step4_out* out, char* err, size_t errlen) {
+    auto fail = [&](int code, const std::string& m) { if (err && errlen) std::snprintf(err, errlen, "%s", m.c_str()); return code; };
+    if (!h || !P || !out) return fail(W2RAP_E_ARG, "null argument");
+    std::memset(out, 0, sizeof(*out));
+    if (P->flags & ~(W2RAP_STEP4_VOTE_ONLY | W2RAP_STEP4_EDIT_ON_HOST)) return fail(W2RAP_E_ARG, "unknown flag");
+    Ctx& c = h->c;
+    if (P->device != c.device) return fail(W2RAP_E_ARG, "w2rap_step2_run_step4_after_step3: params->device is not the context's device");
+    if (!c.kept.valid)
+        return fail(W2RAP_E_STATE, "w2rap_step2_run_step4_after_step3: the context holds no large-K result of Step 3 (w2rap_step3_run_after_step2 with "
+                                   "W2RAP_STEP3_KEEP_DEVICE comes first; a full Step 4, or anything that changes Step 2's state, gives the result up)");
+    if (hipSetDevice(c.device) != hipSuccess) return fail(W2RAP_E_HIP, "hipSetDevice failed");
+    const Ctx::Kept3 k = c.kept;
+    auto give_up = [&](int code, const std::string& m) { c.drop_kept(); return fail(code, m); };
+    if (c.quals_absent)
+        return give_up(W2RAP_E_STATE, "w2rap_step2_run_step4_after_step3: the reads' raw qualities were never uploaded (Step 2's set_reads ran for a graph-only call): the vote needs them");
+    if (k.n != c.n || (c.n && (!c.d_bases || !c.d_boff || !c.d_len || !c.d_quals || !c.d_qoff)))
+        return give_up(W2RAP_E_STATE, "w2rap_step2_run_step4_after_step3: the context's reads (Step 2's set_reads) are not the ones the kept large-K paths belong to");
+    if (const int rq = quals_wait(c)) { const std::string m = c.err; return give_up(rq, m); }     // a late quality upload still on its way
+    c.prof_sums.clear();
+    // the call takes the kept blocks over: from here on they are blocks of this call like any other, behind `mark` in c.owned
+    const size_t mark = c.owned.size();
+    for (void* p : k.blocks()) c.owned.push_back(p);
+    c.kept = Ctx::Kept3{};
+    Graph4 g; g.K = k.K2; g.E = k.E; g.NV = k.NV; g.ebytes_cap = k.edge_bytes;
+    g.ebits = k.ebits; g.ebyte = k.ebyte; g.elen = k.elen; g.from_off = k.from_off; g.from_v = k.from_v; g.from_e = k.from_e;
+    g.to_off = k.to_off; g.to_v = k.to_v; g.to_e = k.to_e; g.vleft = k.left; g.vright = k.right; g.inv = k.inv2;
+    // (no slack is asked of the read blocks: see upload())
+    const ReadsDev R{c.d_bases, c.d_boff, c.d_len, c.d_quals, c.d_qoff};
+    PathsDev pd; pd.n = k.n; pd.npe = k.path_ints; pd.offset = k.p_offset; pd.off = k.p_off; pd.edges = k.p_edges;
+    const bool vote_only = (P->flags & W2RAP_STEP4_VOTE_ONLY) != 0;
+    bool on_device = !(P->flags & (W2RAP_STEP4_EDIT_ON_HOST | W2RAP_STEP4_VOTE_ONLY));
+    auto body = [&]() -> int {
+        std::vector<int32_t> deleted[2];
+        Ms ms[2];
+        int at = 0, rc = EDIT4_FALLBACK;
+        if (on_device) { DeviceEditor4 ed; rc = passes(c, g, R, pd, *P, ed, deleted, ms, *out, &at); }
+        if (rc == EDIT4_FALLBACK) {       // the host editor goes on where the device editor stopped (pass 1's input is gone once pass 1 is through)
+            on_device = false;
+            HostEditor4 ed;
+            ed.edit = !vote_only;
+            W2_TRY(host_graph_of(c, g, ed));
+            rc = passes(c, g, R, pd, *P, ed, deleted, ms, *out, &at);
+        }
+        if (rc) return rc;
+        return download(c, g, pd, deleted, ms, *out);
+    };
+    const int rc = body();
+    const std::string msg = c.err;
+    save_profile4(c, on_device);
+    // VOTE_ONLY has edited nothing: the kept result stays.  Otherwise it is consumed (or, after a failure, given up); either way every
+    // block this call allocated goes back to the pool
+    const std::vector<void*> stay = (!rc && vote_only) ? k.blocks() : std::vector<void*>{};
+    for (size_t i = mark; i < c.owned.size(); ++i)
+        if (std::find(stay.begin(), stay.end(), c.owned[i]) == stay.end()) c.park(c.owned[i]);
+    c.owned.resize(mark);
+    if (!rc && vote_only) c.kept = k;
     if (rc) { w2rap_step4_free(out); return fail(rc, msg); }
     return 0;
 }

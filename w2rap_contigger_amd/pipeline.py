@@ -2,8 +2,8 @@
 
 Mirrors ``w2rap-contigger -r r1.fastq,r2.fastq -o OUT -p PREFIX [-K 200] [--min_freq 4] [--min_qual 7] --from_step A --to_step B`` for
 1 <= A <= B <= 4 (src/modules/w2rap-contigger.cc:300-409): consecutive steps run in one process hand their data over in HBM
-(w2rap_step1_run_into_step2, the staged Step-2 entry points, w2rap_step3_run_after_step2), a run that starts at step 2 or 3 loads the
-files the previous step wrote, and every step writes what the reference writes:
+(w2rap_step1_run_into_step2, the staged Step-2 entry points, w2rap_step3_run_after_step2, w2rap_step2_run_step4_after_step3), a run that
+starts at step 2, 3 or 4 loads the files the previous step wrote, and every step writes what the reference writes:
     step 1: OUT/frag_reads_orig.fastb, .qualp  -- ALWAYS (the reference writes them when `dump_all || to_step < 6`,
             w2rap-contigger.cc:312-318, and its steps 2..6 load them again, :322-328: a hand-over to `--from_step 4` needs them)
     step 2: OUT/PREFIX.small_K.hbv, .paths (last step or dump_all, :343-347), OUT/small_K.freqs (always, BuildReadQGraph.cc:1108)
@@ -72,29 +72,35 @@ def run(read_files, out_dir, prefix, large_k=200, min_freq=4, min_qual=7, from_s
             if from_step == 3:
                 r3 = step3.run_step3_files(out_dir, prefix, large_k, device, extend_paths=extend_paths)
             else:
-                r3 = step3.repath_after_step2(ctx, large_k, extend_paths=extend_paths)
+                # a run that goes on to step 4 keeps the large-K result in HBM for it, and brings it down only to write it
+                chained = to_step == 4
+                r3 = step3.repath_after_step2(ctx, large_k, extend_paths=extend_paths, keep_on_device=chained, fetch=not chained or dump_all)
                 if to_step == 3 or dump_all:                        # w2rap-contigger.cc:373
                     F.write_hbv(pre + ".large_K.hbv", r3.hbv)
                     F.write_paths(pre + ".large_K.paths", r3.path_offset, r3.path_off, r3.path_edges)
                 with open(pre + ".first.frags.dist", "w") as f:
                     f.write(step3.frags_text(r3.frag_count))
             out["step3"] = r3
-            log(f"Repathing to second graph DONE: {r3.n_unique_places} unique places, {r3.hbv.n_edges} large-K edge objects")
-    if to_step == 4:
-        log("--== Step 4: Cleaning graph ==--")
-        if from_step == 4:
-            r4 = step4.run_step4_files(out_dir, prefix, min_size, device)
-        else:                                                       # the large-K graph and paths come back to the host between steps 3 and 4
-            r3 = out["step3"]
-            pk, bo, ln = F.read_fastb(os.path.join(out_dir, "frag_reads_orig.fastb"))
-            pq, po = F.read_qualp(os.path.join(out_dir, "frag_reads_orig.qualp"))
-            quals, qoff = F.qualp_to_raw(pq, po)
-            r4 = step4.clean200x(r3.hbv, (r3.path_offset, r3.path_off, r3.path_edges), pk, bo, ln, quals, qoff, min_size=min_size, device=device, inv=r3.inv2)
-            F.write_hbv(pre + ".large_K.clean.hbv", r4.hbv)
-            F.write_paths(pre + ".large_K.clean.paths", r4.path_offset, r4.path_off, r4.path_edges)
-        out["step4"] = r4
-        log(f"Cleaning graph DONE: {sum(r4.n_deleted)} edges deleted, {sum(r4.n_runs_merged)} runs merged, {r4.hbv.n_edges} edge objects "
-            f"(host clock in the graph edit: {sum(r4.ms_graph_edit_host):.1f} ms)")
+            n_large = r3.n_edge_objs if from_step <= 2 else r3.hbv.n_edges      # (the counter: a chained run has not fetched the graph)
+            log(f"Repathing to second graph DONE: {r3.n_unique_places} unique places, {n_large} large-K edge objects")
+        if to_step == 4:
+            log("--== Step 4: Cleaning graph ==--")
+            if from_step == 4:
+                r4 = step4.run_step4_files(out_dir, prefix, min_size, device)
+            elif from_step == 3:                                    # Step 3 ran from files and has no reads on the device: host arrays
+                r3 = out["step3"]
+                pk, bo, ln = F.read_fastb(os.path.join(out_dir, "frag_reads_orig.fastb"))
+                pq, po = F.read_qualp(os.path.join(out_dir, "frag_reads_orig.qualp"))
+                quals, qoff = F.qualp_to_raw(pq, po)
+                r4 = step4.clean200x(r3.hbv, (r3.path_offset, r3.path_off, r3.path_edges), pk, bo, ln, quals, qoff, min_size=min_size, device=device, inv=r3.inv2)
+            else:                                                   # reads, large-K graph and paths are where Steps 1-3 left them in HBM
+                r4 = step4.clean200x_after_step3(ctx, min_size=min_size)
+            if from_step != 4:
+                F.write_hbv(pre + ".large_K.clean.hbv", r4.hbv)
+                F.write_paths(pre + ".large_K.clean.paths", r4.path_offset, r4.path_off, r4.path_edges)
+            out["step4"] = r4
+            log(f"Cleaning graph DONE: {sum(r4.n_deleted)} edges deleted, {sum(r4.n_runs_merged)} runs merged, {r4.hbv.n_edges} edge objects "
+                f"(host clock in the graph edit: {sum(r4.ms_graph_edit_host):.1f} ms)")
     return out
 
 

@@ -223,6 +223,7 @@ class Step2Context:
         self.h = self.L.w2rap_step2_create(device, err, 512)
         if not self.h:
             raise Step2Error(2, err.value.decode(errors="replace"))
+        self.device = device
         self._keep = None
         self.n_reads = 0
 

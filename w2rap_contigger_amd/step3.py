@@ -32,6 +32,7 @@ class Step3Params(C.Structure):
 
 NO_FETCH = 1
 PLACES_ONLY = 2
+KEEP_DEVICE = 8         # repath_after_step2 only: the large-K result stays in the context's HBM for step4.clean200x_after_step3
 UNIQUE_KMERS = 4        # the graph is a unipath graph whose K-mers occur once (Step 2's output): include/w2rap_step3.h
 
 
@@ -90,6 +91,8 @@ class Step3Result:
     ms_graph: float
     ms_paths: float
     place_paths: tuple = None     # PLACES_ONLY: (off u64[U+1], edges i32[]) -- a read path per unique place of these reads
+    n_edge_objs: int = 0          # the large-K graph's sizes as counters (what fetch=False still brings down; hbv is empty then)
+    n_vertices: int = 0
 
 
 def _params(K2, device, extend_paths, hint_p, flags, extra_paths, keep):
@@ -100,11 +103,13 @@ def _params(K2, device, extend_paths, hint_p, flags, extra_paths, keep):
     return Step3Params(K2, device, 1 if extend_paths else 0, hint_p, flags, len(xo) - 1, _ptr(xo), _ptr(xe) if len(xe) else None)
 
 
-def repath_in_memory(hbv: F.HBV, paths, K2=200, device=0, edge_order_hint=None, extend_paths=False, extra_paths=None, places_only=False, unique_kmers=False) -> Step3Result:
+def repath_in_memory(hbv: F.HBV, paths, K2=200, device=0, edge_order_hint=None, extend_paths=False, extra_paths=None, places_only=False, unique_kmers=False,
+                     keep_on_device=False) -> Step3Result:
     """Involution + FragDist + RepathInMemory through the one-shot C entry point (w2rap_step3_run).
     unique_kmers: the caller vouches that `hbv` is the unipath graph of Step 2 (every K-mer once): W2RAP_STEP3_UNIQUE_KMERS.
     paths = (offset i32[n], path_off u64[n+1], edges i32[]); edge_order_hint = (packed, byte_off, len) of the large-K canonical
-    edges in the order to replay, or None for the lexicographic order."""
+    edges in the order to replay, or None for the lexicographic order.  keep_on_device has no context to keep anything in: the library
+    answers W2RAP_E_ARG (repath_after_step2 is the call that takes it)."""
     L = lib()
     keep = [np.ascontiguousarray(hbv.edge_packed, np.uint8), np.ascontiguousarray(hbv.edge_byte_off, np.uint64), np.ascontiguousarray(hbv.edge_len, np.uint32),
             np.ascontiguousarray(paths[0], np.int32), np.ascontiguousarray(paths[1], np.uint64), np.ascontiguousarray(paths[2], np.int32)]
@@ -118,7 +123,8 @@ def repath_in_memory(hbv: F.HBV, paths, K2=200, device=0, edge_order_hint=None, 
         eh, k2 = make_hint(*edge_order_hint)
         keep.append(k2)
         hint_p = C.pointer(eh)
-    p = _params(K2, device, extend_paths, hint_p, (PLACES_ONLY if places_only else 0) | (UNIQUE_KMERS if unique_kmers else 0), extra_paths, keep)
+    p = _params(K2, device, extend_paths, hint_p, (PLACES_ONLY if places_only else 0) | (UNIQUE_KMERS if unique_kmers else 0) | (KEEP_DEVICE if keep_on_device else 0),
+                extra_paths, keep)
     o = Step3Out()
     err = C.create_string_buffer(1024)
     rc = L.w2rap_step3_run(C.byref(i), C.byref(p), C.byref(o), err, 1024)
@@ -127,9 +133,11 @@ def repath_in_memory(hbv: F.HBV, paths, K2=200, device=0, edge_order_hint=None, 
     return _result3(L, o, len(keep[2]))
 
 
-def repath_after_step2(ctx, K2=200, edge_order_hint=None, fetch=True, extra_paths=None, places_only=False, extend_paths=False) -> Step3Result:
+def repath_after_step2(ctx, K2=200, edge_order_hint=None, fetch=True, extra_paths=None, places_only=False, extend_paths=False, keep_on_device=False) -> Step3Result:
     """Step 3 straight behind Step 2 on the same GPU context (step2.Step2Context after path_reads): graph and paths stay in HBM
-    (w2rap_step3_run_after_step2) -- the reference's default flow of steps 2 and 3 in one process."""
+    (w2rap_step3_run_after_step2) -- the reference's default flow of steps 2 and 3 in one process.
+    keep_on_device: the large-K graph and paths also STAY in the context's HBM, for step4.clean200x_after_step3 (W2RAP_STEP3_KEEP_DEVICE;
+    with fetch=False only the counters come down).  Not with places_only or extra_paths (Step2Error, W2RAP_E_ARG)."""
     L = lib()
     keep = []
     hint_p = None
@@ -137,7 +145,8 @@ def repath_after_step2(ctx, K2=200, edge_order_hint=None, fetch=True, extra_path
         eh, k2 = make_hint(*edge_order_hint)
         keep.append(k2)
         hint_p = C.pointer(eh)
-    p = _params(K2, 0, extend_paths, hint_p, (0 if fetch else NO_FETCH) | (PLACES_ONLY if places_only else 0), extra_paths, keep)
+    p = _params(K2, 0, extend_paths, hint_p, (0 if fetch else NO_FETCH) | (PLACES_ONLY if places_only else 0) | (KEEP_DEVICE if keep_on_device else 0),
+                extra_paths, keep)
     o = Step3Out()
     err = C.create_string_buffer(1024)
     rc = L.w2rap_step3_run_after_step2(ctx.h, C.byref(p), C.byref(o), err, 1024)
@@ -165,7 +174,7 @@ def _result3(L, o, n_in_objs) -> Step3Result:
                            np.array(list(o.frag_count), dtype=np.uint64),
                            _np_from(o.path_offset, np.int32, NP), po, _np_from(o.path_edges, np.int32, int(po[-1])),
                            o.n_reads_pathed, o.n_reads_multipathed, o.n_places, o.n_unique_places, o.n_place_bases, o.n_kmer_instances,
-                           o.n_kmers_distinct, o.n_unipaths, o.ms_places, o.ms_dict, o.ms_graph, o.ms_paths, pp)
+                           o.n_kmers_distinct, o.n_unipaths, o.ms_places, o.ms_dict, o.ms_graph, o.ms_paths, pp, n_edge_objs=NO, n_vertices=NV)
     finally:
         L.w2rap_step3_free(C.byref(o))
 

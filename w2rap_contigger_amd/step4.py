@@ -9,8 +9,11 @@ frag_reads_orig.{fastb,qualp}, writes <prefix>.large_K.clean.{hbv,paths}.
 The vote over the reads, the rewrite of the read paths and the edit of the graph itself (delete, merge runs, renumber: the k4e_*
 kernels) run in HIP kernels: the graph goes up once and comes down once.  ``edit="host"`` (EDIT_ON_HOST) runs the library's host edit
 instead, the cross-check; a graph that misses a precondition of the device edit (adjacency lists not sorted by neighbour, a run whose
-mirror image is not a run) takes it silently, with the same result.  `Step4Result.edit_on_device` tells which one ran.  The HIP library
-is the only implementation (no CPU fallback)."""
+mirror image is not a run) takes it silently, with the same result.  `Step4Result.edit_on_device` tells which one ran.
+
+`clean200x_after_step3` is the same step straight behind Step 3 on one `step2.Step2Context` (w2rap_step2_run_step4_after_step3): the reads and
+their qualities are the context's, the large-K graph and paths are what `step3.repath_after_step2(ctx, keep_on_device=True)` left in
+HBM.  Nothing is uploaded.  The HIP library is the only implementation (no CPU fallback)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -59,6 +62,7 @@ def lib():
     L = _lib2()
     if not _ready:
         L.w2rap_step4_run.argtypes = [C.POINTER(Step4In), C.POINTER(Step4Params), C.POINTER(Step4Out), C.c_char_p, C.c_size_t]
+        L.w2rap_step2_run_step4_after_step3.argtypes = [C.c_void_p, C.POINTER(Step4Params), C.POINTER(Step4Out), C.c_char_p, C.c_size_t]
         L.w2rap_step4_free.argtypes = [C.POINTER(Step4Out)]
         L.w2rap_step4_free.restype = None
         L.w2rap_step4_profile.argtypes = [C.c_char_p, C.c_size_t]
@@ -120,6 +124,26 @@ def clean200x(hbv: F.HBV, paths, read_packed, read_byte_off, read_len, quals, qu
     rc = L.w2rap_step4_run(C.byref(i), C.byref(prm), C.byref(o), err, 1024)
     if rc:
         raise Step2Error(rc, err.value.decode(errors="replace"))
+    return _result4(L, o, vote_only)
+
+
+def clean200x_after_step3(ctx, min_size=0, vote_only=False, edit="device") -> Step4Result:
+    """Involution + Clean200x straight behind Step 3 on the same GPU context (w2rap_step2_run_step4_after_step3): `ctx` is a step2.Step2Context
+    whose last Step 3 was step3.repath_after_step2(ctx, ..., keep_on_device=True).  A full run consumes the kept large-K result (a second
+    call raises Step2Error, W2RAP_E_STATE); vote_only leaves it in place.  The context's Step-2 state is untouched."""
+    if edit not in ("device", "host"):
+        raise ValueError(f"edit must be 'device' or 'host', not {edit!r}")
+    L = lib()
+    prm = Step4Params(ctx.device, int(min_size), (VOTE_ONLY if vote_only else 0) | (EDIT_ON_HOST if edit == "host" else 0))
+    o = Step4Out()
+    err = C.create_string_buffer(1024)
+    rc = L.w2rap_step2_run_step4_after_step3(ctx.h, C.byref(prm), C.byref(o), err, 1024)
+    if rc:
+        raise Step2Error(rc, err.value.decode(errors="replace"))
+    return _result4(L, o, vote_only)
+
+
+def _result4(L, o, vote_only) -> Step4Result:
     try:
         NO, NV, NP = o.n_edge_objs, o.n_vertices, o.n_paths
         boff = _np_from(o.edge_byte_off, np.uint64, NO + 1)
