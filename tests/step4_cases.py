@@ -122,16 +122,19 @@ class Hand:
         return np.concatenate(out)
 
     def read(self, path, offset, length, qual=30, errors=(), rc=False):
-        """a read of `length` bases from offset `offset` of the walk `path`; rc: the read of the other strand, pathed on the mirror edges"""
+        """a read of `length` bases from offset `offset` of the walk `path`; rc: the read of the other strand, pathed on the mirror edges;
+        qual: one value for every base, or one value per base in the walk's direction (reversed with the bases when rc)"""
         c = self.cat(path)[offset:offset + length].copy()
+        q = np.full(len(c), qual, np.uint8) if np.ndim(qual) == 0 else np.array(qual, np.uint8)
+        assert len(q) == len(c)
         for p in errors:
             c[p] = (c[p] + 1) & 3
         if rc:
             total = len(self.cat(path))
             path = [e ^ 1 for e in reversed(path)]
             offset = total - offset - length
-            c = _rc(c)
-        self.paths.append(list(path)); self.offs.append(offset); self.codes.append(c); self.quals.append(np.full(len(c), qual, np.uint8))
+            c = _rc(c); q = q[::-1].copy()
+        self.paths.append(list(path)); self.offs.append(offset); self.codes.append(c); self.quals.append(q)
 
     def case(self):
         h = self.b.hbv()

@@ -20,6 +20,7 @@ MAX_EXTS = 10
 MAX_RL = 250
 MAX_DEL, MIN_WIN, MAX_LOSE, MIN_RATIO = 15, 100, 50, 5
 RUN_SIZES = []          # edges per merged run of the runs made so far (read by the tests that assert what the fixtures exercise)
+PLACEMENTS = None       # a list: vote() appends (vertex, walks, depth, placements) per voted branch vertex, in the order of the flat placement list
 
 
 class Graph:
@@ -233,6 +234,8 @@ def vote(g: Graph, inv, offs, paths, reads: Reads, cnt: Counters):
                             continue
                         rpi.append((rid, offs[rid] - sum(g.kmers(x) for x in p[:j + 1])))
         cnt.n_placements += len(pi) + len(rpi)
+        if PLACEMENTS is not None:
+            PLACEMENTS.append((v, N, depth, len(pi) + len(rpi)))
         for fw, lst in ((True, pi), (False, rpi)):
             for rid, start in lst:
                 b = reads.codes[roff[rid]:roff[rid + 1]]
