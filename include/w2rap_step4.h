@@ -54,6 +54,8 @@ typedef struct w2rap_step4_in {
     const uint64_t* to_off;          /* [n_vertices+1] */
     const int32_t*  to_e;            /* [n_edge_objs] to_edge_obj_ */
     const int32_t*  inv;             /* [n_edge_objs] hbvr.Involution (w2rap_step3_out.inv2), or NULL: computed here from the sequences */
+                                     /* (checked: an involution of edges of equal length.  If it does not mirror a merged run onto a run,
+                                      *  the call returns W2RAP_E_GRAPH where the reference's walk would leave the graph) */
     /* pathsr */
     uint64_t n_paths;
     const int32_t*  path_offset;     /* [n_paths] */

@@ -10,6 +10,7 @@ never run on.
 `vote=False` disables the weak-branch vote: what is left is min_size, Cleanup and the renumbering."""
 from __future__ import annotations
 
+from collections import namedtuple
 from dataclasses import dataclass, field
 
 import numpy as np
@@ -20,6 +21,10 @@ MAX_EXTS = 10
 MAX_RL = 250
 MAX_DEL, MIN_WIN, MAX_LOSE, MIN_RATIO = 15, 100, 50, 5
 RUN_SIZES = []          # edges per merged run of the runs made so far (read by the tests that assert what the fixtures exercise)
+RUNS = []               # per call of remove_unneeded_vertices2 (one a pass) the list of its pushed runs, in the order they were found
+# a pushed run: its ends, its kill vertices from eleft to eright, and those of its mirror image (inv[eright], inv[eleft]) where the same
+# pass found that as a run of its own (None: a circle whose mirror edge lies on the same circle, or an inv that mirrors no run onto it)
+Run = namedtuple("Run", "eleft eright kill mirror_kill")
 PLACEMENTS = None       # a list: vote() appends (vertex, walks, depth, placements) per voted branch vertex, in the order of the flat placement list
 
 
@@ -285,13 +290,16 @@ def remove_unneeded_vertices2(g: Graph, inv, offs, paths):          # GapToyTool
             kill[v] = True
             queue.append(v)
     bound = []
+    found, pushed = {}, []                             # (recording only: RUNS)
     while queue:
         v = queue.pop()
         if not kill[v]:
             continue
         vleft = v
+        seen_left, seen_right = [], []
         while True:
             kill[vleft] = False
+            seen_left.append(vleft)
             eleft = g.to_e[vleft][0]
             vleft = g.to[vleft][0]
             if not kill[vleft]:
@@ -299,13 +307,17 @@ def remove_unneeded_vertices2(g: Graph, inv, offs, paths):          # GapToyTool
         vright = v
         while True:
             kill[vright] = False
+            seen_right.append(vright)
             eright = g.frm_e[vright][0]
             vright = g.frm[vright][0]
             if not kill[vright]:
                 break
+        found[(eleft, eright)] = tuple(seen_left[::-1] + seen_right[1:])
         if eleft < inv[eright]:
             bound.append((eleft, eright))
             bound.append((inv[eright], inv[eleft]))
+            pushed.append((eleft, eright))
+    RUNS.append([Run(a, b, found[(a, b)], found.get((inv[b], inv[a]))) for a, b in pushed])
     E0 = len(g.edges)
     renum = list(range(E0))
     offsets = [0] * E0

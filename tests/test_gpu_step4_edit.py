@@ -1,6 +1,9 @@
 """Step 4's graph edit on the GPU (the k4e_* kernels): byte equality with the recorded runs of the unmodified reference, equality with the
 library's host edit in everything it returns, and the CPU model (tests/step4_model.py) as the judge on hand-made graphs, one rule of the
-reference's numbering each (tests/step4_edit_cases.py).  No comparison has a tolerance."""
+reference's numbering each (tests/step4_edit_cases.py); the same graphs under the numbering of a real graph (random vertex and edge ids,
+both tie orders), counts on the edges of a block and of a sort tile, members of one k-mer, a pass that deletes every edge, and an inv
+that mirrors no run onto a run.  test_step4_edit_model.py proves on the CPU what each of those inputs exercises.  No comparison has a
+tolerance."""
 import os
 
 import numpy as np
@@ -152,3 +155,106 @@ def test_a_call_after_a_fallback_finds_a_clean_context():
     second = step4.clean200x(h, paths, pk, bo, ln, quals, min_size=ms, edit="device")
     assert second.edit_on_device is True and _k4e()
     _same(second, M.clean200x(h, None, paths, M.reads_of(pk, bo, ln, quals), ms))
+
+
+# ---- real numbering, sizes, the driver's other paths (step4_edit_cases.py; each is proven on the model in test_step4_edit_model.py)
+_MODELS = {}
+
+
+def _model(key, inputs):
+    if key not in _MODELS:
+        h, paths, (pk, bo, ln), quals, ms = inputs
+        _MODELS[key] = M.clean200x(h, None, paths, M.reads_of(pk, bo, ln, quals), ms)
+        M.RUNS.clear(); M.RUN_SIZES.clear()                   # (the model's records for the CPU proofs: not read here)
+    return _MODELS[key]
+
+
+def _device_host_model(key, inputs):
+    h, paths, (pk, bo, ln), quals, ms = inputs
+    m = _model(key, inputs)
+    dev = step4.clean200x(h, paths, pk, bo, ln, quals, min_size=ms, edit="device")
+    assert dev.edit_on_device is True and _k4e()
+    _same(dev, m)
+    host = step4.clean200x(h, paths, pk, bo, ln, quals, min_size=ms, edit="host")
+    assert host.edit_on_device is False
+    _same(host, m)
+    _same_results(dev, host)
+
+
+@pytest.mark.parametrize("name", EC.size_names())
+def test_counts_on_block_and_tile_edges_and_members_of_one_kmer(name):
+    _device_host_model(("size", name), EC.size_case(name).inputs)
+
+
+@pytest.mark.parametrize("name", sorted(EC.variant_names()))
+def test_renumbered_graphs_on_both_paths(name):
+    _device_host_model(("variant", name), EC.renumbered_variant(name))
+
+
+def test_pass_one_deletes_every_edge():
+    """pass 2 has no edge to run a kernel on: the device edit declines there, the one-shot call starts over on the host"""
+    inputs = EC.all_deleted_case()
+    h, paths, (pk, bo, ln), quals, ms = inputs
+    m = _model("all_deleted", inputs)
+    assert m.deleted == [[0, 1, 2, 3, 4, 5], []] and m.hbv.n_edges == 0
+    dev = step4.clean200x(h, paths, pk, bo, ln, quals, min_size=ms, edit="device")
+    assert dev.edit_on_device is False and not _k4e()
+    _same(dev, m)
+    host = step4.clean200x(h, paths, pk, bo, ln, quals, min_size=ms, edit="host")
+    _same(host, m)
+    _same_results(dev, host)
+
+
+def test_pass_one_deletes_every_edge_behind_step3():
+    """the chained call cannot start over (pass 1 has consumed Step 3's result): the host editor goes on at pass 2 from the empty graph on
+    the device.  300 error-free reads of one random 1 kb genome: the large-K graph is isolated edges, all within min_size"""
+    rng = np.random.default_rng(61)
+    genome = rng.integers(0, 4, 1000).astype(np.uint8)
+    codes = []
+    for _ in range(300):
+        at = int(rng.integers(0, 1000 - 150 + 1))
+        r = genome[at:at + 150]
+        codes.append((3 - r[::-1]).astype(np.uint8) if rng.random() < 0.5 else r)
+    off = np.arange(301, dtype=np.uint64) * 150
+    pk, bo, ln = F.pack_bases(np.concatenate(codes), off)
+    quals = np.full(300 * 150, 30, np.uint8)
+    paths_of = lambda x: (x.path_offset, x.path_off, x.path_edges)
+    with step2.Step2Context(0) as ctx:
+        ctx.set_reads_host(pk, bo, ln, quals=quals, qual_off=off)
+        ctx.count_kmers(7, 2); ctx.build_graph(None); ctx.path_reads()
+        idle = ctx.device_bytes()
+        r3 = step3.repath_after_step2(ctx, 200, keep_on_device=True)
+        assert r3.hbv.n_edges > 0 and ctx.device_bytes() > idle
+        ms = int(r3.hbv.edge_len.max())                              # above every edge's k-mers
+        res = step4.clean200x_after_step3(ctx, min_size=ms)
+        assert res.edit_on_device is False
+        assert ctx.device_bytes() == idle
+        # the context is as good as before: the next round edits on the device and leaves as little behind
+        ctx.count_kmers(7, 2); ctx.build_graph(None); ctx.path_reads()
+        assert ctx.device_bytes() == idle
+        step3.repath_after_step2(ctx, 200, keep_on_device=True, fetch=False)
+        nxt = step4.clean200x_after_step3(ctx)
+        assert nxt.edit_on_device is True and ctx.device_bytes() == idle
+    m = M.clean200x(r3.hbv, r3.inv2, paths_of(r3), M.reads_of(pk, bo, ln, quals), ms)
+    assert m.deleted == [list(range(r3.hbv.n_edges)), []] and m.hbv.n_edges == 0
+    _same(res, m)
+    one_shot = step4.clean200x(r3.hbv, paths_of(r3), pk, bo, ln, quals, min_size=ms, inv=r3.inv2)
+    assert one_shot.edit_on_device is False
+    _same_results(res, one_shot)
+    m0 = M.clean200x(r3.hbv, r3.inv2, paths_of(r3), M.reads_of(pk, bo, ln, quals), 0)
+    _same(nxt, m0)
+
+
+@pytest.mark.parametrize("edit", ["host", "device"])
+@pytest.mark.parametrize("name", ["circle", "self", "swap"])
+def test_an_inv_that_mirrors_no_run_onto_a_run_is_an_error(name, edit):
+    """the argument check accepts it; on the device k4e_records declines, and the host edit, which walks the 'mirror run' as the reference
+    does, stops at the first vertex that is not on a run (tools/step4_bad_inv.cpp is the same under the host sanitizers)"""
+    h, paths, (pk, bo, ln), quals, inv = EC.bad_inv_cases()[name]
+    with pytest.raises(step2.Step2Error) as e:
+        step4.clean200x(h, paths, pk, bo, ln, quals, inv=inv, edit=edit)
+    assert e.value.code == 6 and "inv" in str(e.value), str(e.value)
+    h, paths, (pk, bo, ln), quals, ms = _EDIT_CASES["a_interleaved_runs"].inputs
+    after = step4.clean200x(h, paths, pk, bo, ln, quals, min_size=ms, edit="device")
+    assert after.edit_on_device is True and _k4e()
+    _same(after, _model("a_interleaved_runs", _EDIT_CASES["a_interleaved_runs"].inputs))

@@ -82,8 +82,8 @@ struct Csr { std::vector<uint64_t> from_off, to_off; std::vector<int32_t> from_v
 // packed 2-bit edge objects -> one base code per byte
 void unpack_edges(uint64_t E, const uint8_t* packed, const uint64_t* byte_off, const uint32_t* len, std::vector<std::vector<uint8_t>>& edges);
 int host_involution(const HostGraph& g, std::vector<int>& inv, std::string& err);
-void edit_graph(HostGraph& g, std::vector<int>& inv, std::vector<char>& dead, unsigned min_size, bool edit, std::vector<int32_t>& deleted,
-                std::vector<int32_t>& map, std::vector<int32_t>& add, uint64_t& n_merged);
+int edit_graph(HostGraph& g, std::vector<int>& inv, std::vector<char>& dead, unsigned min_size, bool edit, std::vector<int32_t>& deleted,
+               std::vector<int32_t>& map, std::vector<int32_t>& add, uint64_t& n_merged, std::string& err);
 void pack_edges(const HostGraph& g, std::vector<uint8_t>& packed, std::vector<uint64_t>& boff, std::vector<uint32_t>& len);
 void make_csr(const HostGraph& g, Csr& c);
 // host arrays of a graph whose K, E, NV and ebytes_cap are set in g -> fresh blocks in g (`ebits` with the 32 bytes of slack that k4_walks

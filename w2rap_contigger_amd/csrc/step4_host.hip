@@ -37,9 +37,12 @@ int host_involution(const HostGraph& g, std::vector<int>& inv, std::string& err)
 }
 
 // one pass's edit.  in: dead[e] from the vote (ids of g).  out: the sorted unique deleted list, g and inv edited,
-// map[e] (old id -> final id, -1: deleted) and add[e] (offsets[e]) for the path kernels, the number of merged runs
-void edit_graph(HostGraph& g, std::vector<int>& inv, std::vector<char>& dead, unsigned min_size, bool edit, std::vector<int32_t>& deleted,
-                std::vector<int32_t>& map, std::vector<int32_t>& add, uint64_t& n_merged) {
+// map[e] (old id -> final id, -1: deleted) and add[e] (offsets[e]) for the path kernels, the number of merged runs.
+// -> 0, or W2RAP_E_GRAPH (g and inv are then half edited and of no use): the reference walks a pushed run's mirror image
+// (inv[eright], inv[eleft]) along the single out-edges of its kill vertices without a look (GapToyTools3.cc:150-175); an inv that does
+// not mirror runs onto runs sends that walk off the graph or round a circle, so here every step of it is checked
+int edit_graph(HostGraph& g, std::vector<int>& inv, std::vector<char>& dead, unsigned min_size, bool edit, std::vector<int32_t>& deleted,
+               std::vector<int32_t>& map, std::vector<int32_t>& add, uint64_t& n_merged, std::string& err) {
     const size_t NV = g.frm.size(), E0 = g.edges.size();
     if (min_size > 0) {                                                      // Clean200.cc:370-380
         for (size_t v = 0; v < NV; ++v) {
@@ -54,7 +57,7 @@ void edit_graph(HostGraph& g, std::vector<int>& inv, std::vector<char>& dead, un
     deleted.clear();
     for (size_t e = 0; e < E0; ++e) if (dead[e]) deleted.push_back((int32_t)e);
     n_merged = 0;
-    if (!edit) return;
+    if (!edit) return 0;
     g.delete_edges(dead);
     // Cleanup: a path is cut at its first edge that is no longer in the graph (`alive` below)
     std::vector<char> alive;
@@ -86,7 +89,13 @@ void edit_graph(HostGraph& g, std::vector<int>& inv, std::vector<char>& dead, un
         const int new_no = (int)g.edges.size();
         int off = g.kmers(b.first);
         renum[b.first] = new_no; dead2[b.first] = 1;
+        // the first walk checks every step; the second one below repeats it on the unchanged graph
+        size_t steps = 0;
         for (int v = to_right[b.first]; v != to_right[b.second]; v = g.frm[v][0]) {
+            if (g.frm[v].size() != 1 || ++steps > NV) {
+                err = "inv does not mirror runs onto runs: the walk from inv[eright] of a merged run does not reach inv[eleft] along single out-edges";
+                return W2RAP_E_GRAPH;
+            }
             const int e = g.frm_e[v][0];
             dead2[e] = 1; offsets[e] = off; renum[e] = new_no; off += g.kmers(e);
         }
@@ -135,6 +144,7 @@ void edit_graph(HostGraph& g, std::vector<int>& inv, std::vector<char>& dead, un
     g = std::move(h);
     map.assign(E0, -1); add.assign(E0, 0);
     for (size_t e = 0; e < E0; ++e) if (alive[e]) { map[e] = to_new[renum[e]]; add[e] = offsets[e]; }
+    return 0;
 }
 
 void pack_edges(const HostGraph& g, std::vector<uint8_t>& packed, std::vector<uint64_t>& boff, std::vector<uint32_t>& len) {
@@ -207,7 +217,7 @@ int HostEditor4::pass(Ctx& c, const Graph4& gd, uint8_t* d_dead, unsigned min_si
     if (E0) W2_HIP(hipMemcpyAsync(dead.data(), d_dead, E0, hipMemcpyDeviceToHost, c.stream));
     W2_HIP(hipStreamSynchronize(c.stream));
     std::vector<int32_t> map, add;
-    edit_graph(g, inv, dead, min_size, edit, *deleted, map, add, *n_merged);
+    W2_TRY(edit_graph(g, inv, dead, min_size, edit, *deleted, map, add, *n_merged, c.err));
     *d_map = nullptr; *d_add = nullptr;
     if (!edit) { *next = gd; return 0; }
     // ---- the next pass's graph on the device

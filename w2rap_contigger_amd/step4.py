@@ -9,7 +9,8 @@ frag_reads_orig.{fastb,qualp}, writes <prefix>.large_K.clean.{hbv,paths}.
 The vote over the reads, the rewrite of the read paths and the edit of the graph itself (delete, merge runs, renumber: the k4e_*
 kernels) run in HIP kernels: the graph goes up once and comes down once.  ``edit="host"`` (EDIT_ON_HOST) runs the library's host edit
 instead, the cross-check; a graph that misses a precondition of the device edit (adjacency lists not sorted by neighbour, a run whose
-mirror image is not a run) takes it silently, with the same result.  `Step4Result.edit_on_device` tells which one ran.
+mirror image is not a run) takes it silently, with the same result.  `Step4Result.edit_on_device` tells which one ran.  An `inv` that
+pairs a merged run's ends with edges no run joins (the reference would walk off the graph) raises Step2Error, W2RAP_E_GRAPH.
 
 `clean200x_after_step3` is the same step straight behind Step 3 on one `step2.Step2Context` (w2rap_step2_run_step4_after_step3): the reads and
 their qualities are the context's, the large-K graph and paths are what `step3.repath_after_step2(ctx, keep_on_device=True)` left in
