@@ -1,4 +1,5 @@
-/* w2rap_step5.h -- C ABI of the MI355X-native replacement for the LAST line of w2rap-contigger's Step 5: PartnersToEnds.
+/* w2rap_step5.h -- C ABI of the MI355X-native replacements for the two read-sized ends of w2rap-contigger's Step 5: its LAST line,
+ * PartnersToEnds (below), and its opening, the paths index, Unsat's links and LayoutReads (w2rap_step5_open, further down).
  * Exported by the same shared library as Steps 1-4 (w2rap_contigger_amd/libw2rap_step2.so).
  *
  * Drop-in boundary.  w2rap_step5_partners_to_ends replaces exactly this call of the reference's main (src/modules/w2rap-contigger.cc:448):
@@ -77,8 +78,79 @@ typedef struct w2rap_step5_out {
 int  w2rap_step5_partners_to_ends(const w2rap_step5_in* in, const w2rap_step5_params* params, w2rap_step5_out* out, char* err, size_t errlen);
 void w2rap_step5_free(w2rap_step5_out* out);
 
-/* per-kernel device time of the last w2rap_step5_partners_to_ends in this process: "kernel_name total_ms launches\n" lines; returns the
- * bytes needed */
+/* ==== the OPENING of Step 5: the three read-sized passes the reference runs before its first cluster exists =====================
+ * w2rap_step5_open computes, from the clean graph, its involution and the read paths (no bases, no qualities):
+ *   INDEX   invert(pathsr, paths_inv, E)              src/modules/w2rap-contigger.cc:427, src/VecUtilities.h:693
+ *   LINKS   Phase 1 of Unsat: unsats[e] and mult      src/paths/long/large/Unsat.cc:142-207
+ *   LAYOUT  LayoutReads                               src/paths/long/large/GapToyTools2.cc:550-588
+ * Each result is one CSR over the edge objects.  The clustering half of Unsat, the local assemblies and AddNewStuff stay the reference's.
+ * All kernels are HIP for gfx950 (k5o_* of step5_open.hip, the library's scan and radix sort); there is no CPU fallback
+ * (W2RAP_E_NO_DEVICE).  Integer arithmetic throughout; the result does not depend on the order in which reads or pairs are processed.
+ *
+ * Limits (32-bit ids, as elsewhere in the library; beyond them the call answers W2RAP_E_ARG): n_edge_objs and n_vertices below 2^31,
+ * n_paths below 2^30 (a read has up to four layout entries, and the layout's sort carries an entry's number as its 32-bit value).
+ * The number of path entries is not limited: keys and offsets are 64-bit.
+ *
+ * INDEX.   index_read[index_off[e] .. index_off[e+1]) = the ids of the reads whose path holds e, ascending, a read once per occurrence.
+ * LINKS.   A pair (reads 2p, 2p+1; pid = p) with both paths non-empty is examined: x1 = the edges of p1, x2 = inv of the edges of p2,
+ *          reversed.  It is dropped when x1 and x2 share an edge (Meet2), or when v = to_right[x1.back] equals w = to_left[x2.front].
+ *          Otherwise w is searched from v over from_v, level by level for 15 levels, the frontier a MULTISET (no visited set): a level
+ *          that holds w satisfies the pair, however large the level; otherwise a level of more than 50 entries ends the search.  A
+ *          pair that is not satisfied and has p1.back != p2.back gives the links (p1.back, inv[p2.back], pid) and
+ *          (p2.back, inv[p1.back], pid).  link_to / link_pid[link_off[e] .. link_off[e+1]) = unsats[e] after the reference's Sort and
+ *          de-duplication, ordered by (link_to, pid).  kind_from / kind_to / kind_mult [n_kinds] = the map `mult`: one entry per distinct
+ *          (e, link_to) in that order, kind_mult its number of links.
+ * LAYOUT.  layout_pos / layout_id / layout_fw [layout_off[e] .. layout_off[e+1]) = layout_pos[e], layout_id[e], layout_or[e].  Per read
+ *          with a path x of n > 0 edges, kmers(e) = edge_len[e] - K + 1: forward (x[0], offset) and, if n > 1, (x[n-1], offset - kmers(x[0]))
+ *          -- the reference skips the interior edges BEFORE it subtracts their length, so only the first edge's K-mers come off, which
+ *          is reproduced; reverse, with y = inv of x reversed, len = edge_len[y[0]] + the sum of kmers(y[j]) over j >= 1 and
+ *          pos = len - (offset + read_len): (y[0], pos) and, if n > 1, (y[n-1], pos - kmers(y[0])).  Each edge's entries ascend by pos as
+ *          a SIGNED value.  Ties: the reference's SortSync leaves them in an unspecified order and its only consumer (FindPidsST) reads
+ *          the lists as sets; THIS LIBRARY orders ties by read id, then forward before reverse -- its own choice, not the reference's.
+ */
+#define W2RAP_STEP5_OPEN_INDEX  1u
+#define W2RAP_STEP5_OPEN_LINKS  2u
+#define W2RAP_STEP5_OPEN_LAYOUT 4u
+
+typedef struct w2rap_step5_open_in {
+    int32_t  K;                      /* hbv.K(); 16 <= K <= 640 (only LAYOUT reads it) */
+    uint64_t n_edge_objs;
+    const uint32_t* edge_len;        /* [n_edge_objs] bases, >= K */
+    uint64_t n_vertices;
+    const uint64_t* from_off;        /* [n_vertices+1] */
+    const int32_t*  from_v;          /* [n_edge_objs] */
+    const int32_t*  from_e;          /* [n_edge_objs] */
+    const uint64_t* to_off;          /* [n_vertices+1] */
+    const int32_t*  to_e;            /* [n_edge_objs] */
+    const int32_t*  inv;             /* [n_edge_objs]; inv[inv[e]] == e */
+    uint64_t n_paths;                /* even: read r and read r ^ 1 are mates */
+    const int32_t*  path_offset;     /* [n_paths] */
+    const uint64_t* path_off;        /* [n_paths+1] */
+    const int32_t*  path_edges;
+    const uint32_t* read_len;        /* [n_paths] bases[i].size() */
+} w2rap_step5_open_in;
+
+/* params: w2rap_step5_params; flags = any of W2RAP_STEP5_OPEN_*, 0 = all three.  A part that is not asked for launches no kernel and
+ * leaves its pointers null, its counters and its time zero */
+typedef struct w2rap_step5_open_out {
+    uint64_t* index_off;  uint32_t* index_read;                                  /* [E+1], [n_index] */
+    uint64_t* link_off;   int32_t* link_to;  uint32_t* link_pid;                 /* [E+1], [n_links] */
+    int32_t*  kind_from;  int32_t* kind_to;  uint32_t* kind_mult;                /* [n_kinds] */
+    uint64_t* layout_off; int32_t* layout_pos; uint32_t* layout_id; uint8_t* layout_fw;   /* [E+1], [n_layout]; fw 1 = forward */
+    /* LINKS: pairs with both paths non-empty, and what became of them (placed = meet + same_vertex + reached + unsat_depth + unsat_overflow) */
+    uint64_t n_pairs_placed, n_meet, n_same_vertex, n_reached;
+    uint64_t n_unsat_depth;          /* fell out of the 15 levels */
+    uint64_t n_unsat_overflow;       /* stopped by a level of more than 50 */
+    uint64_t n_unsat_same_end;       /* of the unsatisfied: p1.back == p2.back, no link */
+    uint64_t n_links, n_kinds, n_index, n_layout;
+    float ms_index, ms_links, ms_layout;       /* device time per part, milliseconds */
+} w2rap_step5_open_out;
+
+int  w2rap_step5_open(const w2rap_step5_open_in* in, const w2rap_step5_params* params, w2rap_step5_open_out* out, char* err, size_t errlen);
+void w2rap_step5_open_free(w2rap_step5_open_out* out);
+
+/* per-kernel device time of the last w2rap_step5_partners_to_ends or w2rap_step5_open in this process: "kernel_name total_ms launches\n"
+ * lines; returns the bytes needed */
 size_t w2rap_step5_profile(char* buf, size_t len);
 
 #ifdef __cplusplus

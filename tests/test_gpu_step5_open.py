@@ -1,0 +1,169 @@
+"""Step 5's opening on the GPU (w2rap_step5_open: the paths index, Unsat's links and multiplicities, LayoutReads) against the literals of
+the hand-made cases and against its CPU model (step5_open_model.py) array for array: hand-made and generated cases, each part alone,
+the early exit, argument errors, and a second call in the same process."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import step5_open_cases as S
+import step5_open_model as M
+from w2rap_contigger_amd import step2, step5
+
+pytestmark = pytest.mark.gpu
+
+CASES = S.cases()
+E_ARG = 1          # W2RAP_E_ARG (w2rap_step2.h)
+ARRAYS = {"index": ("index_off", "index_read"), "links": ("link_off", "link_to", "link_pid", "kind_from", "kind_to", "kind_mult"),
+          "layout": ("layout_off", "layout_pos", "layout_id", "layout_fw")}
+PART_COUNTERS = {"index": ("n_index",), "layout": ("n_layout",), "links": tuple(k for k in S.COUNTERS if k not in ("n_index", "n_layout"))}
+# a kernel only that part launches
+PART_KERNEL = {"index": "k5o_index_emit", "links": "k5o_pair_filter", "layout": "k5o_layout_fill"}
+
+
+def _same(res, m, parts=("index", "links", "layout")):
+    for p in parts:
+        for k in PART_COUNTERS[p]:
+            assert res.counters[k] == m.counters[k], k
+        for a in ARRAYS[p]:
+            got, want = getattr(res, a), getattr(m, a)
+            assert got is not None and got.dtype == want.dtype and np.array_equal(got, want), a
+
+
+def test_counter_names_match_the_binding():
+    assert S.COUNTERS == step5.OPEN_COUNTERS
+
+
+@pytest.mark.parametrize("name", sorted(CASES))
+def test_hand_made_cases(name):
+    c = CASES[name]
+    res = step5.opening(*c.inputs())
+    assert res.counters == c.counters
+    assert S.per_edge(res.index_off, res.index_read) == c.index
+    assert S.per_edge(res.link_off, res.link_to, res.link_pid) == c.links
+    assert S.kinds(res) == c.mult
+    assert S.per_edge(res.layout_off, res.layout_pos, res.layout_id, res.layout_fw) == c.layout
+    _same(res, M.opening(*c.inputs()))
+
+
+_GENERATED = {}
+
+
+def generated(seed):
+    """-> (inputs, the model's result), made once"""
+    if seed not in _GENERATED:
+        inputs = S.random_case(seed)
+        _GENERATED[seed] = (inputs, M.opening(*inputs))
+    return _GENERATED[seed]
+
+
+@pytest.mark.parametrize("seed", S.SEEDS)
+def test_against_the_model_on_generated_cases(seed):
+    inputs, m = generated(seed)
+    print(f"seed {seed}: {inputs[0].n_edges} edges, {len(inputs[3])} reads; model {m.counters}, largest multiplicity {int(max(m.kind_mult))}")
+    assert S.seed_conditions(m) == []          # every branch occurs, by the model's own count
+    res = step5.opening(*inputs)
+    _same(res, m)
+    assert step5.profile().get("k5o_reach", (0, 0))[1] == 1
+
+
+@pytest.mark.parametrize("part", sorted(ARRAYS))
+def test_each_part_alone(part):
+    inputs, m = generated(S.SEEDS[0])
+    res = step5.opening(*inputs, parts=(part,))
+    _same(res, m, (part,))
+    prof = step5.profile()
+    for p in ARRAYS:
+        assert (PART_KERNEL[p] in prof) == (p == part), (p, sorted(prof))
+        if p != part:
+            assert all(getattr(res, a) is None for a in ARRAYS[p])
+            assert all(res.counters[k] == 0 for k in PART_COUNTERS[p])
+    assert res.ms[f"ms_{part}"] > 0 and sum(res.ms.values()) == res.ms[f"ms_{part}"]
+
+
+@pytest.mark.parametrize("name", ["v_equals_w", "mates_share_an_edge", "one_read_without_a_path", "paths_of_1_2_and_4_edges"])
+def test_no_surviving_pair_launches_no_search(name):
+    """the links part alone, so that a sort or an offsets kernel in the profile could only be its own: the pair filter is the one
+    kernel with a profile line (the library's scan has none)"""
+    c = CASES[name]
+    res = step5.opening(*c.inputs(), parts=("links",))
+    assert set(step5.profile()) == {"k5o_pair_filter"}
+    assert {k: res.counters[k] for k in PART_COUNTERS["links"]} == {k: c.counters[k] for k in PART_COUNTERS["links"]}
+    assert res.counters["n_links"] == 0 and res.counters["n_kinds"] == 0
+    assert len(res.link_off) == c.inputs()[0].n_edges + 1 and not res.link_off.any()
+    assert len(res.link_to) == 0 and len(res.link_pid) == 0 and len(res.kind_mult) == 0
+
+
+def _raw_open(n_edge_objs=0, n_vertices=0, n_paths=0):
+    """w2rap_step5_open on sizes alone, every array null -> (return code, message)"""
+    L = step5.lib()
+    i = step5.Step5OpenIn(K=20, n_edge_objs=n_edge_objs, n_vertices=n_vertices, n_paths=n_paths)
+    o = step5.Step5OpenOut()
+    err = C.create_string_buffer(1024)
+    rc = L.w2rap_step5_open(C.byref(i), C.byref(step5.Step5Params(0, 0)), C.byref(o), err, 1024)
+    if rc == 0:
+        L.w2rap_step5_open_free(C.byref(o))
+    return rc, err.value.decode()
+
+
+@pytest.mark.parametrize("sizes", [dict(n_paths=1 << 30), dict(n_edge_objs=1 << 31), dict(n_vertices=1 << 31)])
+def test_sizes_beyond_32_bit_ids_are_refused(sizes):
+    """the limits the header states, refused before any array is looked at (all of them are null here)"""
+    rc, msg = _raw_open(**sizes)
+    assert rc == E_ARG and "ids are 32-bit" in msg
+
+
+@pytest.mark.parametrize("sizes,message", [(dict(n_paths=(1 << 30) - 2), "null input array"), (dict(n_edge_objs=(1 << 31) - 1, n_vertices=1), "null graph array"),
+                                           (dict(n_vertices=(1 << 31) - 1), "null adjacency offsets")])
+def test_largest_sizes_inside_the_limits_pass_the_size_check(sizes, message):
+    """one below each limit the call goes on to the next check, which finds the null arrays"""
+    rc, msg = _raw_open(**sizes)
+    assert rc == E_ARG and message in msg and "32-bit" not in msg
+
+
+def test_argument_errors():
+    h, inv, paths, read_len = CASES["multiplicities_3_and_1"].inputs()
+    po = paths[1]
+    with pytest.raises(step2.Step2Error) as e:                                 # an odd number of paths
+        step5.opening(h, inv, (paths[0][:-1], po[:-1], paths[2][:int(po[-2])]), read_len[:-1])
+    assert e.value.code == E_ARG and "odd" in str(e.value)
+    bad = paths[2].copy(); bad[3] = h.n_edges
+    with pytest.raises(step2.Step2Error) as e:
+        step5.opening(h, inv, (paths[0], po, bad), read_len)
+    assert e.value.code == E_ARG and "a path names an edge object that does not exist" in str(e.value)
+    bad = inv.copy(); bad[2] = h.n_edges
+    with pytest.raises(step2.Step2Error) as e:
+        step5.opening(h, bad, paths, read_len)
+    assert e.value.code == E_ARG and "inv names an edge object that does not exist" in str(e.value)
+    bad = inv.copy(); bad[0] = 2                                               # inv[0] = 2, inv[2] = 3
+    with pytest.raises(step2.Step2Error) as e:
+        step5.opening(h, bad, paths, read_len)
+    assert e.value.code == E_ARG and "inv[inv[e]] != e" in str(e.value)
+
+
+def _idle_context_bytes():
+    """live device bytes of the cached context the one-shot entry points use (taken from the cache and handed back)"""
+    L = step5.lib()
+    L.w2rap_step2_acquire.restype = C.c_void_p
+    L.w2rap_step2_acquire.argtypes = [C.c_int, C.c_char_p, C.c_size_t]
+    L.w2rap_step2_release.restype = None
+    L.w2rap_step2_release.argtypes = [C.c_void_p]
+    L.w2rap_step2_device_bytes.restype = C.c_uint64
+    L.w2rap_step2_device_bytes.argtypes = [C.c_void_p]
+    err = C.create_string_buffer(256)
+    ctx = L.w2rap_step2_acquire(0, err, 256)
+    assert ctx, err.value
+    try:
+        return int(L.w2rap_step2_device_bytes(ctx))
+    finally:
+        L.w2rap_step2_release(ctx)
+
+
+def test_second_call_in_one_process():
+    inputs, m = generated(S.SEEDS[1])
+    before = _idle_context_bytes()
+    a = step5.opening(*inputs)
+    b = step5.opening(*inputs)
+    _same(a, m); _same(b, m)
+    assert a.counters == b.counters
+    assert _idle_context_bytes() == before

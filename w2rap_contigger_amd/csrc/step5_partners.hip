@@ -22,6 +22,7 @@
 #include <string>
 #include <vector>
 #include "ctx.h"
+#include "step5_runs.h"
 #include "../../include/w2rap_step5.h"
 
 namespace w2 {
@@ -33,8 +34,6 @@ constexpr uint32_t NONE = 0xFFFFFFFFu;
 constexpr unsigned ROUND_BATCH = 32;                          // relaxation rounds between two looks at the "changed" words
 static_assert(ROUND_BATCH == 32, "the profile line of a batch is named k5_relax_x32");
 constexpr uint64_t KMASK = (1ull << (2 * KLEN)) - 1;
-
-inline unsigned grid5(uint64_t n, unsigned b = 256) { return (unsigned)((n + b - 1) / b); }
 
 // the 28-mer at base `pos` of a packed sequence: base pos + i at bits 2i.  Reads 8 bytes from byte pos / 4 on: the sequences' blocks
 // carry 16 bytes of slack, and whatever lies behind base pos + 27 is masked off
@@ -105,10 +104,6 @@ __global__ __launch_bounds__(256) void k5_emit(uint64_t NKM, uint64_t NI, const 
     keys[j] = kmer28(R.bits + R.boff[ids[i]], roff);
     vals[j] = (uint32_t)j;
     loc[j] = make_uint2((uint32_t)i, roff);
-}
-__global__ __launch_bounds__(256) void k5_heads(uint64_t n, const uint64_t* __restrict__ keys, uint32_t* __restrict__ head) {
-    const uint64_t j = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-    if (j < n) head[j] = j == 0 || keys[j] != keys[j - 1];
 }
 __global__ __launch_bounds__(256) void k5_groups(uint64_t n, const uint64_t* __restrict__ keys, const uint32_t* __restrict__ head, const uint64_t* __restrict__ hpos,
                                                  uint64_t* __restrict__ ukey, uint32_t* __restrict__ ustart) {
@@ -281,6 +276,9 @@ __global__ __launch_bounds__(256) void k5_path_write(uint64_t n, const uint64_t*
 
 std::string g_profile5;
 
+}  // namespace
+
+// (also called by step5_open.hip: w2rap_step5_profile reports the last Step-5 call of either kind)
 void save_profile5(Ctx& c) {
     (void)hipStreamSynchronize(c.stream);
     c.presolve();
@@ -288,25 +286,12 @@ void save_profile5(Ctx& c) {
     for (auto& s : c.prof_sums) { char line[256]; std::snprintf(line, sizeof line, "%s %.4f %llu\n", s.name.c_str(), s.ms, (unsigned long long)s.launches); g_profile5 += line; }
 }
 
+namespace {
+
 template <class T> T* host_dup(const T* src, uint64_t n) {
     T* p = (T*)host_result_alloc((n ? n : 1) * sizeof(T));
     if (p && n) std::memcpy(p, src, n * sizeof(T));
     return p;
-}
-unsigned bits_for(uint64_t count) {                            // bits that hold every value below `count`
-    unsigned b = 1;
-    while (b < 64 && (count - 1) >> b) ++b;
-    return b;
-}
-
-// heads of the runs of equal keys in a sorted array, their ranks, their number
-int run_heads(Ctx& c, const char* name, const uint64_t* keys, uint64_t n, uint32_t** head, uint64_t** hpos, uint64_t* n_runs) {
-    W2_ALLOC(*head, uint32_t, n + 1); W2_ALLOC(*hpos, uint64_t, n + 2);
-    LAUNCH(c, name, k5_heads, dim3(grid5(n)), dim3(256), 0, n, keys, *head);
-    W2_TRY(exclusive_scan_u32_to_u64(c, *head, *hpos, n));
-    W2_HIP(hipMemcpyAsync(n_runs, *hpos + n, 8, hipMemcpyDeviceToHost, c.stream));
-    W2_HIP(hipStreamSynchronize(c.stream));
-    return 0;
 }
 
 int partners(Ctx& c, const w2rap_step5_in& in, uint32_t max_len, w2rap_step5_out& out) {

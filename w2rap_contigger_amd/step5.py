@@ -27,6 +27,10 @@ class Step5Params(C.Structure):
     _fields_ = [("device", C.c_int32), ("flags", C.c_uint32)]
 
 
+OPEN_COUNTERS = ("n_pairs_placed", "n_meet", "n_same_vertex", "n_reached", "n_unsat_depth", "n_unsat_overflow", "n_unsat_same_end",
+                 "n_links", "n_kinds", "n_index", "n_layout")
+OPEN_PARTS = {"index": 1, "links": 2, "layout": 4}       # W2RAP_STEP5_OPEN_*
+OPEN_PHASES = ("ms_index", "ms_links", "ms_layout")
 COUNTERS = ("n_interesting", "n_read_kmers", "n_dict_kmers", "n_candidates", "n_good", "n_placed", "n_ambiguous")
 PHASES = ("ms_ends", "ms_select", "ms_dict", "ms_edges", "ms_candidates", "ms_verify", "ms_paths")
 
@@ -34,6 +38,19 @@ PHASES = ("ms_ends", "ms_select", "ms_dict", "ms_edges", "ms_candidates", "ms_ve
 class Step5Out(C.Structure):
     _fields_ = ([("n_paths", C.c_uint64), ("path_offset", C.c_void_p), ("path_off", C.c_void_p), ("path_edges", C.c_void_p)] +
                 [(k, C.c_uint64) for k in COUNTERS] + [(k, C.c_float) for k in PHASES])
+
+
+class Step5OpenIn(C.Structure):
+    _fields_ = [("K", C.c_int32), ("n_edge_objs", C.c_uint64), ("edge_len", C.c_void_p), ("n_vertices", C.c_uint64), ("from_off", C.c_void_p), ("from_v", C.c_void_p),
+                ("from_e", C.c_void_p), ("to_off", C.c_void_p), ("to_e", C.c_void_p), ("inv", C.c_void_p),
+                ("n_paths", C.c_uint64), ("path_offset", C.c_void_p), ("path_off", C.c_void_p), ("path_edges", C.c_void_p), ("read_len", C.c_void_p)]
+
+
+_OPEN_ARRAYS = ("index_off", "index_read", "link_off", "link_to", "link_pid", "kind_from", "kind_to", "kind_mult", "layout_off", "layout_pos", "layout_id", "layout_fw")
+
+
+class Step5OpenOut(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k in _OPEN_ARRAYS] + [(k, C.c_uint64) for k in OPEN_COUNTERS] + [(k, C.c_float) for k in OPEN_PHASES]
 
 
 _ready = False
@@ -46,6 +63,9 @@ def lib():
         L.w2rap_step5_partners_to_ends.argtypes = [C.POINTER(Step5In), C.POINTER(Step5Params), C.POINTER(Step5Out), C.c_char_p, C.c_size_t]
         L.w2rap_step5_free.argtypes = [C.POINTER(Step5Out)]
         L.w2rap_step5_free.restype = None
+        L.w2rap_step5_open.argtypes = [C.POINTER(Step5OpenIn), C.POINTER(Step5Params), C.POINTER(Step5OpenOut), C.c_char_p, C.c_size_t]
+        L.w2rap_step5_open_free.argtypes = [C.POINTER(Step5OpenOut)]
+        L.w2rap_step5_open_free.restype = None
         L.w2rap_step5_profile.argtypes = [C.c_char_p, C.c_size_t]
         L.w2rap_step5_profile.restype = C.c_size_t
         _ready = True
@@ -93,8 +113,68 @@ def partners_to_ends(hbv: F.HBV, paths, reads, quals, device=0, qual_off=None) -
         L.w2rap_step5_free(C.byref(o))
 
 
+@dataclass
+class Step5Opening:
+    """the three CSRs over the edge objects (include/w2rap_step5.h); the arrays of a part that was not asked for are None"""
+    index_off: np.ndarray         # u64[E+1]
+    index_read: np.ndarray        # u32: read ids, ascending per edge
+    link_off: np.ndarray          # u64[E+1]
+    link_to: np.ndarray           # i32, ordered by (link_to, pid) per edge
+    link_pid: np.ndarray          # u32
+    kind_from: np.ndarray         # i32[n_kinds]: the distinct (edge, link_to), in order ...
+    kind_to: np.ndarray
+    kind_mult: np.ndarray         # u32: ... and how many links each has
+    layout_off: np.ndarray        # u64[E+1]
+    layout_pos: np.ndarray        # i32, ascending (signed) per edge; ties by read id, then forward first
+    layout_id: np.ndarray         # u32
+    layout_fw: np.ndarray         # u8, 1 = forward
+    counters: dict                # OPEN_COUNTERS -> int
+    ms: dict                      # OPEN_PHASES -> device milliseconds
+
+
+def opening(hbv: F.HBV, inv, paths, read_len, parts=("index", "links", "layout"), device=0) -> Step5Opening:
+    """The read-sized passes at the front of Step 5 through the C entry point (w2rap_step5_open): the paths index (invert), the links
+    and multiplicities of Unsat's phase 1, and LayoutReads.  paths = (offset i32[n], path_off u64[n+1], edges i32[]); inv = the graph's
+    involution; read_len u32[n].  parts: any of "index", "links", "layout"."""
+    L = lib()
+    flags = 0
+    for p in parts:
+        if p not in OPEN_PARTS:
+            raise ValueError(f"unknown part {p!r}: one of {sorted(OPEN_PARTS)}")
+        flags |= OPEN_PARTS[p]
+    if not flags:
+        raise ValueError("no part asked for")
+    keep = [np.ascontiguousarray(hbv.edge_len, np.uint32), np.ascontiguousarray(hbv.from_off, np.uint64), np.ascontiguousarray(hbv.from_v, np.int32),
+            np.ascontiguousarray(hbv.from_e, np.int32), np.ascontiguousarray(hbv.to_off, np.uint64), np.ascontiguousarray(hbv.to_e, np.int32),
+            np.ascontiguousarray(inv, np.int32), np.ascontiguousarray(paths[0], np.int32), np.ascontiguousarray(paths[1], np.uint64),
+            np.ascontiguousarray(paths[2], np.int32), np.ascontiguousarray(read_len, np.uint32)]
+    if len(keep[6]) != len(keep[0]):
+        raise ValueError("inv must have one entry per edge object")
+    if len(keep[8]) != len(keep[7]) + 1 or len(keep[10]) != len(keep[7]):
+        raise ValueError("path_off must have n + 1 entries and read_len n, n = len(path_offset)")
+    p = lambda a: _ptr(a) if len(a) else None
+    i = Step5OpenIn(hbv.K, len(keep[0]), p(keep[0]), hbv.n_vertices, p(keep[1]), p(keep[2]), p(keep[3]), p(keep[4]), p(keep[5]), p(keep[6]),
+                    len(keep[7]), p(keep[7]), p(keep[8]), p(keep[9]), p(keep[10]))
+    prm = Step5Params(device, flags)
+    o = Step5OpenOut()
+    err = C.create_string_buffer(1024)
+    rc = L.w2rap_step5_open(C.byref(i), C.byref(prm), C.byref(o), err, 1024)
+    if rc:
+        raise Step2Error(rc, err.value.decode(errors="replace"))
+    try:
+        E = len(keep[0])
+        size = {"index_off": E + 1, "index_read": o.n_index, "link_off": E + 1, "link_to": o.n_links, "link_pid": o.n_links, "kind_from": o.n_kinds,
+                "kind_to": o.n_kinds, "kind_mult": o.n_kinds, "layout_off": E + 1, "layout_pos": o.n_layout, "layout_id": o.n_layout, "layout_fw": o.n_layout}
+        dtype = {"index_off": np.uint64, "index_read": np.uint32, "link_off": np.uint64, "link_to": np.int32, "link_pid": np.uint32, "kind_from": np.int32,
+                 "kind_to": np.int32, "kind_mult": np.uint32, "layout_off": np.uint64, "layout_pos": np.int32, "layout_id": np.uint32, "layout_fw": np.uint8}
+        arrays = {k: (_np_from(getattr(o, k), dtype[k], int(size[k])) if getattr(o, k) else None) for k in _OPEN_ARRAYS}
+        return Step5Opening(**arrays, counters={k: int(getattr(o, k)) for k in OPEN_COUNTERS}, ms={k: float(getattr(o, k)) for k in OPEN_PHASES})
+    finally:
+        L.w2rap_step5_open_free(C.byref(o))
+
+
 def profile():
-    """-> {kernel name: (total ms, launches)} of the last partners_to_ends in this process"""
+    """-> {kernel name: (total ms, launches)} of the last partners_to_ends or opening in this process"""
     L = lib()
     n = L.w2rap_step5_profile(None, 0)
     buf = C.create_string_buffer(int(n) + 16)
