@@ -129,21 +129,24 @@ def gfa_goldens():
 
 
 # the tests whose reference runs are replayed from refruns/<case>/ (conftest.reference_outputs)
-REFRUN_TESTS = ("tests/test_step3_consumer.py", "tests/test_step3_oracle.py", "tests/test_gfa_oracle.py", "tests/test_step1_oracle.py")
+REFRUN_TESTS = ("tests/test_step3_consumer.py", "tests/test_step3_oracle.py", "tests/test_gfa_oracle.py", "tests/test_step1_oracle.py",
+                "tests/test_step5_reference.py", "tests/test_step4_model.py")
 
 
-def refruns():
-    """runs those tests with W2RAP_RECORD_REFERENCE=1: every reference run they make is done live and recorded"""
+def refruns(tests=()):
+    """runs those tests with W2RAP_RECORD_REFERENCE=1: every reference run they make is done live and recorded.  `make_golden.py refruns
+    <test file> ...` records the runs of the files named only and leaves every other case as it is"""
     import subprocess
-    shutil.rmtree(os.path.join(HERE, "refruns"), ignore_errors=True)
-    subprocess.check_call([sys.executable, "-m", "pytest", "-q", "-m", "not gpu", *REFRUN_TESTS], cwd=ROOT,
+    if not tests:
+        shutil.rmtree(os.path.join(HERE, "refruns"), ignore_errors=True)
+    subprocess.check_call([sys.executable, "-m", "pytest", "-q", "-m", "not gpu", *(tests or REFRUN_TESTS)], cwd=ROOT,
                           env=dict(os.environ, W2RAP_RECORD_REFERENCE="1"))
 
 
 def main():
     O.build(ref=True)
     if len(sys.argv) > 1 and sys.argv[1] == "refruns":
-        return refruns()
+        return refruns(sys.argv[2:])
     if len(sys.argv) > 1 and sys.argv[1] == "gfa":
         return gfa_goldens()
     if len(sys.argv) > 1 and sys.argv[1] == "step1":

@@ -9,13 +9,21 @@ sequence overlap (nothing here reads a base), a handful of reads.  Every case wr
     Case.layout   {edge: [(pos, read id, forward)]}
     Case.counters every one of step5.OPEN_COUNTERS
 
+    recorded() -> the names of the cases (hand-made, and random_<seed> for SEEDS) whose run of the reference's own invert and LayoutReads
+                  lies under tests/golden/refruns/step5_open_<name>/
+    reference_run(name, workdir) -> (index, layout) of that run, as per_edge gives them
+
 Unless a case says otherwise an edge has 30 bases (11 K-mers) and a read has 10 bases at offset 0 of a one-edge path [e]: its layout
 entries are (e, 0, forward) and (inv e, 30 - 10 = 20, reverse).  In the search cases the pair is (a read on `a`, a read on inv t) for a
 forward edge t = W -> X: x1 = [a], x2 = [t], the search runs from v = to_right[a] for w = W, and an unsatisfied pair links a -> t and
 inv t -> inv a."""
+import os
+
 import numpy as np
 
+from conftest import reference_outputs
 from step4_cases import Builder
+from w2rap_contigger_amd import formats as F
 
 K = 20
 COUNTERS = ("n_pairs_placed", "n_meet", "n_same_vertex", "n_reached", "n_unsat_depth", "n_unsat_overflow", "n_unsat_same_end",
@@ -364,3 +372,50 @@ def seed_conditions(m):
     if not (len(m.layout_pos) and int(min(m.layout_pos)) < 0):
         missing.append("a negative layout position")
     return missing
+
+
+# ---- recorded runs of the reference's invert and LayoutReads ------------------------------------------------------------------------
+INPUTS = ["t.hbv", "t.paths", "frag_reads_orig.fastb", "t.inv"]
+OUTPUTS = ["t.index.txt", "t.layout.txt"]
+# cases the reference could not be run on -> its message; they stay on literals and model
+NOT_RECORDED = {}
+_INPUTS = {}
+
+
+def inputs_of(name):
+    """the inputs of a hand-made case, or of the generated case random_<seed>, made once"""
+    if name not in _INPUTS:
+        _INPUTS[name] = random_case(int(name[len("random_"):])) if name.startswith("random_") else cases()[name].inputs()
+    return _INPUTS[name]
+
+
+def recorded():
+    return [n for n in sorted(cases()) + [f"random_{s}" for s in SEEDS] if n not in NOT_RECORDED]
+
+
+def reference_run(name, workdir):
+    """stages the case's inputs in workdir (reads of the case's lengths, every base A: LayoutReads asks for the sizes only; t.inv, the
+    case's own involution, one integer per line), puts the recorded t.index.txt and t.layout.txt beside them (recording: runs
+    oracle/_ref/ref_step5 at 1 thread and at 4, which must agree) -> ({edge: [read ids]}, {edge: [(pos, id, forward)]}), in the
+    reference's order"""
+    h, inv, paths, read_len = inputs_of(name)
+    F.write_hbv(os.path.join(workdir, "t.hbv"), h)
+    F.write_paths(os.path.join(workdir, "t.paths"), *paths)
+    off = np.zeros(len(read_len) + 1, np.uint64); np.cumsum(read_len, out=off[1:])
+    F.write_fastb(os.path.join(workdir, "frag_reads_orig.fastb"), *F.pack_bases(np.zeros(int(off[-1]), np.uint8), off))
+    with open(os.path.join(workdir, "t.inv"), "w") as f:
+        f.write("".join(f"{int(x)}\n" for x in inv))
+
+    def run():
+        from oracle import oracle5
+        got = []
+        for threads in (1, 4):
+            oracle5.run_reference5(workdir, "open", threads)
+            got.append([open(os.path.join(workdir, o), "rb").read() for o in OUTPUTS])
+        assert got[0] == got[1], f"{name}: the reference's result at 4 threads is not its result at 1"
+    reference_outputs(f"step5_open_{name}", workdir, INPUTS, OUTPUTS, run)
+    rows = [[[int(x) for x in line.split()] for line in open(os.path.join(workdir, o)).read().split("\n")[:-1]] for o in OUTPUTS]
+    assert len(rows[0]) == len(rows[1]) == h.n_edges
+    index = {e: l for e, l in enumerate(rows[0]) if l}
+    layout = {e: [(l[j], l[j + 1], bool(l[j + 2])) for j in range(0, len(l), 3)] for e, l in enumerate(rows[1]) if l}
+    return index, layout

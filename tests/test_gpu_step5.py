@@ -1,5 +1,6 @@
-"""Step 5's tail on the GPU (w2rap_step5_partners_to_ends) against its CPU model (step5_model.py): the hand-made cases, two generated
-cases behind the library's own Steps 2-4, the early return, argument errors, and a second call in the same process."""
+"""Step 5's tail on the GPU (w2rap_step5_partners_to_ends) against recorded runs of the reference's own PartnersToEnds (replayed from
+tests/golden/refruns/step5_tail_<case>/) and against its CPU model (step5_model.py): the hand-made cases, seeded small random cases, two
+generated cases behind the library's own Steps 2-4, the early return, argument errors, and a second call in the same process."""
 import ctypes as C
 
 import numpy as np
@@ -34,6 +35,27 @@ def test_hand_made_cases(name):
     for k, v in c.counters.items():
         assert res.counters[k] == v, k
     _same(res, M.partners_to_ends(h, paths, reads, quals))
+
+
+@pytest.mark.parametrize("name", S.recorded())
+def test_equals_the_recorded_reference(name, tmp_path):
+    """replay only: the reference's t.out.paths for the case's inputs, recorded where the reference was at hand"""
+    offset, path_off, edges = S.reference_run(name, str(tmp_path))
+    res = step5.partners_to_ends(*S.inputs_of(name))
+    assert np.array_equal(res.path_off, path_off)
+    assert np.array_equal(res.path_edges, edges)
+    assert np.array_equal(res.path_offset, offset)
+
+
+@pytest.mark.parametrize("seed", S.SEEDS)
+def test_against_the_model_on_random_cases(seed):
+    h, paths, reads, quals = S.inputs_of(f"random_{seed}")
+    m = M.partners_to_ends(h, paths, reads, quals)
+    print(f"seed {seed}: {h.n_edges} edges, {len(reads[2])} reads; model {m.counters} {m.extra}")
+    assert S.seed_conditions(m) == []          # every branch occurs, by the model's own count
+    res = step5.partners_to_ends(h, paths, reads, quals)
+    _same(res, m)
+    assert step5.profile().get("k5_verify", (0, 0))[1] == 1
 
 
 # ---- generated: the planted workload through Steps 2, 3 and 4 of this library, then a seeded 5 % of the reads lose their paths

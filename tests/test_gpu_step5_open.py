@@ -1,6 +1,7 @@
 """Step 5's opening on the GPU (w2rap_step5_open: the paths index, Unsat's links and multiplicities, LayoutReads) against the literals of
-the hand-made cases and against its CPU model (step5_open_model.py) array for array: hand-made and generated cases, each part alone,
-the early exit, argument errors, and a second call in the same process."""
+the hand-made cases, against recorded runs of the reference's own invert and LayoutReads (index and layout; replayed from
+tests/golden/refruns/step5_open_<case>/) and against its CPU model (step5_open_model.py) array for array: hand-made and generated cases,
+each part alone, the early exit, argument errors, and a second call in the same process."""
 import ctypes as C
 
 import numpy as np
@@ -46,13 +47,27 @@ def test_hand_made_cases(name):
     _same(res, M.opening(*c.inputs()))
 
 
+@pytest.mark.parametrize("name", S.recorded())
+def test_index_and_layout_equal_the_recorded_reference(name, tmp_path):
+    """replay only.  The index list for list; the layout per edge: the positions in order and the (pos, id, forward) entries as a multiset
+    (SortSync leaves the order of entries that tie on pos open; the library's order is its own)"""
+    index, layout = S.reference_run(name, str(tmp_path))
+    res = step5.opening(*S.inputs_of(name))
+    assert S.per_edge(res.index_off, res.index_read) == index
+    lay = {e: [(p, i, bool(f)) for p, i, f in l] for e, l in S.per_edge(res.layout_off, res.layout_pos, res.layout_id, res.layout_fw).items()}
+    assert sorted(lay) == sorted(layout)
+    for e, l in lay.items():
+        assert [p for p, _, _ in l] == [p for p, _, _ in layout[e]], f"edge {e}"
+        assert sorted(l) == sorted(layout[e]), f"edge {e}"
+
+
 _GENERATED = {}
 
 
 def generated(seed):
     """-> (inputs, the model's result), made once"""
     if seed not in _GENERATED:
-        inputs = S.random_case(seed)
+        inputs = S.inputs_of(f"random_{seed}")
         _GENERATED[seed] = (inputs, M.opening(*inputs))
     return _GENERATED[seed]
 
