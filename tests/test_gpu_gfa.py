@@ -76,6 +76,14 @@ def test_gpu_gfa_rejects_a_graph_without_reverse_complements():
     fe = h.from_e.copy(); fe[0] = h.n_edges + 7                     # ... or name one that does not exist
     with pytest.raises(step2.Step2Error, match="does not exist"):
         gfa.gfa_dump(F.HBV(h.K, h.from_off, h.from_v, fe, h.to_off, h.to_e, h.edge_packed, h.edge_byte_off, h.edge_len))
+    fe = h.from_e.copy(); fe[0] = fe[1]                             # ... or name one twice, in either list: rejected on the host, before any kernel
+    with pytest.raises(step2.Step2Error, match="does not name every edge object once") as e:
+        gfa.gfa_dump(F.HBV(h.K, h.from_off, h.from_v, fe, h.to_off, h.to_e, h.edge_packed, h.edge_byte_off, h.edge_len))
+    assert e.value.code == 1
+    te = h.to_e.copy(); te[-1] = te[0]
+    with pytest.raises(step2.Step2Error, match="does not name every edge object once") as e:
+        gfa.gfa_dump(F.HBV(h.K, h.from_off, h.from_v, h.from_e, h.to_off, te, h.edge_packed, h.edge_byte_off, h.edge_len))
+    assert e.value.code == 1
 
 
 def test_gpu_gfa_of_a_fresh_step2_and_step3_graph():

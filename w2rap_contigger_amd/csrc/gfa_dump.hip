@@ -9,6 +9,7 @@
 //   GFADump, find_lines = false  src/GFADump.cc:228-286              kg_seg_len + scan + kg_seg_write (16 output bytes per thread, line by
 //                                                                      binary search), kg_links<false> + scan + kg_links<true>
 // Sequence text dominates: 1 byte written per base, 1/4 byte read.
+#include <algorithm>
 #include <cstdlib>
 #include <cstring>
 #include <string>
@@ -309,10 +310,14 @@ int gfa(Ctx& c, const w2rap_gfa_in& in, const w2rap_gfa_params& P, w2rap_gfa_out
         uint64_t canonical = 0;
         for (uint64_t s : sizes) canonical += s;
         out.canonical_size = canonical;
+        // The source compares cs * 100.0 / denom with the decile; the reference tool as built (-Ofast) multiplies cs by 100.0 / denom,
+        // one ulp low where the running sum lands on a decile exactly, and takes one more contig there.  This file is built without
+        // fast-math, so the product below is evaluated as written.
         auto walk = [&](uint64_t denom, bool stop_at_end, auto&& put) {
             uint64_t k = 0; int64_t cs = 0;                                  // sizes[NC-1-k] = the k-th longest
+            const double per = 100.0 / (double)denom;
             for (int i = 10, j = 0; i < 100; i += 10, ++j) {
-                while ((double)(cs * 100.0) / denom < i && (!stop_at_end || k < NC)) { if (k >= NC) break; cs += sizes[NC - 1 - k]; ++k; }
+                while ((double)cs * per < i && (!stop_at_end || k < NC)) { if (k >= NC) break; cs += sizes[NC - 1 - k]; ++k; }
                 put(j, (stop_at_end && k == NC) ? -1 : (k ? (int64_t)sizes[NC - k] : 0));
             }
         };
@@ -367,6 +372,19 @@ int w2rap_gfa_dump(const w2rap_gfa_in* in, const w2rap_gfa_params* P, w2rap_gfa_
     for (uint64_t o = 0; o < in->n_edge_objs; ++o) {
         if (in->edge_len[o] == 0) return fail(W2RAP_E_ARG, "an empty edge object");
         if (in->edge_byte_off[o + 1] - in->edge_byte_off[o] != (in->edge_len[o] + 3ull) / 4) return fail(W2RAP_E_ARG, "edge_byte_off does not match edge_len");
+    }
+    {   // every object once in each list: one named twice would leave another without a left or right vertex, and kg_links would index the
+        // offsets with -1 (an id out of range is left to kg_ends, which reports it)
+        std::vector<uint8_t> seen(in->n_edge_objs);
+        for (const int32_t* lst : {in->from_e, in->to_e}) {
+            std::fill(seen.begin(), seen.end(), 0);
+            for (uint64_t i = 0; i < in->n_edge_objs; ++i) {
+                const int32_t x = lst[i];
+                if (x < 0 || (uint64_t)x >= in->n_edge_objs) continue;
+                if (seen[x]) return fail(W2RAP_E_ARG, "an adjacency list does not name every edge object once");
+                seen[x] = 1;
+            }
+        }
     }
     char ebuf[512] = {0};
     w2rap_step2_ctx* h = w2rap_step2_acquire(P->device, ebuf, sizeof ebuf);
