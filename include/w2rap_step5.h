@@ -1,5 +1,6 @@
-/* w2rap_step5.h -- C ABI of the MI355X-native replacements for the two read-sized ends of w2rap-contigger's Step 5: its LAST line,
- * PartnersToEnds (below), and its opening, the paths index, Unsat's links and LayoutReads (w2rap_step5_open, further down).
+/* w2rap_step5.h -- C ABI of the MI355X-native replacements for the read-sized parts of w2rap-contigger's Step 5: its LAST line,
+ * PartnersToEnds (below), its opening, the paths index, Unsat's links and LayoutReads (w2rap_step5_open, further down), and AddNewStuff,
+ * which rebuilds the graph with the patches in front of PartnersToEnds (w2rap_step5_add_new_stuff, at the end).
  * Exported by the same shared library as Steps 1-4 (w2rap_contigger_amd/libw2rap_step2.so).
  *
  * Drop-in boundary.  w2rap_step5_partners_to_ends replaces exactly this call of the reference's main (src/modules/w2rap-contigger.cc:448):
@@ -7,7 +8,8 @@
  * A read that has no path, whose mate (read id ^ 1) is placed and ends on an edge within 500 K-mers of a dead end of the graph, has its
  * 28-mers looked up against every edge object; every (edge, offset) hit is checked with a quality-aware sliding window, and the read is
  * placed -- path [edge], offset -- when exactly ONE candidate is good.  The graph is not edited; the output is the read paths.
- * Everything before it in Step 5 (the local assemblies, AddNewStuff, Unsat) and Steps 6-7 stay the reference's.
+ * AddNewStuff, the call in front of it, is w2rap_step5_add_new_stuff (at the end of this header).  The local assemblies, the clustering
+ * half of Unsat and Steps 6-7 stay the reference's.
  *
  * What runs where.  Everything runs in HIP kernels for gfx950 (the k5_* kernels of step5_partners.hip, the library's scans and radix sort);
  * there is no CPU fallback (W2RAP_E_NO_DEVICE).  The host checks the arguments and derives each edge's two vertices from the adjacency
@@ -149,7 +151,80 @@ typedef struct w2rap_step5_open_out {
 int  w2rap_step5_open(const w2rap_step5_open_in* in, const w2rap_step5_params* params, w2rap_step5_open_out* out, char* err, size_t errlen);
 void w2rap_step5_open_free(w2rap_step5_open_out* out);
 
-/* per-kernel device time of the last w2rap_step5_partners_to_ends or w2rap_step5_open in this process: "kernel_name total_ms launches\n"
+/* ==== the CLOSE of Step 5: AddNewStuff, the call in front of PartnersToEnds and the only place in Step 5 where the graph changes ====
+ *     AddNewStuff(new_stuff, hbr, inv2, pathsr, bases, quals, MIN_GAIN, TRACE_PATHS, work_dir, EXT_MODE);
+ *                                                  src/modules/w2rap-contigger.cc:447, src/paths/long/large/GapToyTools4.cc:133-368
+ * w2rap_step5_add_new_stuff takes the clean large-K graph, the read paths, the reads with their qualities and the patch sequences
+ * `new_stuff` (what the local assemblies of AssembleGaps2 found), and does what the reference does:
+ *   ALL        allx = the edge objects in id order, then one (K+1)-mer per vertex crossing in BuildAll's order (vertex, i1 over To, i2
+ *              over From: the last K bases of e1 followed by base K-1 of e2), then new_stuff                          (:131-161, :238-241)
+ *   GRAPH      buildBigKHBVFromReads(K, allx): the SAME builder RepathInMemory calls -- the back half of this library's Step 3, shared
+ *              (csrc/step3_back.h).  W2RAP_STEP3_UNIQUE_KMERS' shortcut is off here: new_stuff repeats the graph's K-mers.  to3[e] /
+ *              left3[e] = the path and first skip of sequence e of allx, e an old edge object                         (:250-262)
+ *   TRANSLATE  TranslatePaths: every read path moves onto the new graph and is cut to ONE edge.  A path the reference clear()s keeps its
+ *              OLD offset (ReadPath::clear is std::vector's: mOffset is not touched), and so it does here             (:164-197)
+ *   EXTEND     ExtendPath, mode 1: a read that runs past the end of its edge is extended over the branches behind it when exactly one
+ *              extension covering the read beats the runner-up by min_gain in summed quality at mismatches           (:289-356)
+ * The new graph comes back laid out exactly as w2rap_step3_out lays one out; edge numbering as in Step 3 (canonical, or edge_order_hint).
+ * All kernels are HIP for gfx950 (k5a_* of step5_add.hip and the k3_* of the shared back half); there is no CPU fallback.
+ *
+ * W2RAP_E_ARG before any kernel runs: K odd or outside [16, 640] (what the Step-3 stage builds); ext_mode != 1 -- the reference's mode 2
+ * is NOT built; min_gain < 1 -- at 1 and above a tie for the best extension never extends, so the order the reference's SortSync leaves
+ * ties in cannot matter, below 1 it would; an unknown flag; and every check of w2rap_step5_in.  new_stuff entries may have any length,
+ * 0 and below K included (they hold no K-mer), and n_new may be 0.
+ */
+#define W2RAP_STEP5_ADD_KEEP_MAP 1u  /* return to3 / left3 */
+
+typedef struct w2rap_step5_add_params {
+    int32_t  device;                 /* HIP device ordinal */
+    int32_t  min_gain;               /* MIN_GAIN: the reference passes 5; >= 1 */
+    int32_t  ext_mode;               /* EXT_MODE: the reference passes 1; only 1 is built */
+    const w2rap_edge_hint* edge_order_hint;   /* as in Step 3; NULL = canonical (lexicographic) order of the new graph's unipaths */
+    uint32_t flags;                  /* W2RAP_STEP5_ADD_KEEP_MAP */
+} w2rap_step5_add_params;
+
+typedef struct w2rap_step5_add_out {
+    /* the new graph, as w2rap_step3_out lays it out */
+    int32_t  K;
+    uint64_t n_vertices;
+    uint64_t n_edge_objs;
+    uint8_t*  edge_packed;
+    uint64_t* edge_byte_off;         /* [n_edge_objs+1] */
+    uint32_t* edge_len;              /* [n_edge_objs] */
+    int32_t*  vleft;                 /* [n_edge_objs] */
+    int32_t*  vright;                /* [n_edge_objs] */
+    uint64_t* from_off;              /* [n_vertices+1] */
+    int32_t*  from_v;
+    int32_t*  from_e;
+    uint64_t* to_off;                /* [n_vertices+1] */
+    int32_t*  to_v;
+    int32_t*  to_e;
+    int32_t*  inv2;                  /* [n_edge_objs] the new graph's involution */
+    /* ALL read paths on the new graph */
+    uint64_t n_paths;
+    int32_t*  path_offset;           /* [n_paths] */
+    uint64_t* path_off;              /* [n_paths+1] */
+    int32_t*  path_edges;
+    /* W2RAP_STEP5_ADD_KEEP_MAP: a CSR over the OLD edge objects, and left3 */
+    uint64_t n_old_edge_objs;
+    uint64_t* to3_off;               /* [n_old_edge_objs+1] */
+    int32_t*  to3;
+    int32_t*  left3;                 /* [n_old_edge_objs] */
+    /* counters */
+    uint64_t n_all, n_junctions, n_all_bases;               /* sequences of allx; of those, vertex crossings; the sum of their lengths */
+    uint64_t n_kmer_instances, n_kmers_distinct, n_unipaths;
+    uint64_t n_tr_empty, n_tr_first, n_tr_walked, n_tr_cleared;   /* TranslatePaths: sum = n_paths */
+    uint64_t n_ext_tried;            /* reads past ExtendPath's early returns = too_many + no_cover + ambiguous + extended */
+    uint64_t n_ext_too_many, n_ext_no_cover, n_ext_ambiguous, n_ext_extended;
+    float ms_all, ms_dict, ms_graph, ms_translate, ms_extend;     /* device time per phase, milliseconds */
+} w2rap_step5_add_out;
+
+/* in: w2rap_step5_in (n_paths need not be even here: no mates are looked at); new_stuff in the packing of the edges */
+int  w2rap_step5_add_new_stuff(const w2rap_step5_in* in, uint64_t n_new, const uint8_t* new_packed, const uint64_t* new_byte_off, const uint32_t* new_len,
+                               const w2rap_step5_add_params* params, w2rap_step5_add_out* out, char* err, size_t errlen);
+void w2rap_step5_add_free(w2rap_step5_add_out* out);
+
+/* per-kernel device time of the last w2rap_step5_partners_to_ends, w2rap_step5_open or w2rap_step5_add_new_stuff in this process: "kernel_name total_ms launches\n"
  * lines; returns the bytes needed */
 size_t w2rap_step5_profile(char* buf, size_t len);
 

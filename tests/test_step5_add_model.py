@@ -1,0 +1,60 @@
+"""The yardstick of AddNewStuff on the CPU: step5_add_model (a restatement of BuildAll, TranslatePaths and ExtendPath, its graph from
+oracle3.run) against recorded runs of the reference's own builder on `allx` (tests/golden/refruns/step5_add_<case>/) and against the
+literal outcomes of the hand-made cases.  No reference binary reaches TranslatePaths or ExtendPath alone: those two rest on the model,
+the model on the literals."""
+import numpy as np
+import pytest
+
+import step5_add_cases as T
+import step5_add_model as M
+from w2rap_contigger_amd import formats as F, hbvtool
+
+
+def run_model(name, **kw):
+    c = T.get(name)
+    return M.add_new_stuff(*c.inputs(), min_gain=c.min_gain, **kw)
+
+
+@pytest.mark.parametrize("name", sorted(T.cases()))
+def test_model_gives_the_literal_outcomes(name):
+    m = run_model(name)
+    T.get(name).check(m)
+    assert sum(m.counters[k] for k in ("n_tr_empty", "n_tr_first", "n_tr_walked", "n_tr_cleared")) == len(m.path_offset)
+
+
+@pytest.mark.parametrize("name", T.RECORDED)
+def test_builder_model_equals_the_recorded_reference(name, tmp_path):
+    """oracle3.run on the encoding, the recorded edge order replayed: the graph and every old edge's path and first skip are the record's"""
+    B, hint = T.recorded_rebuilt(name, str(tmp_path))
+    c = T.get(name)
+    mine = M.rebuild(c.h, c.new, hint)
+    assert F.hbv_to_bytes(mine.hbv, zero_padding=True) == F.hbv_to_bytes(B.hbv, zero_padding=True)
+    assert np.array_equal(mine.inv, B.inv)
+    assert mine.to3 == B.to3 and mine.left3 == B.left3 and mine.n_unipaths == B.n_unipaths
+    # and the whole call on the recorded graph gives what it gives on the model's own, up to the numbering
+    a = M.add_new_stuff(*c.inputs(), min_gain=c.min_gain, rebuilt=B)
+    b = run_model(name)
+    c.check(a)
+    _, pa, _ = hbvtool.canonicalise(a.hbv, (a.path_offset, a.path_off, a.path_edges))
+    _, pb, _ = hbvtool.canonicalise(b.hbv, (b.path_offset, b.path_off, b.path_edges))
+    assert all(np.array_equal(x, y) for x, y in zip(pa, pb))
+    assert a.counters == b.counters
+
+
+@pytest.mark.parametrize("seed", T.SEEDS)
+def test_generated_cases_reach_every_counter(seed):
+    c = T.get(f"random_{seed}")
+    h, paths, reads, quals, new = c.inputs()
+    assert 2800 <= sum(int(x) for x in h.edge_len) // 2 and len(reads[2]) == 400 and set(int(x) for x in reads[2]) == {150}
+    m = run_model(f"random_{seed}")
+    print(seed, h.n_edges, m.counters)
+    assert T.seed_conditions(m) == []
+
+
+def test_overlap_append_takes_the_longest_overlap():
+    v = [1, 2, 3, 2, 3]
+    assert M.overlap_append(v, [2, 3, 2, 3, 9]) == 4 and v == [1, 2, 3, 2, 3, 9]
+    v = [1, 2]
+    assert M.overlap_append(v, [3]) == 0 and v == [1, 2, 3]
+    v = []
+    assert M.overlap_append(v, [5, 6]) == 0 and v == [5, 6]

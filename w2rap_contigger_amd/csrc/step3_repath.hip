@@ -25,6 +25,8 @@
 //    tile-local splitters), circles by min-jumping over K2-mer contents;
 //  * everything that depends on the (arbitrary) edge numbering comes after one small sort of the unipath heads, so the
 //    canonical and the replayed order share every kernel.
+// Everything behind the `all` stage -- buildBigKHBVFromReads on a stream of sequences -- is step3_back / step3_through / step3_pack
+// (step3_back.h): step3() calls them on the unique places, AddNewStuff (step5_add.hip) on its allx.
 // The oracle (oracle/step3_oracle.cc) is the checker in tests/ only; nothing here calls it.
 #include <algorithm>
 #include <chrono>
@@ -34,6 +36,7 @@
 #include <vector>
 #include "ctx.h"
 #include "../../include/w2rap_step3.h"
+#include "step3_back.h"
 
 extern "C" w2rap_step2_ctx* w2rap_step2_create(int device, char* err, size_t errlen);
 extern "C" void w2rap_step2_destroy(w2rap_step2_ctx*);
@@ -1442,6 +1445,377 @@ int dict_by_partition(Ctx& c, uint64_t N2 /* pairs */, const KGeom& q, const uin
     return 0;
 }
 
+
+}  // namespace
+
+// ============================================================================= the back half (step3_back.h): shared with AddNewStuff (step5_add.hip)
+int step3_check(Ctx& c, const uint32_t* d_flags, uint32_t h_flags[4]) {
+    W2_HIP(hipMemcpyAsync(h_flags, d_flags, 16, hipMemcpyDeviceToHost, c.stream));
+    W2_HIP(hipStreamSynchronize(c.stream));
+    const uint32_t f = h_flags[1];
+    if (f & 1) { c.err = "Involution: an edge object has no reverse complement in the graph (HyperBasevector.cc:648-660 needs every edge's RC)"; return W2RAP_E_GRAPH; }
+    if (f & 2) { c.err = "Involution: the objects of the small-K graph do not pair up with their reverse complements"; return W2RAP_E_GRAPH; }
+    if (f & 4) { c.err = "places: two different paths under one 128-bit key"; return W2RAP_E_LIMIT; }
+    if (f & 8) { c.err = "a place longer than 2^31 bases"; return W2RAP_E_LIMIT; }
+    if (f & 16) { c.err = "edge_order_hint: a hinted edge is not a unipath of this graph"; return W2RAP_E_HINT; }
+    if (f & 32) { c.err = "edge_order_hint: an edge is listed twice"; return W2RAP_E_HINT; }
+    if (f & 64) { c.err = "edge_order_hint: a hinted edge has the wrong length"; return W2RAP_E_HINT; }
+    if (f & 128) { c.err = "K2-mer left without an edge (BigKPather.cc:303)"; return W2RAP_E_GRAPH; }
+    if (f & 256) { c.err = "extra_path_edges names an edge object that does not exist"; return W2RAP_E_ARG; }
+    if (f & 512) { c.err = "extend_paths: vleft / vright name a vertex that does not exist"; return W2RAP_E_ARG; }
+    return 0;
+}
+
+int step3_block_index(Ctx& c, const uint64_t* a, uint64_t n, uint64_t total, uint32_t** out) { return block_index(c, a, n, total, out); }
+
+// dictionary, unipaths, objects, vertices, adjacency of the sequences of a stream (buildBigKHBVFromReads behind the kmerizer's input)
+int step3_back(Ctx& c, unsigned K2, const Stream3& S3, const Lone3* lone_in, const w2rap_edge_hint* hint_in, uint32_t* d_flags, unsigned long long* d_cnt, Back3& B) {
+    hipStream_t st = c.stream;
+    unsigned sbits = SORT_BITS;
+    if (test_hook("W2RAP_TEST_SORT_BITS")) { const int v = atoi(getenv("W2RAP_TEST_SORT_BITS")); if (v >= 1 && v <= 63) sbits = (unsigned)v; }    // results do not depend on it
+    const KGeom q{K2, (K2 + 31) / 32, K2 - 32 * ((K2 + 31) / 32 - 1), sbits};
+    const uint64_t U = S3.U, N2 = S3.N2;
+    const uint64_t* all = S3.all; const uint64_t *woff = S3.woff, *koff = S3.koff; const uint32_t* nbases = S3.nbases; const uint32_t* kblk = S3.kblk;
+    const uint8_t* allb = reinterpret_cast<const uint8_t*>(all);
+    const uint64_t NO = lone_in ? lone_in->NO : 0;
+    const uint64_t* voff = lone_in ? lone_in->voff : nullptr; const int32_t* pvec = lone_in ? lone_in->pvec : nullptr; const int32_t* inv = lone_in ? lone_in->inv : nullptr;
+    uint32_t h_flags[4] = {0, 0, 0, 0};
+    auto check = [&]() -> int { return step3_check(c, d_flags, h_flags); };
+    // ---------------------------------------------------------------- dictionary
+    Timer t_dict(st);
+    uint64_t* key = nullptr; uint32_t* val = nullptr; uint16_t* meta = nullptr;
+    W2_ALLOC(key, uint64_t, N2 + 1); W2_ALLOC(val, uint32_t, N2 + 1); W2_ALLOC(meta, uint16_t, N2 + 2);
+    uint64_t* gpos = nullptr; W2_ALLOC(gpos, uint64_t, N2 + 1);
+    // the replay of a given edge order looks its edges up in the hash-ORDERED list of the distinct K2-mers: the sorted form
+    bool sorted_dict = hint_in != nullptr || getenv("W2RAP_STEP3_SORT_DICT") != nullptr;
+    uint32_t *grp_rep, *ctx_by_x; uint64_t* pid;
+    W2_ALLOC(grp_rep, uint32_t, N2 + 1); W2_ALLOC(ctx_by_x, uint32_t, N2 + 1); W2_ALLOC(pid, uint64_t, N2 + 2);
+    // the K2-mers strictly inside a one-edge place whose edge no longer place shares stay out of the dictionary (k3_lone_places)
+    const bool lone_on = !sorted_dict && N2 && lone_in && !getenv("W2RAP_STEP3_NO_LONE");
+    uint8_t* lone = nullptr; unsigned long long n_pairs = N2;
+    if (lone_on) {
+        uint8_t* shared_edge = nullptr; unsigned long long* d_np = nullptr;
+        W2_ALLOC(shared_edge, uint8_t, NO + 1); W2_ALLOC(lone, uint8_t, U + 1); W2_ALLOC(d_np, unsigned long long, 1);
+        W2_HIP(hipMemsetAsync(shared_edge, 0, NO + 1, st)); W2_HIP(hipMemsetAsync(d_np, 0, 8, st));
+        LAUNCH(c, "k3_mid_edges", k3_mid_edges, dim3(grid_for(std::max<uint64_t>(U, NO))), dim3(256), 0, U, NO, voff, pvec, inv, shared_edge);
+        LAUNCH(c, "k3_lone_places", k3_lone_places, dim3(grid_for(U)), dim3(256), 0, U, voff, pvec, shared_edge, lone);
+        LAUNCH(c, "k3_kmer_keys", k3_kmer_keys, dim3((unsigned)((N2 + 256 * KK_PER - 1) / (256 * KK_PER))), dim3(256), 0, N2, U, q, koff, woff, nbases, (const uint64_t*)all, key, val, meta, gpos, grp_rep, ctx_by_x,
+               (const uint8_t*)lone, d_np, (const uint32_t*)kblk);
+        W2_HIP(hipMemcpyAsync(&n_pairs, d_np, 8, hipMemcpyDeviceToHost, st));
+        W2_HIP(hipStreamSynchronize(st));
+        c.release(shared_edge); c.release(d_np);
+        if (getenv("W2RAP_TRACE")) fprintf(stderr, "[w2rap] step 3 dictionary: %llu of %llu occurrences lie strictly inside an edge no longer place shares\n",
+                                           (unsigned long long)(N2 - n_pairs), (unsigned long long)N2);
+    }
+    else if (N2) LAUNCH(c, "k3_kmer_keys", k3_kmer_keys, dim3((unsigned)((N2 + 256 * KK_PER - 1) / (256 * KK_PER))), dim3(256), 0, N2, U, q, koff, woff, nbases, (const uint64_t*)all, key, sorted_dict ? val : (uint32_t*)nullptr, meta, gpos,
+                        grp_rep, ctx_by_x, (const uint8_t*)nullptr, (unsigned long long*)nullptr, (const uint32_t*)kblk);
+    uint32_t *ghead = nullptr, *gcoll = nullptr, *gover = nullptr, *hidx = nullptr;
+    unsigned long long ncoll = 0;
+    if (!sorted_dict && N2) {
+        bool overflow = false;
+        if (n_pairs) W2_TRY(dict_by_partition(c, n_pairs, q, key, lone_on ? val : (const uint32_t*)nullptr, allb, gpos, meta, grp_rep, ctx_by_x, overflow, N2));
+        if (overflow) {
+            if (getenv("W2RAP_TRACE")) fprintf(stderr, "[w2rap] step 3 dictionary: a hash partition overflowed, sorting instead\n");
+            sorted_dict = true;
+            // (the sorted form wants the key of EVERY occurrence in position order)
+            if (lone_on) LAUNCH(c, "k3_kmer_keys", k3_kmer_keys, dim3((unsigned)((N2 + 256 * KK_PER - 1) / (256 * KK_PER))), dim3(256), 0, N2, U, q, koff, woff, nbases, (const uint64_t*)all, key, val, meta, gpos, grp_rep, ctx_by_x,
+                                (const uint8_t*)nullptr, (unsigned long long*)nullptr, (const uint32_t*)kblk);
+            else LAUNCH(c, "k3_iota", k3_iota, dim3(grid_for(N2)), dim3(256), 0, N2, val);
+        }
+    }
+    if (lone) c.release(lone);
+    if (sorted_dict) {
+        W2_TRY(sort_pairs_u64(c, key, val, N2, 0, (int)q.sbits));
+        W2_ALLOC(ghead, uint32_t, N2 + 1); W2_ALLOC(gcoll, uint32_t, N2 + 1); W2_ALLOC(hidx, uint32_t, N2 + 1);
+        if (N2) LAUNCH(c, "k3_group", k3_group, dim3(grid_for(N2)), dim3(256), 0, N2, U, q, key, val, meta, gpos, allb, ghead, gcoll, d_cnt + 103);
+        W2_HIP(hipMemcpyAsync(&ncoll, d_cnt + 103, 8, hipMemcpyDeviceToHost, st));
+        W2_HIP(hipStreamSynchronize(st));
+        if (ncoll) {
+            W2_ALLOC(gover, uint32_t, N2 + 1);
+            W2_HIP(hipMemsetAsync(gover, 0xFF, (N2 + 1) * 4, st));
+            LAUNCH(c, "k3_group_fix", k3_group_fix, dim3(grid_for(N2)), dim3(256), 0, N2, U, q, key, val, meta, gpos, allb, gcoll, ghead, gover);
+        }
+        W2_TRY(inclusive_max_scan_u32(c, ghead, hidx, N2));
+        if (getenv("W2RAP_TRACE") && N2 && N2 < (1u << 22)) {
+            std::vector<uint32_t> hh(N2), hx(N2); std::vector<uint64_t> hk(N2);
+            W2_HIP(hipMemcpy(hh.data(), ghead, N2 * 4, hipMemcpyDeviceToHost)); W2_HIP(hipMemcpy(hx.data(), hidx, N2 * 4, hipMemcpyDeviceToHost));
+            W2_HIP(hipMemcpy(hk.data(), key, N2 * 8, hipMemcpyDeviceToHost));
+            uint64_t nheads = 0, badscan = 0, unsorted = 0; uint32_t m = 0;
+            for (uint64_t j = 0; j < N2; ++j) { if (hh[j]) ++nheads; m = std::max(m, hh[j]); if (hx[j] != m) ++badscan; if (j && (hk[j] & sort_mask(q.sbits)) < (hk[j - 1] & sort_mask(q.sbits))) ++unsorted; }
+            fprintf(stderr, "[w2rap]   group heads %llu, max-scan mismatches %llu, sort-key inversions %llu\n", (unsigned long long)nheads, (unsigned long long)badscan, (unsigned long long)unsorted);
+        }
+        if (N2) {
+            LAUNCH(c, "k3_rep_init", k3_rep_init, dim3(grid_for(N2)), dim3(256), 0, N2, meta, grp_rep, ctx_by_x);
+            LAUNCH(c, "k3_scatter_rep", k3_scatter_rep, dim3(grid_for(N2)), dim3(256), 0, N2, ghead, hidx, (const uint32_t*)gover, val, meta, grp_rep, ctx_by_x);
+        }
+    }
+    W2_TRY(exclusive_scan_is_self(c, grp_rep, pid, N2));          // (the flags "is its own representative" scanned without being written)
+    uint64_t D = 0;
+    W2_HIP(hipMemcpy(&D, pid + N2, 8, hipMemcpyDeviceToHost));
+    if (2 * D >= (1ull << 32) - 2) { c.err = "more than 2^31 distinct K2-mers on one GPU (32-bit node ids)"; return W2RAP_E_LIMIT; }
+    uint32_t *id_of, *krep, *dctx; uint64_t* dhash = nullptr; uint32_t* did = nullptr;
+    W2_ALLOC(id_of, uint32_t, N2 + 1); W2_ALLOC(krep, uint32_t, D + 1); W2_ALLOC(dctx, uint32_t, D + 1);
+    if (N2) LAUNCH(c, "k3_finish_ids", k3_finish_ids, dim3(grid_for(N2)), dim3(256), 0, N2, grp_rep, pid, ctx_by_x, id_of, krep, dctx);
+    if (hint_in && N2) {                   // replay: the sorted (hash, id) list of the distinct K2-mers
+        uint32_t* hf = hidx; uint64_t* hex = pid;    // (reused)
+        W2_ALLOC(dhash, uint64_t, D + 1); W2_ALLOC(did, uint32_t, D + 1);
+        LAUNCH(c, "k3_nonzero", k3_nonzero, dim3(grid_for(N2)), dim3(256), 0, N2, ghead, hf);
+        W2_TRY(exclusive_scan_u32_to_u64(c, hf, hex, N2));
+        LAUNCH(c, "k3_head_list", k3_head_list, dim3(grid_for(N2)), dim3(256), 0, N2, ghead, hex, key, val, id_of, dhash, did);
+    }
+    W2_HIP(hipStreamSynchronize(st));
+    for (void* p : {(void*)key, (void*)val, (void*)ghead, (void*)gcoll, (void*)hidx, (void*)grp_rep, (void*)ctx_by_x, (void*)pid, (void*)gover})
+        if (p) c.release(p);
+    if (getenv("W2RAP_TRACE")) {
+        fprintf(stderr, "[w2rap] step 3 dictionary: %llu occurrences, %llu distinct, %llu neighbours with one sort key but different content\n",
+                (unsigned long long)N2, (unsigned long long)D, ncoll);
+        if (N2 && N2 < (1u << 22)) {                     // small inputs: consistency of the id arrays
+            std::vector<uint32_t> hid(N2), hrep(D), hctx(D);
+            W2_HIP(hipMemcpy(hid.data(), id_of, N2 * 4, hipMemcpyDeviceToHost)); W2_HIP(hipMemcpy(hrep.data(), krep, D * 4, hipMemcpyDeviceToHost));
+            W2_HIP(hipMemcpy(hctx.data(), dctx, D * 4, hipMemcpyDeviceToHost));
+            uint64_t bad_id = 0, bad_rep = 0, zero_ctx = 0;
+            for (uint64_t x = 0; x < N2; ++x) if (hid[x] >= D) ++bad_id;
+            for (uint64_t i = 0; i < D; ++i) { if (hrep[i] >= N2 || hid[hrep[i]] != i) ++bad_rep; if (!(hctx[i] & 0xFF)) ++zero_ctx; }
+            fprintf(stderr, "[w2rap]   ids out of range %llu, representatives inconsistent %llu, empty contexts %llu\n", (unsigned long long)bad_id,
+                    (unsigned long long)bad_rep, (unsigned long long)zero_ctx);
+        }
+    }
+    B.ms_dict = t_dict.stop();
+    // ---------------------------------------------------------------- unipaths
+    Timer t_graph(st);
+    const uint64_t N = 2 * D;
+    const KSrc S{allb, gpos, krep, meta, q};
+    uint32_t *nbr, *nxt0, *nxt, *rnk; unsigned long long* rankw; uint8_t *cyc, *mid, *is_head;
+    W2_ALLOC(nbr, uint32_t, N + 2); W2_ALLOC(nxt0, uint32_t, N + 2); W2_ALLOC(nxt, uint32_t, N + 2); W2_ALLOC(rnk, uint32_t, N + 2);
+    W2_ALLOC(rankw, unsigned long long, N + 2); W2_ALLOC(cyc, uint8_t, N + 2); W2_ALLOC(mid, uint8_t, N + 2); W2_ALLOC(is_head, uint8_t, N + 2);
+    W2_HIP(hipMemsetAsync(nbr, 0xFF, (N + 2) * 4, st));
+    W2_HIP(hipMemsetAsync(d_flags, 0, 32, st));
+    if (D) {
+        if (N2 > 1) LAUNCH(c, "k3_nbr", k3_nbr, dim3(grid_for(N2)), dim3(256), 0, N2, U, koff, id_of, meta, nbr, (const uint32_t*)kblk);
+        LAUNCH(c, "k3_links", k3_links, dim3(grid_for(D)), dim3(256), 0, D, dctx, nbr, nxt0);
+        W2_TRY(run_ranking(c, N, nxt0, nxt, rnk, rankw, cyc, mid, d_flags, nullptr, nullptr, false));
+        W2_TRY(check());
+        if (h_flags[2]) {                            // smooth circles
+            uint32_t *nx, *mn, *nx2, *mn2;
+            W2_ALLOC(nx, uint32_t, N); W2_ALLOC(mn, uint32_t, N); W2_ALLOC(nx2, uint32_t, N); W2_ALLOC(mn2, uint32_t, N);
+            LAUNCH(c, "k3_minjump_init", k3_minjump_init, dim3(grid_for(N)), dim3(256), 0, N, nxt0, cyc, nx, mn);
+            for (int round = 0; round < 33; ++round) {
+                LAUNCH(c, "k3_minjump", k3_minjump, dim3(grid_for(N)), dim3(256), 0, N, S, nx, mn, nx2, mn2);
+                std::swap(nx, nx2); std::swap(mn, mn2);
+            }
+            LAUNCH(c, "k3_cycle_cut", k3_cycle_cut, dim3(grid_for(D)), dim3(256), 0, D, cyc, mn, nxt0);
+            W2_HIP(hipStreamSynchronize(st));
+            c.release(nx); c.release(mn); c.release(nx2); c.release(mn2);
+            W2_HIP(hipMemsetAsync(d_flags, 0, 32, st));
+            W2_TRY(run_ranking(c, N, nxt0, nxt, rnk, rankw, cyc, mid, d_flags, nullptr, nullptr, false));
+            W2_TRY(check());
+            if (h_flags[2]) { c.err = "failed to close circle (BigKPather.cc:141)"; return W2RAP_E_GRAPH; }
+        }
+        W2_HIP(hipMemsetAsync(mid, 0, N, st));
+        LAUNCH(c, "k3_mid", k3_mid, dim3(grid_for(D)), dim3(256), 0, D, S, nxt, rnk, mid);
+    }
+    const uint64_t head_cap = D ? c.rank_ends + 1 : 1;
+    uint32_t* head_v = nullptr;
+    W2_ALLOC(head_v, uint32_t, head_cap + 1);
+    if (N) {
+        uint32_t* cand = nullptr;
+        W2_ALLOC(cand, uint32_t, head_cap + 1);
+        LAUNCH(c, "k3_head_cands", k3_head_cands, dim3((unsigned)((N + 256 * HC_PER - 1) / (256 * HC_PER))), dim3(256), 0, N, nxt0, is_head, cand, d_cnt + 101, head_cap);
+        LAUNCH(c, "k3_heads", k3_heads, dim3(grid_for(head_cap)), dim3(256), 0, (const unsigned long long*)(d_cnt + 101), head_cap, (const uint32_t*)cand, S, dctx, nxt, rnk, mid, is_head,
+               head_v, d_cnt + 102);
+        c.release(cand);
+    }
+    unsigned long long E = 0;
+    W2_HIP(hipMemcpyAsync(&E, d_cnt + 102, 8, hipMemcpyDeviceToHost, st));
+    W2_HIP(hipStreamSynchronize(st));
+    if (E > head_cap) { c.err = "more canonical heads than chain ends"; return W2RAP_E_GRAPH; }
+    uint32_t *perm, *head_edge, *edge_head, *edge_nk; uint64_t* wtmp;
+    W2_ALLOC(perm, uint32_t, E + 1); W2_ALLOC(head_edge, uint32_t, N + 2); W2_ALLOC(edge_head, uint32_t, E + 1); W2_ALLOC(edge_nk, uint32_t, E + 1); W2_ALLOC(wtmp, uint64_t, E + 1);
+    W2_HIP(hipMemsetAsync(head_edge, 0xFF, (N + 2) * 4, st));
+    const w2rap_edge_hint* hint = hint_in;
+    if (hint) {
+        if (hint->n_edges != E) { c.err = "edge_order_hint has " + std::to_string(hint->n_edges) + " edges, the graph has " + std::to_string(E); return W2RAP_E_HINT; }
+        for (uint64_t e = 0; e < E; ++e) {
+            if (hint->len[e] < K2) { c.err = "edge_order_hint: edge shorter than K2"; return W2RAP_E_HINT; }
+            if (hint->byte_off[e + 1] < hint->byte_off[e] || hint->byte_off[e + 1] - hint->byte_off[e] != ((uint64_t)hint->len[e] + 3) / 4) {
+                c.err = "edge_order_hint: byte_off does not match len"; return W2RAP_E_HINT;
+            }
+        }
+        uint8_t* hbits = nullptr; uint64_t *hbyte = nullptr, *hbase0 = nullptr; uint32_t* hlen = nullptr;
+        W2_TRY(up_pooled(c, &hbits, hint->packed, E ? hint->byte_off[E] : 0, 32));
+        W2_TRY(up_pooled(c, &hbyte, hint->byte_off, E + 1));
+        W2_TRY(up_pooled(c, &hlen, hint->len, E));
+        W2_ALLOC(hbase0, uint64_t, E + 1);
+        LAUNCH(c, "k3_mul4", k3_mul4, dim3(grid_for(E + 1)), dim3(256), 0, E + 1, hbyte, hbase0);
+        if (E) LAUNCH(c, "k3_edge_from_hint", k3_edge_from_hint, dim3(grid_for(E)), dim3(256), 0, E, D, S, hbits, hbase0, hlen, dhash, did, is_head, rnk, head_edge, edge_head, edge_nk, d_flags);
+        W2_TRY(check());
+        for (void* p : {(void*)hbits, (void*)hbyte, (void*)hlen, (void*)hbase0}) c.release(p);
+    } else if (E) {
+        // canonical order: the unipaths by their sequences = by their first K2-mers (distinct), NW words, least significant first
+        // ONE sort by the first word, then the (short) runs of equal first words ordered by full comparison; NW sorts, least significant
+        // word first, only if a run is too long for that
+        bool by_words = test_hook("W2RAP_TEST_STEP3_FULL_SORTS");
+        unsigned max_run = 64;
+        if (test_hook("W2RAP_TEST_TIE_RUN")) max_run = (unsigned)atoi(getenv("W2RAP_TEST_TIE_RUN"));
+        LAUNCH(c, "k3_iota", k3_iota, dim3(grid_for(E)), dim3(256), 0, E, perm);
+        if (!by_words) {
+            LAUNCH(c, "k3_head_word", k3_head_word, dim3(grid_for(E)), dim3(256), 0, E, S, head_v, perm, 0u, wtmp);
+            W2_TRY(sort_pairs_u64(c, wtmp, perm, E, 0, 64));
+            W2_HIP(hipMemsetAsync(d_flags + 6, 0, 4, st));
+            LAUNCH(c, "k3_edge_tie_sort", k3_edge_tie_sort, dim3(grid_for(E)), dim3(256), 0, E, S, head_v, wtmp, perm, max_run, d_flags);
+            uint32_t long_run = 0;
+            W2_HIP(hipMemcpyAsync(&long_run, d_flags + 6, 4, hipMemcpyDeviceToHost, st));
+            W2_HIP(hipStreamSynchronize(st));
+            if (long_run) { by_words = true; LAUNCH(c, "k3_iota", k3_iota, dim3(grid_for(E)), dim3(256), 0, E, perm); }
+        }
+        if (by_words)
+            W2_TRY(sort_by_words(c, perm, E, q.NW, wtmp, [&](unsigned j, uint64_t* tmp) -> int {
+                LAUNCH(c, "k3_head_word", k3_head_word, dim3(grid_for(E)), dim3(256), 0, E, S, head_v, perm, j, tmp);
+                return 0; }));
+        LAUNCH(c, "k3_edge_from_sorted", k3_edge_from_sorted, dim3(grid_for(E)), dim3(256), 0, E, perm, head_v, rnk, head_edge, edge_head, edge_nk);
+    }
+    // ---- edge sequences, K2-mer placements
+    uint32_t* elen = nullptr; uint64_t* edge_off = nullptr;
+    W2_ALLOC(elen, uint32_t, E + 1); W2_ALLOC(edge_off, uint64_t, E + 2);
+    if (E) LAUNCH(c, "k3_edge_len", k3_edge_len, dim3(grid_for(E)), dim3(256), 0, E, K2, edge_nk, elen);
+    W2_TRY(exclusive_scan_u32_to_u64(c, elen, edge_off, E));
+    uint64_t edge_bases = 0;
+    W2_HIP(hipMemcpy(&edge_bases, edge_off + E, 8, hipMemcpyDeviceToHost));
+    uint8_t* codes = nullptr; uint32_t *k_edge, *k_off;
+    W2_ALLOC(codes, uint8_t, edge_bases + 64); W2_ALLOC(k_edge, uint32_t, D + 1); W2_ALLOC(k_off, uint32_t, D + 1);
+    if (D) LAUNCH(c, "k3_assign", k3_assign, dim3(grid_for(D)), dim3(256), 0, D, S, nxt, rnk, head_edge, edge_off, k_edge, k_off, codes, d_flags);
+    W2_TRY(check());
+    // ---- objects, vertices, adjacency
+    uint32_t* nobj = nullptr; uint64_t* ooff = nullptr;
+    W2_ALLOC(nobj, uint32_t, E + 1); W2_ALLOC(ooff, uint64_t, E + 2);
+    if (E) LAUNCH(c, "k3_edge_nobj", k3_edge_nobj, dim3(grid_for(E)), dim3(256), 0, E, edge_head, edge_nk, dctx, nobj);
+    W2_TRY(exclusive_scan_u32_to_u64(c, nobj, ooff, E));
+    uint64_t NO2 = 0;
+    W2_HIP(hipMemcpy(&NO2, ooff + E, 8, hipMemcpyDeviceToHost));
+    int32_t *fwdX, *revX, *inv2, *left, *right; uint32_t* obj_edge;
+    W2_ALLOC(fwdX, int32_t, E + 1); W2_ALLOC(revX, int32_t, E + 1); W2_ALLOC(inv2, int32_t, NO2 + 1); W2_ALLOC(obj_edge, uint32_t, NO2 + 1);
+    W2_ALLOC(left, int32_t, NO2 + 1); W2_ALLOC(right, int32_t, NO2 + 1);
+    if (E) LAUNCH(c, "k3_edge_xlat", k3_edge_xlat, dim3(grid_for(E)), dim3(256), 0, E, nobj, ooff, fwdX, revX, obj_edge, inv2);
+    uint64_t NV = 0;
+    const uint64_t nends = 2 * NO2;
+    if (nends) {
+        uint64_t *ehash, *etmp, *eex; uint32_t *eperm, *eflag;
+        W2_ALLOC(ehash, uint64_t, nends); W2_ALLOC(etmp, uint64_t, nends); W2_ALLOC(eex, uint64_t, nends + 1); W2_ALLOC(eperm, uint32_t, nends); W2_ALLOC(eflag, uint32_t, nends);
+        LAUNCH(c, "k3_end_hash", k3_end_hash, dim3(grid_for(nends)), dim3(256), 0, NO2, K2, obj_edge, edge_off, edge_nk, codes, ehash);
+        LAUNCH(c, "k3_iota", k3_iota, dim3(grid_for(nends)), dim3(256), 0, nends, eperm);
+        const unsigned EW = (K2 - 1 + 31) / 32;
+        uint64_t* ewords = nullptr;
+        W2_ALLOC(ewords, uint64_t, (uint64_t)EW * nends);
+        LAUNCH(c, "k3_end_words", k3_end_words, dim3(grid_for(nends)), dim3(256), 0, nends, K2, EW, obj_edge, edge_off, edge_nk, codes, ewords);
+        // ONE sort by the hash, boundaries where it changes, equal hashes verified by content (k3_end_group); by (hash, sequence) -- LSD over
+        // the sequence words, then the hash -- only if two contents share a hash.  Same vertex numbers either way: the groups are ordered by hash.
+        bool by_words = test_hook("W2RAP_TEST_STEP3_FULL_SORTS");
+        const bool pretend = test_hook("W2RAP_TEST_ENDS_COLLISION");
+        for (;;) {
+            if (by_words)
+                W2_TRY(sort_by_words(c, eperm, nends, EW, etmp, [&](unsigned j, uint64_t* tmp) -> int {
+                    LAUNCH(c, "k3_gather_u64", k3_gather_u64, dim3(grid_for(nends)), dim3(256), 0, nends, ewords + (uint64_t)j * nends, eperm, tmp);
+                    return 0; }));
+            LAUNCH(c, "k3_gather_u64", k3_gather_u64, dim3(grid_for(nends)), dim3(256), 0, nends, ehash, eperm, etmp);
+            W2_TRY(sort_pairs_u64(c, etmp, eperm, nends, 0, 64));
+            if (by_words) {
+                // vertex boundaries: the hash or any sequence word differs from the predecessor's
+                LAUNCH(c, "k3_end_differs", k3_end_differs, dim3(grid_for(nends)), dim3(256), 0, nends, etmp, eflag, true);
+                for (unsigned j = 0; j < EW; ++j) {
+                    LAUNCH(c, "k3_gather_u64", k3_gather_u64, dim3(grid_for(nends)), dim3(256), 0, nends, ewords + (uint64_t)j * nends, eperm, etmp);
+                    LAUNCH(c, "k3_end_differs", k3_end_differs, dim3(grid_for(nends)), dim3(256), 0, nends, etmp, eflag, false);
+                }
+            } else {
+                W2_HIP(hipMemsetAsync(d_flags + 7, 0, 4, st));
+                LAUNCH(c, "k3_end_group", k3_end_group, dim3(grid_for(nends)), dim3(256), 0, nends, EW, etmp, eperm, ewords, eflag, d_flags, pretend);
+            }
+            W2_TRY(exclusive_scan_u32_to_u64(c, eflag, eex, nends));
+            uint32_t shared_hash = 0;
+            if (!by_words) W2_HIP(hipMemcpyAsync(&shared_hash, d_flags + 7, 4, hipMemcpyDeviceToHost, st));
+            W2_HIP(hipMemcpy(&NV, eex + nends, 8, hipMemcpyDeviceToHost));
+            W2_HIP(hipStreamSynchronize(st));
+            if (shared_hash && !by_words) { by_words = true; LAUNCH(c, "k3_iota", k3_iota, dim3(grid_for(nends)), dim3(256), 0, nends, eperm); continue; }
+            break;
+        }
+        c.release(ewords);
+        NV += 1;
+        LAUNCH(c, "k3_end_vertices", k3_end_vertices, dim3(grid_for(nends)), dim3(256), 0, nends, eperm, eflag, eex, left, right);
+        W2_HIP(hipStreamSynchronize(st));
+        for (void* p : {(void*)ehash, (void*)etmp, (void*)eex, (void*)eperm, (void*)eflag}) c.release(p);
+    }
+    uint64_t *from_off, *to_off; int32_t *from_v, *from_e, *to_v, *to_e;
+    W2_ALLOC(from_off, uint64_t, NV + 2); W2_ALLOC(to_off, uint64_t, NV + 2);
+    W2_ALLOC(from_v, int32_t, NO2 + 1); W2_ALLOC(from_e, int32_t, NO2 + 1); W2_ALLOC(to_v, int32_t, NO2 + 1); W2_ALLOC(to_e, int32_t, NO2 + 1);
+    {
+        uint64_t* akeys = nullptr; uint32_t *avals = nullptr, *deg = nullptr;
+        W2_ALLOC(akeys, uint64_t, NO2 + 1); W2_ALLOC(avals, uint32_t, NO2 + 1); W2_ALLOC(deg, uint32_t, NV + 1);
+        for (int dir = 0; dir < 2; ++dir) {          // AddEdge keeps from_[v] sorted by target with ties in insertion (= object id) order: stable sort by (v, w)
+            W2_HIP(hipMemsetAsync(deg, 0, (NV + 1) * 4, st));
+            if (NO2) {
+                LAUNCH(c, "k3_adj_keys", k3_adj_keys, dim3(grid_for(NO2)), dim3(256), 0, NO2, dir ? right : left, dir ? left : right, akeys, avals, deg);
+                W2_TRY(sort_pairs_u64(c, akeys, avals, NO2, 0, 64));
+                LAUNCH(c, "k3_adj_out", k3_adj_out, dim3(grid_for(NO2)), dim3(256), 0, NO2, avals, dir ? left : right, dir ? to_v : from_v, dir ? to_e : from_e);
+            }
+            W2_TRY(exclusive_scan_u32_to_u64(c, deg, dir ? to_off : from_off, NV));
+        }
+        c.release(akeys); c.release(avals); c.release(deg);
+    }
+    B.ms_graph = t_graph.stop();
+    B.D = D; B.E = E; B.NO2 = NO2; B.NV = NV;
+    B.id_of = id_of; B.meta = meta; B.k_edge = k_edge; B.k_off = k_off; B.edge_nk = edge_nk; B.edge_off = edge_off; B.codes = codes;
+    B.fwdX = fwdX; B.revX = revX; B.inv2 = inv2; B.obj_edge = obj_edge; B.left = left; B.right = right;
+    B.from_off = from_off; B.from_v = from_v; B.from_e = from_e; B.to_off = to_off; B.to_v = to_v; B.to_e = to_e;
+    return 0;
+}
+
+// every sequence's path through the graph (Pather :321-357): ipath[oex[koff[u]] .. oex[koff[u + 1]]) and, for a sequence with a K2-mer,
+// ioff[u], starts[u] (the first K2-mer's offset on its edge: the path's first skip) and stops[u]
+int step3_through(Ctx& c, const Stream3& S3, Back3& B) {
+    hipStream_t st = c.stream;
+    const uint64_t U = S3.U, N2 = S3.N2;
+    uint32_t* ostart = nullptr; int32_t *oobj, *starts, *stops; uint64_t* oex;
+    W2_ALLOC(ostart, uint32_t, N2 + 1); W2_ALLOC(oobj, int32_t, N2 + 1); W2_ALLOC(oex, uint64_t, N2 + 2); W2_ALLOC(starts, int32_t, U + 1); W2_ALLOC(stops, int32_t, U + 1);
+    if (N2) LAUNCH(c, "k3_occ", k3_occ, dim3(grid_for(N2)), dim3(256), 0, N2, U, S3.koff, (const uint32_t*)B.id_of, (const uint16_t*)B.meta, (const uint32_t*)B.k_edge, (const uint32_t*)B.k_off,
+                   (const uint32_t*)B.edge_nk, (const int32_t*)B.fwdX, (const int32_t*)B.revX, ostart, oobj, starts, stops, S3.kblk);
+    W2_TRY(exclusive_scan_u32_to_u64(c, ostart, oex, N2));
+    uint64_t nip = 0;
+    W2_HIP(hipMemcpy(&nip, oex + N2, 8, hipMemcpyDeviceToHost));
+    int32_t* ipath = nullptr; uint64_t* ioff = nullptr;
+    W2_ALLOC(ipath, int32_t, nip + 1); W2_ALLOC(ioff, uint64_t, U + 2);
+    if (N2) LAUNCH(c, "k3_place_paths", k3_place_paths, dim3(grid_for(N2)), dim3(256), 0, N2, U, S3.koff, (const uint32_t*)ostart, (const uint64_t*)oex, (const int32_t*)oobj, ipath, ioff, S3.kblk);
+    B.nip = nip;                                                   // (the copy's source outlives this function: Back3 is the caller's)
+    W2_HIP(hipMemcpyAsync(ioff + U, &B.nip, 8, hipMemcpyHostToDevice, st));
+    B.oex = oex; B.ipath = ipath; B.ioff = ioff; B.starts = starts; B.stops = stops;
+    return 0;
+}
+
+// the edge objects packed four bases to a byte, 33 zeroed bytes of slack behind the last
+int step3_pack(Ctx& c, unsigned K2, Back3& B) {
+    hipStream_t st = c.stream;
+    const uint64_t NO2 = B.NO2;
+    uint32_t *d_olen = nullptr, *d_nby = nullptr; uint64_t* d_byoff = nullptr; uint8_t* d_packed = nullptr;
+    W2_ALLOC(d_olen, uint32_t, NO2 + 1); W2_ALLOC(d_nby, uint32_t, NO2 + 1); W2_ALLOC(d_byoff, uint64_t, NO2 + 2);
+    if (NO2) LAUNCH(c, "k3_obj_len", k3_obj_len, dim3(grid_for(NO2)), dim3(256), 0, NO2, K2, (const uint32_t*)B.obj_edge, (const uint32_t*)B.edge_nk, d_olen, d_nby);
+    W2_TRY(exclusive_scan_u32_to_u64(c, d_nby, d_byoff, NO2));
+    uint64_t total_bytes = 0;
+    W2_HIP(hipMemcpy(&total_bytes, d_byoff + NO2, 8, hipMemcpyDeviceToHost));
+    // 32 zeroed bytes of slack behind the last edge (for every caller: they cost nothing): Step 4's k4_walks and k4e_gather read past it,
+    // and with W2RAP_STEP3_KEEP_DEVICE this block becomes Graph4::ebits as it stands, without a copy
+    W2_ALLOC(d_packed, uint8_t, total_bytes + 33);
+    W2_HIP(hipMemsetAsync(d_packed + total_bytes, 0, 33, st));
+    if (total_bytes) {
+        uint32_t* bblk = nullptr;
+        W2_TRY(block_index(c, (const uint64_t*)d_byoff, NO2, total_bytes, &bblk));
+        LAUNCH(c, "k3_pack_objs", k3_pack_objs, dim3(grid_for(total_bytes)), dim3(256), 0, total_bytes, NO2, K2, (const uint64_t*)d_byoff, (const uint32_t*)B.obj_edge, (const uint32_t*)B.edge_nk,
+               (const uint64_t*)B.edge_off, (const uint8_t*)B.codes, d_packed, (const uint32_t*)bblk);
+        c.release(bblk);
+    }
+    B.olen = d_olen; B.byoff = d_byoff; B.packed = d_packed; B.total_bytes = total_bytes;
+    return 0;
+}
+
+namespace {
+
 // the small-K graph's edge objects and the read paths, on the device
 struct DevIn { unsigned K; uint64_t NO; const uint8_t* obits /* +32 readable bytes */; const uint64_t* obyte; const uint32_t* olen;
                uint64_t n; const int32_t* p_offset; const uint64_t* p_off; const int32_t* p_edges;
@@ -1451,30 +1825,12 @@ struct DevIn { unsigned K; uint64_t NO; const uint8_t* obits /* +32 readable byt
 int step3(Ctx& c, const DevIn& in, const w2rap_step3_params& P, w2rap_step3_out& out) {
     hipStream_t st = c.stream;
     const unsigned K = in.K, K2 = P.K2;
-    unsigned sbits = SORT_BITS;
-    if (test_hook("W2RAP_TEST_SORT_BITS")) { const int v = atoi(getenv("W2RAP_TEST_SORT_BITS")); if (v >= 1 && v <= 63) sbits = (unsigned)v; }    // results do not depend on it
-    const KGeom q{K2, (K2 + 31) / 32, K2 - 32 * ((K2 + 31) / 32 - 1), sbits};
     const uint64_t NO = in.NO, n = in.n;
     uint32_t* d_flags = nullptr;                   // [0] ranking "changed"  [1] error bits  [2] has cycles
     W2_ALLOC(d_flags, uint32_t, 8);
     W2_HIP(hipMemsetAsync(d_flags, 0, 32, st));
     uint32_t h_flags[4] = {0, 0, 0, 0};
-    auto check = [&]() -> int {
-        W2_HIP(hipMemcpyAsync(h_flags, d_flags, 16, hipMemcpyDeviceToHost, st));
-        W2_HIP(hipStreamSynchronize(st));
-        const uint32_t f = h_flags[1];
-        if (f & 1) { c.err = "Involution: an edge object has no reverse complement in the graph (HyperBasevector.cc:648-660 needs every edge's RC)"; return W2RAP_E_GRAPH; }
-        if (f & 2) { c.err = "Involution: the objects of the small-K graph do not pair up with their reverse complements"; return W2RAP_E_GRAPH; }
-        if (f & 4) { c.err = "places: two different paths under one 128-bit key"; return W2RAP_E_LIMIT; }
-        if (f & 8) { c.err = "a place longer than 2^31 bases"; return W2RAP_E_LIMIT; }
-        if (f & 16) { c.err = "edge_order_hint: a hinted edge is not a unipath of this graph"; return W2RAP_E_HINT; }
-        if (f & 32) { c.err = "edge_order_hint: an edge is listed twice"; return W2RAP_E_HINT; }
-        if (f & 64) { c.err = "edge_order_hint: a hinted edge has the wrong length"; return W2RAP_E_HINT; }
-        if (f & 128) { c.err = "K2-mer left without an edge (BigKPather.cc:303)"; return W2RAP_E_GRAPH; }
-        if (f & 256) { c.err = "extra_path_edges names an edge object that does not exist"; return W2RAP_E_ARG; }
-        if (f & 512) { c.err = "extend_paths: vleft / vright name a vertex that does not exist"; return W2RAP_E_ARG; }
-        return 0;
-    };
+    auto check = [&]() -> int { return step3_check(c, d_flags, h_flags); };
     // ---------------------------------------------------------------- inputs
     Timer t_places(st);
     const uint8_t* obits = in.obits; const uint64_t* obyte = in.obyte; const uint32_t* olen = in.olen;
@@ -1691,298 +2047,18 @@ int step3(Ctx& c, const DevIn& in, const w2rap_step3_params& P, w2rap_step3_out&
     W2_TRY(block_index(c, (const uint64_t*)koff, U, N2 ? N2 : 1, &kblk));
     const uint8_t* allb = reinterpret_cast<const uint8_t*>(all);
     out.ms_places = t_places.stop();
-    // ---------------------------------------------------------------- dictionary
-    Timer t_dict(st);
-    uint64_t* key = nullptr; uint32_t* val = nullptr; uint16_t* meta = nullptr;
-    W2_ALLOC(key, uint64_t, N2 + 1); W2_ALLOC(val, uint32_t, N2 + 1); W2_ALLOC(meta, uint16_t, N2 + 2);
-    uint64_t* gpos = nullptr; W2_ALLOC(gpos, uint64_t, N2 + 1);
-    // the replay of a given edge order looks its edges up in the hash-ORDERED list of the distinct K2-mers: the sorted form
-    bool sorted_dict = P.edge_order_hint != nullptr || getenv("W2RAP_STEP3_SORT_DICT") != nullptr;
-    uint32_t *grp_rep, *ctx_by_x; uint64_t* pid;
-    W2_ALLOC(grp_rep, uint32_t, N2 + 1); W2_ALLOC(ctx_by_x, uint32_t, N2 + 1); W2_ALLOC(pid, uint64_t, N2 + 2);
-    // the K2-mers strictly inside a one-edge place whose edge no longer place shares stay out of the dictionary (k3_lone_places)
-    const bool lone_on = !sorted_dict && N2 && (in.unique_kmers || (P.flags & W2RAP_STEP3_UNIQUE_KMERS)) && !getenv("W2RAP_STEP3_NO_LONE");
-    uint8_t* lone = nullptr; unsigned long long n_pairs = N2;
-    if (lone_on) {
-        uint8_t* shared_edge = nullptr; unsigned long long* d_np = nullptr;
-        W2_ALLOC(shared_edge, uint8_t, NO + 1); W2_ALLOC(lone, uint8_t, U + 1); W2_ALLOC(d_np, unsigned long long, 1);
-        W2_HIP(hipMemsetAsync(shared_edge, 0, NO + 1, st)); W2_HIP(hipMemsetAsync(d_np, 0, 8, st));
-        LAUNCH(c, "k3_mid_edges", k3_mid_edges, dim3(grid_for(std::max<uint64_t>(U, NO))), dim3(256), 0, U, NO, voff, pvec, inv, shared_edge);
-        LAUNCH(c, "k3_lone_places", k3_lone_places, dim3(grid_for(U)), dim3(256), 0, U, voff, pvec, shared_edge, lone);
-        LAUNCH(c, "k3_kmer_keys", k3_kmer_keys, dim3((unsigned)((N2 + 256 * KK_PER - 1) / (256 * KK_PER))), dim3(256), 0, N2, U, q, koff, woff, nbases, (const uint64_t*)all, key, val, meta, gpos, grp_rep, ctx_by_x,
-               (const uint8_t*)lone, d_np, (const uint32_t*)kblk);
-        W2_HIP(hipMemcpyAsync(&n_pairs, d_np, 8, hipMemcpyDeviceToHost, st));
-        W2_HIP(hipStreamSynchronize(st));
-        c.release(shared_edge); c.release(d_np);
-        if (getenv("W2RAP_TRACE")) fprintf(stderr, "[w2rap] step 3 dictionary: %llu of %llu occurrences lie strictly inside an edge no longer place shares\n",
-                                           (unsigned long long)(N2 - n_pairs), (unsigned long long)N2);
-    }
-    else if (N2) LAUNCH(c, "k3_kmer_keys", k3_kmer_keys, dim3((unsigned)((N2 + 256 * KK_PER - 1) / (256 * KK_PER))), dim3(256), 0, N2, U, q, koff, woff, nbases, (const uint64_t*)all, key, sorted_dict ? val : (uint32_t*)nullptr, meta, gpos,
-                        grp_rep, ctx_by_x, (const uint8_t*)nullptr, (unsigned long long*)nullptr, (const uint32_t*)kblk);
-    uint32_t *ghead = nullptr, *gcoll = nullptr, *gover = nullptr, *hidx = nullptr;
-    unsigned long long ncoll = 0;
-    if (!sorted_dict && N2) {
-        bool overflow = false;
-        if (n_pairs) W2_TRY(dict_by_partition(c, n_pairs, q, key, lone_on ? val : (const uint32_t*)nullptr, allb, gpos, meta, grp_rep, ctx_by_x, overflow, N2));
-        if (overflow) {
-            if (getenv("W2RAP_TRACE")) fprintf(stderr, "[w2rap] step 3 dictionary: a hash partition overflowed, sorting instead\n");
-            sorted_dict = true;
-            // (the sorted form wants the key of EVERY occurrence in position order)
-            if (lone_on) LAUNCH(c, "k3_kmer_keys", k3_kmer_keys, dim3((unsigned)((N2 + 256 * KK_PER - 1) / (256 * KK_PER))), dim3(256), 0, N2, U, q, koff, woff, nbases, (const uint64_t*)all, key, val, meta, gpos, grp_rep, ctx_by_x,
-                                (const uint8_t*)nullptr, (unsigned long long*)nullptr, (const uint32_t*)kblk);
-            else LAUNCH(c, "k3_iota", k3_iota, dim3(grid_for(N2)), dim3(256), 0, N2, val);
-        }
-    }
-    if (lone) c.release(lone);
-    if (sorted_dict) {
-        W2_TRY(sort_pairs_u64(c, key, val, N2, 0, (int)q.sbits));
-        W2_ALLOC(ghead, uint32_t, N2 + 1); W2_ALLOC(gcoll, uint32_t, N2 + 1); W2_ALLOC(hidx, uint32_t, N2 + 1);
-        if (N2) LAUNCH(c, "k3_group", k3_group, dim3(grid_for(N2)), dim3(256), 0, N2, U, q, key, val, meta, gpos, allb, ghead, gcoll, d_cnt + 103);
-        W2_HIP(hipMemcpyAsync(&ncoll, d_cnt + 103, 8, hipMemcpyDeviceToHost, st));
-        W2_HIP(hipStreamSynchronize(st));
-        if (ncoll) {
-            W2_ALLOC(gover, uint32_t, N2 + 1);
-            W2_HIP(hipMemsetAsync(gover, 0xFF, (N2 + 1) * 4, st));
-            LAUNCH(c, "k3_group_fix", k3_group_fix, dim3(grid_for(N2)), dim3(256), 0, N2, U, q, key, val, meta, gpos, allb, gcoll, ghead, gover);
-        }
-        W2_TRY(inclusive_max_scan_u32(c, ghead, hidx, N2));
-        if (getenv("W2RAP_TRACE") && N2 && N2 < (1u << 22)) {
-            std::vector<uint32_t> hh(N2), hx(N2); std::vector<uint64_t> hk(N2);
-            W2_HIP(hipMemcpy(hh.data(), ghead, N2 * 4, hipMemcpyDeviceToHost)); W2_HIP(hipMemcpy(hx.data(), hidx, N2 * 4, hipMemcpyDeviceToHost));
-            W2_HIP(hipMemcpy(hk.data(), key, N2 * 8, hipMemcpyDeviceToHost));
-            uint64_t nheads = 0, badscan = 0, unsorted = 0; uint32_t m = 0;
-            for (uint64_t j = 0; j < N2; ++j) { if (hh[j]) ++nheads; m = std::max(m, hh[j]); if (hx[j] != m) ++badscan; if (j && (hk[j] & sort_mask(q.sbits)) < (hk[j - 1] & sort_mask(q.sbits))) ++unsorted; }
-            fprintf(stderr, "[w2rap]   group heads %llu, max-scan mismatches %llu, sort-key inversions %llu\n", (unsigned long long)nheads, (unsigned long long)badscan, (unsigned long long)unsorted);
-        }
-        if (N2) {
-            LAUNCH(c, "k3_rep_init", k3_rep_init, dim3(grid_for(N2)), dim3(256), 0, N2, meta, grp_rep, ctx_by_x);
-            LAUNCH(c, "k3_scatter_rep", k3_scatter_rep, dim3(grid_for(N2)), dim3(256), 0, N2, ghead, hidx, (const uint32_t*)gover, val, meta, grp_rep, ctx_by_x);
-        }
-    }
-    W2_TRY(exclusive_scan_is_self(c, grp_rep, pid, N2));          // (the flags "is its own representative" scanned without being written)
-    uint64_t D = 0;
-    W2_HIP(hipMemcpy(&D, pid + N2, 8, hipMemcpyDeviceToHost));
-    if (2 * D >= (1ull << 32) - 2) { c.err = "more than 2^31 distinct K2-mers on one GPU (32-bit node ids)"; return W2RAP_E_LIMIT; }
-    uint32_t *id_of, *krep, *dctx; uint64_t* dhash = nullptr; uint32_t* did = nullptr;
-    W2_ALLOC(id_of, uint32_t, N2 + 1); W2_ALLOC(krep, uint32_t, D + 1); W2_ALLOC(dctx, uint32_t, D + 1);
-    if (N2) LAUNCH(c, "k3_finish_ids", k3_finish_ids, dim3(grid_for(N2)), dim3(256), 0, N2, grp_rep, pid, ctx_by_x, id_of, krep, dctx);
-    if (P.edge_order_hint && N2) {                   // replay: the sorted (hash, id) list of the distinct K2-mers
-        uint32_t* hf = hidx; uint64_t* hex = pid;    // (reused)
-        W2_ALLOC(dhash, uint64_t, D + 1); W2_ALLOC(did, uint32_t, D + 1);
-        LAUNCH(c, "k3_nonzero", k3_nonzero, dim3(grid_for(N2)), dim3(256), 0, N2, ghead, hf);
-        W2_TRY(exclusive_scan_u32_to_u64(c, hf, hex, N2));
-        LAUNCH(c, "k3_head_list", k3_head_list, dim3(grid_for(N2)), dim3(256), 0, N2, ghead, hex, key, val, id_of, dhash, did);
-    }
-    W2_HIP(hipStreamSynchronize(st));
-    for (void* p : {(void*)key, (void*)val, (void*)ghead, (void*)gcoll, (void*)hidx, (void*)grp_rep, (void*)ctx_by_x, (void*)pid, (void*)gover})
-        if (p) c.release(p);
-    if (getenv("W2RAP_TRACE")) {
-        fprintf(stderr, "[w2rap] step 3 dictionary: %llu occurrences, %llu distinct, %llu neighbours with one sort key but different content\n",
-                (unsigned long long)N2, (unsigned long long)D, ncoll);
-        if (N2 && N2 < (1u << 22)) {                     // small inputs: consistency of the id arrays
-            std::vector<uint32_t> hid(N2), hrep(D), hctx(D);
-            W2_HIP(hipMemcpy(hid.data(), id_of, N2 * 4, hipMemcpyDeviceToHost)); W2_HIP(hipMemcpy(hrep.data(), krep, D * 4, hipMemcpyDeviceToHost));
-            W2_HIP(hipMemcpy(hctx.data(), dctx, D * 4, hipMemcpyDeviceToHost));
-            uint64_t bad_id = 0, bad_rep = 0, zero_ctx = 0;
-            for (uint64_t x = 0; x < N2; ++x) if (hid[x] >= D) ++bad_id;
-            for (uint64_t i = 0; i < D; ++i) { if (hrep[i] >= N2 || hid[hrep[i]] != i) ++bad_rep; if (!(hctx[i] & 0xFF)) ++zero_ctx; }
-            fprintf(stderr, "[w2rap]   ids out of range %llu, representatives inconsistent %llu, empty contexts %llu\n", (unsigned long long)bad_id,
-                    (unsigned long long)bad_rep, (unsigned long long)zero_ctx);
-        }
-    }
-    out.ms_dict = t_dict.stop();
-    // ---------------------------------------------------------------- unipaths
-    Timer t_graph(st);
-    const uint64_t N = 2 * D;
-    const KSrc S{allb, gpos, krep, meta, q};
-    uint32_t *nbr, *nxt0, *nxt, *rnk; unsigned long long* rankw; uint8_t *cyc, *mid, *is_head;
-    W2_ALLOC(nbr, uint32_t, N + 2); W2_ALLOC(nxt0, uint32_t, N + 2); W2_ALLOC(nxt, uint32_t, N + 2); W2_ALLOC(rnk, uint32_t, N + 2);
-    W2_ALLOC(rankw, unsigned long long, N + 2); W2_ALLOC(cyc, uint8_t, N + 2); W2_ALLOC(mid, uint8_t, N + 2); W2_ALLOC(is_head, uint8_t, N + 2);
-    W2_HIP(hipMemsetAsync(nbr, 0xFF, (N + 2) * 4, st));
-    W2_HIP(hipMemsetAsync(d_flags, 0, 32, st));
-    if (D) {
-        if (N2 > 1) LAUNCH(c, "k3_nbr", k3_nbr, dim3(grid_for(N2)), dim3(256), 0, N2, U, koff, id_of, meta, nbr, (const uint32_t*)kblk);
-        LAUNCH(c, "k3_links", k3_links, dim3(grid_for(D)), dim3(256), 0, D, dctx, nbr, nxt0);
-        W2_TRY(run_ranking(c, N, nxt0, nxt, rnk, rankw, cyc, mid, d_flags, nullptr, nullptr, false));
-        W2_TRY(check());
-        if (h_flags[2]) {                            // smooth circles
-            uint32_t *nx, *mn, *nx2, *mn2;
-            W2_ALLOC(nx, uint32_t, N); W2_ALLOC(mn, uint32_t, N); W2_ALLOC(nx2, uint32_t, N); W2_ALLOC(mn2, uint32_t, N);
-            LAUNCH(c, "k3_minjump_init", k3_minjump_init, dim3(grid_for(N)), dim3(256), 0, N, nxt0, cyc, nx, mn);
-            for (int round = 0; round < 33; ++round) {
-                LAUNCH(c, "k3_minjump", k3_minjump, dim3(grid_for(N)), dim3(256), 0, N, S, nx, mn, nx2, mn2);
-                std::swap(nx, nx2); std::swap(mn, mn2);
-            }
-            LAUNCH(c, "k3_cycle_cut", k3_cycle_cut, dim3(grid_for(D)), dim3(256), 0, D, cyc, mn, nxt0);
-            W2_HIP(hipStreamSynchronize(st));
-            c.release(nx); c.release(mn); c.release(nx2); c.release(mn2);
-            W2_HIP(hipMemsetAsync(d_flags, 0, 32, st));
-            W2_TRY(run_ranking(c, N, nxt0, nxt, rnk, rankw, cyc, mid, d_flags, nullptr, nullptr, false));
-            W2_TRY(check());
-            if (h_flags[2]) { c.err = "failed to close circle (BigKPather.cc:141)"; return W2RAP_E_GRAPH; }
-        }
-        W2_HIP(hipMemsetAsync(mid, 0, N, st));
-        LAUNCH(c, "k3_mid", k3_mid, dim3(grid_for(D)), dim3(256), 0, D, S, nxt, rnk, mid);
-    }
-    const uint64_t head_cap = D ? c.rank_ends + 1 : 1;
-    uint32_t* head_v = nullptr;
-    W2_ALLOC(head_v, uint32_t, head_cap + 1);
-    if (N) {
-        uint32_t* cand = nullptr;
-        W2_ALLOC(cand, uint32_t, head_cap + 1);
-        LAUNCH(c, "k3_head_cands", k3_head_cands, dim3((unsigned)((N + 256 * HC_PER - 1) / (256 * HC_PER))), dim3(256), 0, N, nxt0, is_head, cand, d_cnt + 101, head_cap);
-        LAUNCH(c, "k3_heads", k3_heads, dim3(grid_for(head_cap)), dim3(256), 0, (const unsigned long long*)(d_cnt + 101), head_cap, (const uint32_t*)cand, S, dctx, nxt, rnk, mid, is_head,
-               head_v, d_cnt + 102);
-        c.release(cand);
-    }
-    unsigned long long E = 0;
-    W2_HIP(hipMemcpyAsync(&E, d_cnt + 102, 8, hipMemcpyDeviceToHost, st));
-    W2_HIP(hipStreamSynchronize(st));
-    if (E > head_cap) { c.err = "more canonical heads than chain ends"; return W2RAP_E_GRAPH; }
-    uint32_t *perm, *head_edge, *edge_head, *edge_nk; uint64_t* wtmp;
-    W2_ALLOC(perm, uint32_t, E + 1); W2_ALLOC(head_edge, uint32_t, N + 2); W2_ALLOC(edge_head, uint32_t, E + 1); W2_ALLOC(edge_nk, uint32_t, E + 1); W2_ALLOC(wtmp, uint64_t, E + 1);
-    W2_HIP(hipMemsetAsync(head_edge, 0xFF, (N + 2) * 4, st));
-    const w2rap_edge_hint* hint = P.edge_order_hint;
-    if (hint) {
-        if (hint->n_edges != E) { c.err = "edge_order_hint has " + std::to_string(hint->n_edges) + " edges, the graph has " + std::to_string(E); return W2RAP_E_HINT; }
-        for (uint64_t e = 0; e < E; ++e) {
-            if (hint->len[e] < K2) { c.err = "edge_order_hint: edge shorter than K2"; return W2RAP_E_HINT; }
-            if (hint->byte_off[e + 1] < hint->byte_off[e] || hint->byte_off[e + 1] - hint->byte_off[e] != ((uint64_t)hint->len[e] + 3) / 4) {
-                c.err = "edge_order_hint: byte_off does not match len"; return W2RAP_E_HINT;
-            }
-        }
-        uint8_t* hbits = nullptr; uint64_t *hbyte = nullptr, *hbase0 = nullptr; uint32_t* hlen = nullptr;
-        W2_TRY(up_pooled(c, &hbits, hint->packed, E ? hint->byte_off[E] : 0, 32));
-        W2_TRY(up_pooled(c, &hbyte, hint->byte_off, E + 1));
-        W2_TRY(up_pooled(c, &hlen, hint->len, E));
-        W2_ALLOC(hbase0, uint64_t, E + 1);
-        LAUNCH(c, "k3_mul4", k3_mul4, dim3(grid_for(E + 1)), dim3(256), 0, E + 1, hbyte, hbase0);
-        if (E) LAUNCH(c, "k3_edge_from_hint", k3_edge_from_hint, dim3(grid_for(E)), dim3(256), 0, E, D, S, hbits, hbase0, hlen, dhash, did, is_head, rnk, head_edge, edge_head, edge_nk, d_flags);
-        W2_TRY(check());
-        for (void* p : {(void*)hbits, (void*)hbyte, (void*)hlen, (void*)hbase0}) c.release(p);
-    } else if (E) {
-        // canonical order: the unipaths by their sequences = by their first K2-mers (distinct), NW words, least significant first
-        // ONE sort by the first word, then the (short) runs of equal first words ordered by full comparison; NW sorts, least significant
-        // word first, only if a run is too long for that
-        bool by_words = test_hook("W2RAP_TEST_STEP3_FULL_SORTS");
-        unsigned max_run = 64;
-        if (test_hook("W2RAP_TEST_TIE_RUN")) max_run = (unsigned)atoi(getenv("W2RAP_TEST_TIE_RUN"));
-        LAUNCH(c, "k3_iota", k3_iota, dim3(grid_for(E)), dim3(256), 0, E, perm);
-        if (!by_words) {
-            LAUNCH(c, "k3_head_word", k3_head_word, dim3(grid_for(E)), dim3(256), 0, E, S, head_v, perm, 0u, wtmp);
-            W2_TRY(sort_pairs_u64(c, wtmp, perm, E, 0, 64));
-            W2_HIP(hipMemsetAsync(d_flags + 6, 0, 4, st));
-            LAUNCH(c, "k3_edge_tie_sort", k3_edge_tie_sort, dim3(grid_for(E)), dim3(256), 0, E, S, head_v, wtmp, perm, max_run, d_flags);
-            uint32_t long_run = 0;
-            W2_HIP(hipMemcpyAsync(&long_run, d_flags + 6, 4, hipMemcpyDeviceToHost, st));
-            W2_HIP(hipStreamSynchronize(st));
-            if (long_run) { by_words = true; LAUNCH(c, "k3_iota", k3_iota, dim3(grid_for(E)), dim3(256), 0, E, perm); }
-        }
-        if (by_words)
-            W2_TRY(sort_by_words(c, perm, E, q.NW, wtmp, [&](unsigned j, uint64_t* tmp) -> int {
-                LAUNCH(c, "k3_head_word", k3_head_word, dim3(grid_for(E)), dim3(256), 0, E, S, head_v, perm, j, tmp);
-                return 0; }));
-        LAUNCH(c, "k3_edge_from_sorted", k3_edge_from_sorted, dim3(grid_for(E)), dim3(256), 0, E, perm, head_v, rnk, head_edge, edge_head, edge_nk);
-    }
-    // ---- edge sequences, K2-mer placements
-    uint32_t* elen = nullptr; uint64_t* edge_off = nullptr;
-    W2_ALLOC(elen, uint32_t, E + 1); W2_ALLOC(edge_off, uint64_t, E + 2);
-    if (E) LAUNCH(c, "k3_edge_len", k3_edge_len, dim3(grid_for(E)), dim3(256), 0, E, K2, edge_nk, elen);
-    W2_TRY(exclusive_scan_u32_to_u64(c, elen, edge_off, E));
-    uint64_t edge_bases = 0;
-    W2_HIP(hipMemcpy(&edge_bases, edge_off + E, 8, hipMemcpyDeviceToHost));
-    uint8_t* codes = nullptr; uint32_t *k_edge, *k_off;
-    W2_ALLOC(codes, uint8_t, edge_bases + 64); W2_ALLOC(k_edge, uint32_t, D + 1); W2_ALLOC(k_off, uint32_t, D + 1);
-    if (D) LAUNCH(c, "k3_assign", k3_assign, dim3(grid_for(D)), dim3(256), 0, D, S, nxt, rnk, head_edge, edge_off, k_edge, k_off, codes, d_flags);
-    W2_TRY(check());
-    // ---- objects, vertices, adjacency
-    uint32_t* nobj = nullptr; uint64_t* ooff = nullptr;
-    W2_ALLOC(nobj, uint32_t, E + 1); W2_ALLOC(ooff, uint64_t, E + 2);
-    if (E) LAUNCH(c, "k3_edge_nobj", k3_edge_nobj, dim3(grid_for(E)), dim3(256), 0, E, edge_head, edge_nk, dctx, nobj);
-    W2_TRY(exclusive_scan_u32_to_u64(c, nobj, ooff, E));
-    uint64_t NO2 = 0;
-    W2_HIP(hipMemcpy(&NO2, ooff + E, 8, hipMemcpyDeviceToHost));
-    int32_t *fwdX, *revX, *inv2, *left, *right; uint32_t* obj_edge;
-    W2_ALLOC(fwdX, int32_t, E + 1); W2_ALLOC(revX, int32_t, E + 1); W2_ALLOC(inv2, int32_t, NO2 + 1); W2_ALLOC(obj_edge, uint32_t, NO2 + 1);
-    W2_ALLOC(left, int32_t, NO2 + 1); W2_ALLOC(right, int32_t, NO2 + 1);
-    if (E) LAUNCH(c, "k3_edge_xlat", k3_edge_xlat, dim3(grid_for(E)), dim3(256), 0, E, nobj, ooff, fwdX, revX, obj_edge, inv2);
-    uint64_t NV = 0;
-    const uint64_t nends = 2 * NO2;
-    if (nends) {
-        uint64_t *ehash, *etmp, *eex; uint32_t *eperm, *eflag;
-        W2_ALLOC(ehash, uint64_t, nends); W2_ALLOC(etmp, uint64_t, nends); W2_ALLOC(eex, uint64_t, nends + 1); W2_ALLOC(eperm, uint32_t, nends); W2_ALLOC(eflag, uint32_t, nends);
-        LAUNCH(c, "k3_end_hash", k3_end_hash, dim3(grid_for(nends)), dim3(256), 0, NO2, K2, obj_edge, edge_off, edge_nk, codes, ehash);
-        LAUNCH(c, "k3_iota", k3_iota, dim3(grid_for(nends)), dim3(256), 0, nends, eperm);
-        const unsigned EW = (K2 - 1 + 31) / 32;
-        uint64_t* ewords = nullptr;
-        W2_ALLOC(ewords, uint64_t, (uint64_t)EW * nends);
-        LAUNCH(c, "k3_end_words", k3_end_words, dim3(grid_for(nends)), dim3(256), 0, nends, K2, EW, obj_edge, edge_off, edge_nk, codes, ewords);
-        // ONE sort by the hash, boundaries where it changes, equal hashes verified by content (k3_end_group); by (hash, sequence) -- LSD over
-        // the sequence words, then the hash -- only if two contents share a hash.  Same vertex numbers either way: the groups are ordered by hash.
-        bool by_words = test_hook("W2RAP_TEST_STEP3_FULL_SORTS");
-        const bool pretend = test_hook("W2RAP_TEST_ENDS_COLLISION");
-        for (;;) {
-            if (by_words)
-                W2_TRY(sort_by_words(c, eperm, nends, EW, etmp, [&](unsigned j, uint64_t* tmp) -> int {
-                    LAUNCH(c, "k3_gather_u64", k3_gather_u64, dim3(grid_for(nends)), dim3(256), 0, nends, ewords + (uint64_t)j * nends, eperm, tmp);
-                    return 0; }));
-            LAUNCH(c, "k3_gather_u64", k3_gather_u64, dim3(grid_for(nends)), dim3(256), 0, nends, ehash, eperm, etmp);
-            W2_TRY(sort_pairs_u64(c, etmp, eperm, nends, 0, 64));
-            if (by_words) {
-                // vertex boundaries: the hash or any sequence word differs from the predecessor's
-                LAUNCH(c, "k3_end_differs", k3_end_differs, dim3(grid_for(nends)), dim3(256), 0, nends, etmp, eflag, true);
-                for (unsigned j = 0; j < EW; ++j) {
-                    LAUNCH(c, "k3_gather_u64", k3_gather_u64, dim3(grid_for(nends)), dim3(256), 0, nends, ewords + (uint64_t)j * nends, eperm, etmp);
-                    LAUNCH(c, "k3_end_differs", k3_end_differs, dim3(grid_for(nends)), dim3(256), 0, nends, etmp, eflag, false);
-                }
-            } else {
-                W2_HIP(hipMemsetAsync(d_flags + 7, 0, 4, st));
-                LAUNCH(c, "k3_end_group", k3_end_group, dim3(grid_for(nends)), dim3(256), 0, nends, EW, etmp, eperm, ewords, eflag, d_flags, pretend);
-            }
-            W2_TRY(exclusive_scan_u32_to_u64(c, eflag, eex, nends));
-            uint32_t shared_hash = 0;
-            if (!by_words) W2_HIP(hipMemcpyAsync(&shared_hash, d_flags + 7, 4, hipMemcpyDeviceToHost, st));
-            W2_HIP(hipMemcpy(&NV, eex + nends, 8, hipMemcpyDeviceToHost));
-            W2_HIP(hipStreamSynchronize(st));
-            if (shared_hash && !by_words) { by_words = true; LAUNCH(c, "k3_iota", k3_iota, dim3(grid_for(nends)), dim3(256), 0, nends, eperm); continue; }
-            break;
-        }
-        c.release(ewords);
-        NV += 1;
-        LAUNCH(c, "k3_end_vertices", k3_end_vertices, dim3(grid_for(nends)), dim3(256), 0, nends, eperm, eflag, eex, left, right);
-        W2_HIP(hipStreamSynchronize(st));
-        for (void* p : {(void*)ehash, (void*)etmp, (void*)eex, (void*)eperm, (void*)eflag}) c.release(p);
-    }
-    uint64_t *from_off, *to_off; int32_t *from_v, *from_e, *to_v, *to_e;
-    W2_ALLOC(from_off, uint64_t, NV + 2); W2_ALLOC(to_off, uint64_t, NV + 2);
-    W2_ALLOC(from_v, int32_t, NO2 + 1); W2_ALLOC(from_e, int32_t, NO2 + 1); W2_ALLOC(to_v, int32_t, NO2 + 1); W2_ALLOC(to_e, int32_t, NO2 + 1);
-    {
-        uint64_t* akeys = nullptr; uint32_t *avals = nullptr, *deg = nullptr;
-        W2_ALLOC(akeys, uint64_t, NO2 + 1); W2_ALLOC(avals, uint32_t, NO2 + 1); W2_ALLOC(deg, uint32_t, NV + 1);
-        for (int dir = 0; dir < 2; ++dir) {          // AddEdge keeps from_[v] sorted by target with ties in insertion (= object id) order: stable sort by (v, w)
-            W2_HIP(hipMemsetAsync(deg, 0, (NV + 1) * 4, st));
-            if (NO2) {
-                LAUNCH(c, "k3_adj_keys", k3_adj_keys, dim3(grid_for(NO2)), dim3(256), 0, NO2, dir ? right : left, dir ? left : right, akeys, avals, deg);
-                W2_TRY(sort_pairs_u64(c, akeys, avals, NO2, 0, 64));
-                LAUNCH(c, "k3_adj_out", k3_adj_out, dim3(grid_for(NO2)), dim3(256), 0, NO2, avals, dir ? left : right, dir ? to_v : from_v, dir ? to_e : from_e);
-            }
-            W2_TRY(exclusive_scan_u32_to_u64(c, deg, dir ? to_off : from_off, NV));
-        }
-        c.release(akeys); c.release(avals); c.release(deg);
-    }
-    out.ms_graph = t_graph.stop();
+    // ---------------------------------------------------------------- dictionary, unipaths, objects, vertices, adjacency (step3_back)
+    const Stream3 S3{U, N2, all, woff, nbases, koff, kblk};
+    const Lone3 lone3{NO, voff, pvec, inv};
+    Back3 B;
+    W2_TRY(step3_back(c, K2, S3, (in.unique_kmers || (P.flags & W2RAP_STEP3_UNIQUE_KMERS)) ? &lone3 : nullptr, P.edge_order_hint, d_flags, d_cnt, B));
+    out.ms_dict = B.ms_dict; out.ms_graph = B.ms_graph;
+    const uint64_t D = B.D, NO2 = B.NO2, NV = B.NV; const unsigned long long E = B.E;
+    int32_t *inv2 = B.inv2, *left = B.left, *right = B.right, *from_v = B.from_v, *from_e = B.from_e, *to_v = B.to_v, *to_e = B.to_e; uint64_t *from_off = B.from_off, *to_off = B.to_off;
     // ---------------------------------------------------------------- places through the graph, read paths
     Timer t_paths(st);
-    uint32_t* ostart = nullptr; int32_t *oobj, *starts, *stops; uint64_t* oex;
-    W2_ALLOC(ostart, uint32_t, N2 + 1); W2_ALLOC(oobj, int32_t, N2 + 1); W2_ALLOC(oex, uint64_t, N2 + 2); W2_ALLOC(starts, int32_t, U + 1); W2_ALLOC(stops, int32_t, U + 1);
-    if (N2) LAUNCH(c, "k3_occ", k3_occ, dim3(grid_for(N2)), dim3(256), 0, N2, U, koff, id_of, meta, k_edge, k_off, edge_nk, fwdX, revX, ostart, oobj, starts, stops, (const uint32_t*)kblk);
-    W2_TRY(exclusive_scan_u32_to_u64(c, ostart, oex, N2));
-    uint64_t nip = 0;
-    W2_HIP(hipMemcpy(&nip, oex + N2, 8, hipMemcpyDeviceToHost));
-    int32_t* ipath = nullptr; uint64_t* ioff = nullptr;
-    W2_ALLOC(ipath, int32_t, nip + 1); W2_ALLOC(ioff, uint64_t, U + 2);
-    if (N2) LAUNCH(c, "k3_place_paths", k3_place_paths, dim3(grid_for(N2)), dim3(256), 0, N2, U, koff, ostart, oex, oobj, ipath, ioff, (const uint32_t*)kblk);
-    W2_HIP(hipMemcpyAsync(ioff + U, &nip, 8, hipMemcpyHostToDevice, st));
+    W2_TRY(step3_through(c, S3, B));
+    const uint64_t* ioff = B.ioff; const int32_t *ipath = B.ipath, *starts = B.starts, *stops = B.stops;
     uint32_t* rcnt = nullptr; uint64_t* o_off = nullptr; int32_t *o_offset = nullptr, *o_edges = nullptr;
     W2_ALLOC(rcnt, uint32_t, n + 1); W2_ALLOC(o_off, uint64_t, n + 2); W2_ALLOC(o_offset, int32_t, n + 1);
     if (n) LAUNCH(c, "k3_read_counts", k3_read_counts, dim3(grid_for(n)), dim3(256), 0, n, state, place_of_read, ioff, rcnt);
@@ -1994,22 +2070,8 @@ int step3(Ctx& c, const DevIn& in, const w2rap_step3_params& P, w2rap_step3_out&
                          o_offset, o_edges);
     out.ms_paths = t_paths.stop();
     // ---------------------------------------------------------------- results
-    uint32_t *d_olen = nullptr, *d_nby = nullptr; uint64_t* d_byoff = nullptr; uint8_t* d_packed = nullptr;
-    W2_ALLOC(d_olen, uint32_t, NO2 + 1); W2_ALLOC(d_nby, uint32_t, NO2 + 1); W2_ALLOC(d_byoff, uint64_t, NO2 + 2);
-    if (NO2) LAUNCH(c, "k3_obj_len", k3_obj_len, dim3(grid_for(NO2)), dim3(256), 0, NO2, K2, obj_edge, edge_nk, d_olen, d_nby);
-    W2_TRY(exclusive_scan_u32_to_u64(c, d_nby, d_byoff, NO2));
-    uint64_t total_bytes = 0;
-    W2_HIP(hipMemcpy(&total_bytes, d_byoff + NO2, 8, hipMemcpyDeviceToHost));
-    // 32 zeroed bytes of slack behind the last edge (for every caller: they cost nothing): Step 4's k4_walks and k4e_gather read past it,
-    // and with W2RAP_STEP3_KEEP_DEVICE this block becomes Graph4::ebits as it stands, without a copy
-    W2_ALLOC(d_packed, uint8_t, total_bytes + 33);
-    W2_HIP(hipMemsetAsync(d_packed + total_bytes, 0, 33, st));
-    if (total_bytes) {
-        uint32_t* bblk = nullptr;
-        W2_TRY(block_index(c, (const uint64_t*)d_byoff, NO2, total_bytes, &bblk));
-        LAUNCH(c, "k3_pack_objs", k3_pack_objs, dim3(grid_for(total_bytes)), dim3(256), 0, total_bytes, NO2, K2, d_byoff, obj_edge, edge_nk, edge_off, codes, d_packed, (const uint32_t*)bblk);
-        c.release(bblk);
-    }
+    W2_TRY(step3_pack(c, K2, B));
+    uint32_t* d_olen = B.olen; uint64_t* d_byoff = B.byoff; uint8_t* d_packed = B.packed; const uint64_t total_bytes = B.total_bytes;
     unsigned long long h_cnt[112];
     W2_HIP(hipMemcpyAsync(h_cnt, d_cnt, sizeof(h_cnt), hipMemcpyDeviceToHost, st));
     out.K2 = (int32_t)K2; out.n_vertices = NV; out.n_edge_objs = NO2; out.n_paths = n;

@@ -3,8 +3,15 @@
 `partners_to_ends` mirrors ``PartnersToEnds(hbvr, pathsr, bases, quals)``, the last line of the reference's Step 5
 (src/modules/w2rap-contigger.cc:448, src/paths/long/large/GapToyTools5.cc:1150-1517): reads without a path whose mate ends near a dead
 end of the graph are looked up by their 28-mers against every edge, each hit is checked with a quality-aware window, and a read with
-exactly one good (edge, offset) is placed there.  The graph is not edited.  The rest of Step 5 (local assemblies, AddNewStuff, Unsat)
-and Steps 6-7 stay the reference's.  The HIP library is the only implementation (no CPU fallback)."""
+exactly one good (edge, offset) is placed there.  The graph is not edited.
+
+`add_new_stuff` mirrors ``AddNewStuff(new_stuff, hbr, inv2, pathsr, bases, quals, 5, ..., 1)``, the call in front of it
+(w2rap-contigger.cc:447, GapToyTools4.cc:133-368): the graph is rebuilt from its edges, its vertex crossings and the patch sequences,
+every read path is moved onto the new graph and re-extended over the branches with its bases and qualities.  `finish` is the two calls
+one after the other: given new_stuff, what the reference writes as .large_K.final.hbv/.paths.
+
+The rest of Step 5 (the local assemblies, the clustering half of Unsat) and Steps 6-7 stay the reference's.  The HIP library is the only
+implementation (no CPU fallback)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -13,7 +20,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import formats as F
-from .step2 import Step2Error, _np_from, _ptr, lib as _lib2
+from .step2 import EdgeHint, Step2Error, _np_from, _ptr, lib as _lib2, make_hint
 
 
 class Step5In(C.Structure):
@@ -53,6 +60,24 @@ class Step5OpenOut(C.Structure):
     _fields_ = [(k, C.c_void_p) for k in _OPEN_ARRAYS] + [(k, C.c_uint64) for k in OPEN_COUNTERS] + [(k, C.c_float) for k in OPEN_PHASES]
 
 
+ADD_KEEP_MAP = 1                  # W2RAP_STEP5_ADD_KEEP_MAP
+ADD_COUNTERS = ("n_all", "n_junctions", "n_all_bases", "n_kmer_instances", "n_kmers_distinct", "n_unipaths", "n_tr_empty", "n_tr_first", "n_tr_walked",
+                "n_tr_cleared", "n_ext_tried", "n_ext_too_many", "n_ext_no_cover", "n_ext_ambiguous", "n_ext_extended")
+ADD_PHASES = ("ms_all", "ms_dict", "ms_graph", "ms_translate", "ms_extend")
+
+
+class Step5AddParams(C.Structure):
+    _fields_ = [("device", C.c_int32), ("min_gain", C.c_int32), ("ext_mode", C.c_int32), ("edge_order_hint", C.POINTER(EdgeHint)), ("flags", C.c_uint32)]
+
+
+class Step5AddOut(C.Structure):
+    _fields_ = ([("K", C.c_int32), ("n_vertices", C.c_uint64), ("n_edge_objs", C.c_uint64)] +
+                [(k, C.c_void_p) for k in ("edge_packed", "edge_byte_off", "edge_len", "vleft", "vright", "from_off", "from_v", "from_e", "to_off", "to_v", "to_e", "inv2")] +
+                [("n_paths", C.c_uint64), ("path_offset", C.c_void_p), ("path_off", C.c_void_p), ("path_edges", C.c_void_p),
+                 ("n_old_edge_objs", C.c_uint64), ("to3_off", C.c_void_p), ("to3", C.c_void_p), ("left3", C.c_void_p)] +
+                [(k, C.c_uint64) for k in ADD_COUNTERS] + [(k, C.c_float) for k in ADD_PHASES])
+
+
 _ready = False
 
 
@@ -66,6 +91,10 @@ def lib():
         L.w2rap_step5_open.argtypes = [C.POINTER(Step5OpenIn), C.POINTER(Step5Params), C.POINTER(Step5OpenOut), C.c_char_p, C.c_size_t]
         L.w2rap_step5_open_free.argtypes = [C.POINTER(Step5OpenOut)]
         L.w2rap_step5_open_free.restype = None
+        L.w2rap_step5_add_new_stuff.argtypes = [C.POINTER(Step5In), C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Step5AddParams), C.POINTER(Step5AddOut),
+                                                C.c_char_p, C.c_size_t]
+        L.w2rap_step5_add_free.argtypes = [C.POINTER(Step5AddOut)]
+        L.w2rap_step5_add_free.restype = None
         L.w2rap_step5_profile.argtypes = [C.c_char_p, C.c_size_t]
         L.w2rap_step5_profile.restype = C.c_size_t
         _ready = True
@@ -81,11 +110,8 @@ class Step5Result:
     ms: dict                      # PHASES -> device milliseconds
 
 
-def partners_to_ends(hbv: F.HBV, paths, reads, quals, device=0, qual_off=None) -> Step5Result:
-    """PartnersToEnds through the C entry point (w2rap_step5_partners_to_ends).
-    paths = (offset i32[n], path_off u64[n+1], edges i32[]); reads = (packed, byte_off, read_len) as formats.read_fastb gives them;
-    quals = the unpacked .qualp values, one byte per base (formats.qualp_to_raw); qual_off None = the running sum of read_len."""
-    L = lib()
+def _step5_in(hbv, paths, reads, quals, qual_off):
+    """-> (Step5In, the arrays it points into)"""
     ln = np.ascontiguousarray(reads[2], np.uint32)
     if qual_off is None:
         qual_off = np.zeros(len(ln) + 1, np.uint64)
@@ -99,6 +125,15 @@ def partners_to_ends(hbv: F.HBV, paths, reads, quals, device=0, qual_off=None) -
     p = lambda a: _ptr(a) if len(a) else None
     i = Step5In(hbv.K, len(keep[2]), p(keep[0]), p(keep[1]), p(keep[2]), hbv.n_vertices, p(keep[3]), p(keep[4]), p(keep[5]), p(keep[6]), p(keep[7]),
                 len(keep[8]), p(keep[8]), p(keep[9]), p(keep[10]), len(ln), p(keep[11]), p(keep[12]), p(keep[13]), p(keep[14]), p(keep[15]))
+    return i, keep
+
+
+def partners_to_ends(hbv: F.HBV, paths, reads, quals, device=0, qual_off=None) -> Step5Result:
+    """PartnersToEnds through the C entry point (w2rap_step5_partners_to_ends).
+    paths = (offset i32[n], path_off u64[n+1], edges i32[]); reads = (packed, byte_off, read_len) as formats.read_fastb gives them;
+    quals = the unpacked .qualp values, one byte per base (formats.qualp_to_raw); qual_off None = the running sum of read_len."""
+    L = lib()
+    i, keep = _step5_in(hbv, paths, reads, quals, qual_off)
     prm = Step5Params(device, 0)
     o = Step5Out()
     err = C.create_string_buffer(1024)
@@ -111,6 +146,75 @@ def partners_to_ends(hbv: F.HBV, paths, reads, quals, device=0, qual_off=None) -
                            {k: int(getattr(o, k)) for k in COUNTERS}, {k: float(getattr(o, k)) for k in PHASES})
     finally:
         L.w2rap_step5_free(C.byref(o))
+
+
+@dataclass
+class Step5Added:
+    hbv: F.HBV                    # the new graph
+    vleft: np.ndarray
+    vright: np.ndarray
+    to_v: np.ndarray
+    inv: np.ndarray               # its involution
+    path_offset: np.ndarray       # ALL read paths on the new graph
+    path_off: np.ndarray
+    path_edges: np.ndarray
+    counters: dict                # ADD_COUNTERS -> int
+    ms: dict                      # ADD_PHASES -> device milliseconds
+    to3: tuple = None             # keep_map: (off u64[E_old+1], edges i32[]) -- the path of every old edge object through the new graph
+    left3: np.ndarray = None      # keep_map: i32[E_old] its first skip
+
+
+def add_new_stuff(hbv: F.HBV, paths, reads, quals, new_stuff, min_gain=5, ext_mode=1, hint=None, keep_map=False, device=0, qual_off=None) -> Step5Added:
+    """AddNewStuff through the C entry point (w2rap_step5_add_new_stuff).  hbv, paths, reads, quals as for partners_to_ends;
+    new_stuff = (packed, byte_off, len) in the packing of the edges (formats.pack_bases), any lengths, possibly none;
+    hint = (packed, byte_off, len) of the new graph's canonical edges in the order to replay, or None for the lexicographic order."""
+    L = lib()
+    i, keep = _step5_in(hbv, paths, reads, quals, qual_off)
+    npk = np.ascontiguousarray(new_stuff[0], np.uint8); nbo = np.ascontiguousarray(new_stuff[1], np.uint64); nln = np.ascontiguousarray(new_stuff[2], np.uint32)
+    if len(nbo) != len(nln) + 1:
+        raise ValueError("new_stuff: byte_off must have one entry more than len")
+    hint_p = None
+    if hint is not None:
+        eh, k2 = make_hint(*hint)
+        keep.append(k2)
+        hint_p = C.pointer(eh)
+    prm = Step5AddParams(device, min_gain, ext_mode, hint_p, ADD_KEEP_MAP if keep_map else 0)
+    o = Step5AddOut()
+    err = C.create_string_buffer(1024)
+    rc = L.w2rap_step5_add_new_stuff(C.byref(i), len(nln), _ptr(npk) if len(npk) else None, _ptr(nbo), _ptr(nln) if len(nln) else None, C.byref(prm), C.byref(o), err, 1024)
+    if rc:
+        raise Step2Error(rc, err.value.decode(errors="replace"))
+    try:
+        NO, NV, NP = o.n_edge_objs, o.n_vertices, o.n_paths
+        boff = _np_from(o.edge_byte_off, np.uint64, NO + 1)
+        h2 = F.HBV(o.K, _np_from(o.from_off, np.uint64, NV + 1), _np_from(o.from_v, np.int32, NO), _np_from(o.from_e, np.int32, NO),
+                   _np_from(o.to_off, np.uint64, NV + 1), _np_from(o.to_e, np.int32, NO), _np_from(o.edge_packed, np.uint8, int(boff[-1])), boff,
+                   _np_from(o.edge_len, np.uint32, NO))
+        po = _np_from(o.path_off, np.uint64, NP + 1)
+        res = Step5Added(h2, _np_from(o.vleft, np.int32, NO), _np_from(o.vright, np.int32, NO), _np_from(o.to_v, np.int32, NO), _np_from(o.inv2, np.int32, NO),
+                         _np_from(o.path_offset, np.int32, NP), po, _np_from(o.path_edges, np.int32, int(po[-1])),
+                         {k: int(getattr(o, k)) for k in ADD_COUNTERS}, {k: float(getattr(o, k)) for k in ADD_PHASES})
+        if keep_map:
+            t3o = _np_from(o.to3_off, np.uint64, o.n_old_edge_objs + 1)
+            res.to3 = (t3o, _np_from(o.to3, np.int32, int(t3o[-1])))
+            res.left3 = _np_from(o.left3, np.int32, o.n_old_edge_objs)
+        return res
+    finally:
+        L.w2rap_step5_add_free(C.byref(o))
+
+
+@dataclass
+class Step5Finished:
+    added: Step5Added             # the graph (added.hbv, added.inv) and everything AddNewStuff reports
+    placed: Step5Result           # PartnersToEnds on it: the final read paths and its counters
+
+
+def finish(hbv: F.HBV, paths, reads, quals, new_stuff, min_gain=5, ext_mode=1, hint=None, keep_map=False, device=0, qual_off=None) -> Step5Finished:
+    """add_new_stuff, then partners_to_ends on its result: given new_stuff, the graph and the paths the reference writes as
+    .large_K.final.hbv/.paths (w2rap-contigger.cc:447-452)."""
+    a = add_new_stuff(hbv, paths, reads, quals, new_stuff, min_gain, ext_mode, hint, keep_map, device, qual_off)
+    p = partners_to_ends(a.hbv, (a.path_offset, a.path_off, a.path_edges), reads, quals, device, qual_off)
+    return Step5Finished(a, p)
 
 
 @dataclass
@@ -174,7 +278,7 @@ def opening(hbv: F.HBV, inv, paths, read_len, parts=("index", "links", "layout")
 
 
 def profile():
-    """-> {kernel name: (total ms, launches)} of the last partners_to_ends or opening in this process"""
+    """-> {kernel name: (total ms, launches)} of the last partners_to_ends, opening or add_new_stuff in this process"""
     L = lib()
     n = L.w2rap_step5_profile(None, 0)
     buf = C.create_string_buffer(int(n) + 16)
