@@ -130,7 +130,7 @@ def gfa_goldens():
 
 # the tests whose reference runs are replayed from refruns/<case>/ (conftest.reference_outputs)
 REFRUN_TESTS = ("tests/test_step3_consumer.py", "tests/test_step3_oracle.py", "tests/test_gfa_oracle.py", "tests/test_step1_oracle.py",
-                "tests/test_step5_reference.py", "tests/test_step4_model.py", "tests/test_gfa_cases.py")
+                "tests/test_step5_reference.py", "tests/test_step4_model.py", "tests/test_gfa_cases.py", "tests/test_step5_add_model.py")
 
 
 def refruns(tests=()):

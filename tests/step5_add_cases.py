@@ -1,10 +1,12 @@
-"""Inputs for AddNewStuff (w2rap_step5_add_new_stuff): hand-made cases with literal expected paths, three seeded random cases, and the
-recorded runs of the reference's own builder on `allx` (tests/golden/refruns/step5_add_<case>/).  Shared by test_step5_add_model.py
-(CPU: the model against the records and the literals) and test_gpu_step5_add.py (the library against records, literals and model).
+"""Inputs for AddNewStuff (w2rap_step5_add_new_stuff): hand-made cases with literal expected paths, three seeded random cases, the
+recorded runs of the reference's own AddNewStuff on them (tests/golden/refruns/step5_addref_<case>/) and the recorded runs of the
+reference's builder on an encoding of `allx` (step5_add_<case>/).  Shared by test_step5_add_model.py (CPU: the model against the records
+and the literals) and test_gpu_step5_add.py (the library against records, literals and model).
 
 A literal is written in SEQUENCES, not ids: the expected path of a read is a list of edge sequences of the new graph (slices of the
 case's genome) and an offset; the numbering of the new graph (lexicographic by default) never enters."""
 import os
+from dataclasses import dataclass
 
 import numpy as np
 
@@ -331,11 +333,169 @@ def empty_graph(K=80, patch=False, seed=10):
     return c
 
 
+def tandem(K=20, u=24, seed=13):
+    """X U U U Y with a unit U of u >= K bases: the cycle of U's K-mers is entered from X and left to Y, so it is two edges, D (U itself,
+    u - K + 1 K-mers) and C (the K - 1 K-mers that wrap), and the genome reads In D C D C D Out.  The old graph is two edges that meet
+    inside the second D, so their maps hold the loop's edges more than once: [In D C D] and [D C D Out], which overlap by one entry and
+    by three.  OverlapAppend takes the three (Vec.h:612, longest first) -- and so drops a turn of the loop; the reference does."""
+    rng = np.random.default_rng(seed)
+    X, U, Y = R(rng, 120), R(rng, u), R(rng, 150)
+    g = np.concatenate([X, U, U, U, Y]).astype(np.uint8)
+    p0 = len(X); a = u - K + 1
+    assert X[-1] != U[-1] and Y[0] != U[0] and u >= K
+    In, D, C, Out = g[:p0 + K - 1], g[p0:p0 + u], g[p0 + u - K + 1:p0 + u + K - 1], g[p0 + 3 * u - K + 1:]
+    s = p0 + u + 2 + K                                                 # e0's last K-mer is D's third, e1's first D's fourth
+    G = Gb(K, 3)
+    e0 = G.add(g[:s], 0, 1); e1 = G.add(g[s - K + 1:], 1, 2)
+    c = Case(G.hbv(), [g[p0 - 30:p0 + 3 * u + 30]])                    # the patch spans the array
+    c.edges = both([In, D, C, Out])
+    # walks, in the first map alone: 150 - 120 = 30 >= 24 -> 25 on C; then ext = 60 - 13 = 47 = 5 + 19 + 5 + 18 over D C D into Out
+    c.read(g[150:210], 30, [e0, e1], 150, (25, [C, D, C, D, Out]))
+    # an offset past the first edge's end walks through the appended list [In D C D Out]: 65 -> 60 -> 41 -> 36 on Out (a sink: not tried);
+    # [In D C D C D Out], the shortest overlap, would stop on the second C
+    c.read(g[185:245], 30, [e0, e1], 185, (36, [Out]))
+    tile = lambda n: np.concatenate([g[100:p0 + u]] + [U] * (n // u + 1)).astype(np.uint8)[:n]
+    # the list goes round the cycle: entry 0; turn t adds D (a + t u K-mers), C ((t + 1) u) and Out.  ext = 20: D is expanded, C and Out cover
+    c.read(tile(39 + 20), 30, [e0], 100, (100, [In, D, C]))
+    c.read(tile(39 + 20), [30] * 39 + [0] * 20, [e0], 100, (100, [In]))                 # the same at quality 0: a tie
+    # 33 u < ext <= a + 33 u: the D of turn 33 is entry 100 and is not expanded: 101 entries, and only that D matches a read that goes on turning
+    c.read(tile(39 + a + 33 * u), 30, [e0], 100, (100, [In] + [D, C] * 33 + [D]))
+    # one base more: that D is expanded too, entries 101 and 102 exist, the reference gives up
+    c.read(tile(39 + a + 33 * u + 1), 30, [e0], 100, (100, [In]))
+    c.counters = dict(n_junctions=2, n_unipaths=4, n_tr_first=4, n_tr_walked=2, n_tr_cleared=0, n_ext_tried=5, n_ext_extended=3, n_ext_ambiguous=1, n_ext_too_many=1,
+                      n_ext_no_cover=0)
+    return c
+
+
+def hairpin(K=20, seed=15):
+    """inverted repeats.  A S rc(S) B: the middle is its own reverse complement and both strands run through it; the builder cuts it at
+    the palindromic K-mer P, so the edge E = S + 9 bases is followed by P and P by rc(E).  And A S l rc(S) B with a loop l of 5 bases:
+    the edge of S, a bubble of the loop and its reverse complement, the reverse complement of the edge of S.  One read through each"""
+    rng = np.random.default_rng(seed)
+    A, S, B = R(rng, 100), R(rng, 40), R(rng, 100)
+    B[0] = 3 - alt(A[-1])                                              # (the two strands part where the repeat ends, not a base later)
+    g = np.concatenate([A, S, rc(S), B]).astype(np.uint8)
+    A2, S2, l2, B2 = R(rng, 100), R(rng, 40), R(rng, 5), R(rng, 100)
+    B2[0] = 3 - alt(A2[-1])
+    g2 = np.concatenate([A2, S2, l2, rc(S2), B2]).astype(np.uint8)
+    assert l2.tobytes() != rc(l2).tobytes()
+    h = built(K, both([g, g2]))
+    c = Case(h)
+    Ea, E, P, Eb = g[:100 + K - 1], g[100:140 + K // 2 - 1], g[140 - K // 2:140 + K // 2], g[180 - K + 1:]
+    assert P.tobytes() == rc(P).tobytes()
+    Ea2, Es, El, Eb2 = g2[:100 + K - 1], g2[100:140], g2[140 - K + 1:145 + K - 1], g2[185 - K + 1:]
+    c.edges = both([Ea, E, Eb, Ea2, Es, El, Eb2]) + [P]
+    # ext = 150 - 59 = 91: E (30 K-mers), P (1), rc(E) (30), then Eb against rc(Ea)
+    c.read(g[60:210], 30, [edge_id(h, Ea)], 60, (60, [Ea, E, P, rc(E), Eb]))
+    # ext = 155 - 59 = 96: Es (21), the loop against its reverse complement (24), rc(Es) (21), then Eb2 against rc(Ea2)
+    c.read(g2[60:215], 30, [edge_id(h, Ea2)], 60, (60, [Ea2, Es, El, rc(Es), Eb2]))
+    c.counters = dict(n_unipaths=8, n_tr_first=2, n_ext_tried=2, n_ext_extended=2)
+    return c
+
+
+STRIDE_M = (62, 63, 64, 65, 127, 128)
+
+
+def stride(K=20, seed=14, min_gain=5):
+    """One base decides, at extension base m = 62 ... 128, once as the read's last base (ext = m + 1) and once just past it (ext = m),
+    at quality min_gain (extended) and min_gain - 1 (not), the extension starting at read base 0, 1, 2, 3 mod 4.
+    Per m a contig with two SNP bubbles, the second SNP at base m: L -> a0 | a1 -> Mid -> b0 | b1 -> R; all four combinations cover,
+    the first SNP costs 30, the second the deciding quality.  There the deciding base is always the first of its piece (the arm b);
+    so per m also a fork W -> x0 | x1 of two unrelated arms of 140 bases, read at quality 0 but for base m, where the arms differ:
+    the deciding base lies m bases inside one piece."""
+    rng = np.random.default_rng(seed)
+    seqs, bub, fork = [], [], []
+    for m in STRIDE_M:
+        g = R(rng, 100 + m + 60); p1, p2 = 100, 100 + m
+        v1 = g[p1 - K:p1 + K + 1].copy(); v1[K] = alt(g[p1])
+        v2 = g[p2 - K:p2 + K + 1].copy(); v2[K] = alt(g[p2])
+        seqs += [g, v1, v2]; bub.append((m, g, p1, p2))
+        W, x0, x1 = R(rng, 60), R(rng, 140), R(rng, 140)
+        if x1[0] == x0[0]:
+            x1[0] = alt(x0[0])
+        if x1[m] == x0[m]:
+            x1[m] = alt(x0[m])
+        seqs += [np.concatenate([W, x0]), np.concatenate([W[-K:], x1])]; fork.append((m, W, x0, x1))
+    h = built(K, both(seqs))
+    c = Case(h, min_gain=min_gain)
+    c.edges = []
+    i = 0
+    for m, g, p1, p2 in bub:
+        L, a0, Mid, b0, Rr = g[:p1], g[p1 - K + 1:p1 + K], g[p1 + 1:p2], g[p2 - K + 1:p2 + K], g[p2 + 1:]
+        a1 = a0.copy(); a1[K - 1] = alt(g[p1]); b1 = b0.copy(); b1[K - 1] = alt(g[p2])
+        c.edges += both([L, a0, a1, Mid, b0, b1, Rr])
+        for ext, q in ((m + 1, min_gain), (m + 1, min_gain - 1), (m, min_gain), (m, min_gain - 1)):
+            rstop = 40 + i % 4; i += 1
+            n = rstop + ext
+            ql = np.full(n, 30, np.uint8)
+            if ext > m:
+                ql[rstop + m] = q
+            want = [L, a0, Mid] if ext == m else [L, a0, Mid, b0] if q >= min_gain else [L]
+            c.read(g[p1 - rstop:p1 - rstop + n], ql, [edge_id(h, L)], p1 - rstop, (p1 - rstop, want))
+        if m == 64:                                                    # the read's base at the second SNP at quality 0: b1 costs nothing
+            ql = np.full(40 + m + 1, 30, np.uint8); ql[40 + m] = 0
+            c.read(g[p1 - 40:p1 + m + 1], ql, [edge_id(h, L)], p1 - 40, (p1 - 40, [L]))
+    for m, W, x0, x1 in fork:
+        e0, e1 = np.concatenate([W[-(K - 1):], x0]), np.concatenate([W[-(K - 1):], x1])
+        c.edges += both([W, e0, e1])
+        wx = np.concatenate([W, x0])
+        for ext, q in ((m + 1, min_gain), (m + 1, min_gain - 1), (m, min_gain), (m, min_gain - 1)):
+            rstop = 30 + i % 4; i += 1
+            n = rstop + ext
+            ql = np.concatenate([np.full(rstop, 30), np.zeros(ext)]).astype(np.uint8)
+            if ext > m:
+                ql[rstop + m] = q
+            want = [W, e0] if ext > m and q >= min_gain else [W]       # ext = m: base m is not the read's, both arms cost 0
+            c.read(wx[60 - rstop:60 - rstop + n], ql, [edge_id(h, W)], 60 - rstop, (60 - rstop, want))
+    nm = len(STRIDE_M)
+    c.counters = dict(n_tr_first=8 * nm + 1, n_ext_tried=8 * nm + 1, n_ext_extended=3 * nm + nm, n_ext_ambiguous=nm + 1 + 3 * nm, n_ext_too_many=0, n_ext_no_cover=0)
+    return c
+
+
+MIXED_LENS = (100, 149, 150, 151, 250, 251)
+MIXED_COUNTS = (1, 63, 64, 65, 256, 257)
+
+
+def mixed_lengths(n_reads, K=80, seed=4):
+    """`extensions`' graph, n_reads reads of 100, 149, 150, 151, 250 and 251 bases in turn: every read's byte and quality offset depends on
+    the lengths before it.  A read ends 1 ... 79 bases behind the SNP, carries either allele, the SNP at quality 30, min_gain,
+    min_gain - 1 or 0; every seventh has no path, every eleventh a negative offset"""
+    e = extensions(K, seed)
+    hs = M.edge_seqs(e.h)
+    p = 300
+    sL, sa0, sa1, sR = hs[0], hs[2], hs[4], hs[6]                      # (Gb numbers the forward edges 0, 2, 4, ...)
+    g = np.concatenate([sL, sa0[K - 1:K], sR]).astype(np.uint8)       # the genome: L, the SNP, R
+    assert len(sL) == p and len(g) == 600
+    g2 = g.copy(); g2[p] = sa1[K - 1]
+    c = Case(e.h)
+    c.edges = e.edges
+    exts = (1, 2, 3, 4, 5, 63, 64, 65, 79)
+    cnt = dict(n_tr_empty=0, n_tr_first=0, n_tr_walked=0, n_tr_cleared=0, n_ext_tried=0, n_ext_extended=0, n_ext_ambiguous=0, n_ext_no_cover=0, n_ext_too_many=0)
+    for i in range(n_reads):
+        n = MIXED_LENS[i % 6]; ext = exts[(i // 2) % len(exts)]; q = (30, 5, 4, 0)[(i // 3) % 4]; other = i % 2
+        s = p + ext - n
+        ql = np.full(n, 30, np.uint8); ql[p - s] = q
+        b = (g2 if other else g)[s:s + n]
+        if i % 7 == 3:
+            c.read(b, ql, [], i, (i, [])); cnt["n_tr_empty"] += 1
+        elif i % 11 == 5:
+            c.read(b, ql, [0], -5, (-5, [sL])); cnt["n_tr_first"] += 1
+        else:
+            c.read(b, ql, [0], s, (s, [sL, sa1 if other else sa0] if q >= 5 else [sL]))
+            cnt["n_tr_first"] += 1; cnt["n_ext_tried"] += 1; cnt["n_ext_extended" if q >= 5 else "n_ext_ambiguous"] += 1
+    c.counters = cnt
+    return c
+
+
 def cases():
-    return {"chain3": chain3, "gap_bridge": gap_bridge, "branch_patch": branch_patch, "extensions": extensions, "k_edges": k_edges,
-            "ladder_101": lambda: ladder(False), "ladder_102": lambda: ladder(True), "six_junctions": six_junctions, "short_patches": short_patches,
-            "palindrome": palindrome, "chain3_K96": lambda: chain3(96, 11), "gap_bridge_K200": lambda: gap_bridge(200, 12),
-            "empty_graph": empty_graph, "empty_graph_one_patch": lambda: empty_graph(patch=True)}
+    d = {"chain3": chain3, "gap_bridge": gap_bridge, "branch_patch": branch_patch, "extensions": extensions, "k_edges": k_edges,
+         "ladder_101": lambda: ladder(False), "ladder_102": lambda: ladder(True), "six_junctions": six_junctions, "short_patches": short_patches,
+         "palindrome": palindrome, "chain3_K96": lambda: chain3(96, 11), "gap_bridge_K200": lambda: gap_bridge(200, 12),
+         "empty_graph": empty_graph, "empty_graph_one_patch": lambda: empty_graph(patch=True),
+         "tandem": tandem, "hairpin": hairpin, "stride": stride}
+    for n in MIXED_COUNTS:
+        d[f"mixed_lengths_{n}"] = lambda n=n: mixed_lengths(n)
+    return d
 
 
 # ---- seeded random cases ------------------------------------------------------------------------------------------------------------
@@ -421,12 +581,12 @@ def get(name):
 
 
 # ---- recorded runs of the reference's builder on allx ----------------------------------------------------------------------------------
-# Recorded with `python tests/golden/make_golden.py refruns tests/test_step5_add_model.py`: naming the file records its runs only and
-# leaves every other case as it is.  (`refruns` without a file name starts from an empty refruns/ and records the tests of its own list,
-# which does not hold this file: run the line above after it.)
+# Recorded with `python tests/golden/make_golden.py refruns` (every record of the repository) or, these runs only,
+# `... refruns tests/test_step5_add_model.py`.  Twelve hand-made cases are recorded this way; every case has a record of the
+# whole call (reference_add below).
 RECORDED = ("chain3", "gap_bridge", "branch_patch", "extensions", "k_edges", "six_junctions", "short_patches", "palindrome", "chain3_K96", "gap_bridge_K200",
             "ladder_101", "ladder_102")
-# not recorded: empty_graph* (the reference's Step 3 is not run on a graph without an edge object) and random_* (hundreds of sequences each)
+# not recorded here: empty_graph* (the reference's Step 3 is not run on a graph without an edge object), random_* (hundreds of sequences each)
 INPUTS = ["t.small_K.hbv", "t.small_K.paths"]
 OUTPUTS = ["t.large_K.hbv", "t.large_K.paths"]
 
@@ -452,6 +612,107 @@ def reference_run(name, workdir):
         assert got[0] == got[1], f"{name}: the reference's result at 4 threads is not its result at 1"
     reference_outputs(f"step5_add_{name}", workdir, INPUTS, OUTPUTS, run)
     return F.read_hbv(os.path.join(workdir, OUTPUTS[0])), F.read_paths(os.path.join(workdir, OUTPUTS[1]))
+
+
+def involution(h):
+    """the involution of a graph's edge objects, by content"""
+    seqs = M.edge_seqs(h)
+    by = {s.tobytes(): i for i, s in enumerate(seqs)}
+    assert len(by) == len(seqs), "two edge objects of the graph have the same sequence"
+    return np.array([by[rc(s).tobytes()] for s in seqs], np.int32)
+
+
+# ---- recorded runs of the reference's AddNewStuff itself ------------------------------------------------------------------------------
+# tests/golden/refruns/step5_addref_<case>/: oracle/_ref/ref_step5 in mode `add` (the whole call: BuildAll, the builder, TranslatePaths,
+# Involution, ExtendPath) on the case as it stands -- new_stuff unencoded, repeats and entries below K kept, no reverse complements added.
+ADD_INPUTS = ["t.hbv", "t.inv", "t.paths", "frag_reads_orig.fastb", "frag_reads_orig.qualp", "new_stuff.fastb"]
+ADD_OUTPUTS = ["t.out.hbv", "t.out.paths", "t.out.inv"]
+# AddNewStuff's own Validate aborts when two consecutive path edges share no vertex; branch_patch's read [e0, e1] is such a path.  Its
+# second half alone (mode `tail`: TranslatePaths, resize(1), ExtendPath) runs on the recorded builder's graph and map of that case
+TAIL_INPUTS = ["t.hbv", "t.map.txt", "t.paths", "frag_reads_orig.fastb", "frag_reads_orig.qualp"]
+TAIL_OUTPUTS = ["t.out.paths"]
+TAIL_ONLY = ("branch_patch",)
+# the only cases without a record, and why: (name, reason)
+NOT_ADD_RECORDED = ()
+
+
+def add_recorded():
+    """every case that has a step5_addref_ record (mode `add`, or `tail` for TAIL_ONLY)"""
+    left_out = [n for n, _ in NOT_ADD_RECORDED]
+    return [n for n in list(cases()) + [f"random_{s}" for s in SEEDS] if n not in left_out]
+
+
+@dataclass
+class AddRecord:
+    hbv: F.HBV                    # the new graph as the reference numbered it (TAIL_ONLY: the step5_add_ record's)
+    inv: np.ndarray
+    path_offset: np.ndarray
+    path_off: np.ndarray
+    path_edges: np.ndarray
+    rebuilt: object = None        # TAIL_ONLY: the Rebuilt the tail ran on (graph, to3, left3)
+
+
+def _stage_reads(c, workdir):
+    h, paths, reads, quals, new = c.inputs()
+    F.write_paths(os.path.join(workdir, "t.paths"), *paths)
+    F.write_fastb(os.path.join(workdir, "frag_reads_orig.fastb"), *reads)
+    off = np.zeros(len(reads[2]) + 1, np.uint64); np.cumsum(reads[2], out=off[1:])
+    F.write_qualp(os.path.join(workdir, "frag_reads_orig.qualp"), quals, off)
+
+
+def reference_add(name, workdir):
+    """stages the case's files in workdir as ref_step5 reads them and puts the recorded outputs beside them (recording: the binary at 4
+    threads and at 1, which must agree on graph and paths after hbvtool's canonicalisation; the 1-thread files are kept) -> AddRecord"""
+    from conftest import reference_outputs
+    from w2rap_contigger_amd import hbvtool
+    c = get(name)
+    os.makedirs(workdir, exist_ok=True)
+    _stage_reads(c, workdir)
+    P = lambda f: os.path.join(workdir, f)
+    if name in TAIL_ONLY:
+        sub = os.path.join(workdir, "builder"); os.makedirs(sub, exist_ok=True)
+        rec_env = os.environ.pop("W2RAP_RECORD_REFERENCE", None)       # the builder's record is replayed even while this one is made:
+        try:                                                           # the tail's inputs are that record's numbering
+            B, _ = recorded_rebuilt(name, sub)
+        finally:
+            if rec_env is not None:
+                os.environ["W2RAP_RECORD_REFERENCE"] = rec_env
+        F.write_hbv(P("t.hbv"), B.hbv)
+        with open(P("t.map.txt"), "w") as fh:
+            for l3, t3 in zip(B.left3, B.to3):
+                fh.write(" ".join(str(x) for x in [l3] + t3) + "\n")
+        mode, ins, outs = "tail", TAIL_INPUTS, TAIL_OUTPUTS
+    else:
+        F.write_hbv(P("t.hbv"), c.h)
+        with open(P("t.inv"), "w") as fh:
+            fh.write("".join(f"{int(x)}\n" for x in involution(c.h)))
+        F.write_fastb(P("new_stuff.fastb"), *pack_seqs(c.new))
+        mode, ins, outs = "add", ADD_INPUTS, ADD_OUTPUTS
+
+    def run():
+        from oracle import oracle5
+        got = []
+        for threads in (4, 1):
+            out = oracle5.run_reference5(workdir, mode, threads, min_gain=c.min_gain)      # (raises when the binary exits non-zero)
+            g = F.read_hbv(P("t.out.hbv")) if mode == "add" else B.hbv
+            ch, cp, _ = hbvtool.canonicalise(g, F.read_paths(P("t.out.paths")))
+            got.append(F.hbv_to_bytes(ch, zero_padding=True) + F.paths_to_bytes(*cp))
+        assert got[0] == got[1], f"{name}: the reference's result at 4 threads is not its result at 1"
+        return out.split("REF_STEP5")[-1].strip()
+    reference_outputs(f"step5_addref_{name}", workdir, ins, outs, run)
+    po, pf, pe = F.read_paths(P("t.out.paths"))
+    if mode == "tail":
+        return AddRecord(B.hbv, B.inv, po, pf, pe, B)
+    inv = np.array(open(P("t.out.inv")).read().split(), np.int32)
+    g = F.read_hbv(P("t.out.hbv"))
+    if g.K != c.h.K:
+        # When allx holds no K-mer at all the reference's builder only Clear()s hb3 (BigKPather.cc:475-478) and AddNewStuff assigns it: the
+        # graph it writes has the K of a default HyperBasevector, 0.  The library keeps the call's K (its result stays a legal input of
+        # PartnersToEnds); such a record is read with the case's K.  Nothing else may differ in K
+        import dataclasses
+        assert g.K == 0 and g.n_edges == 0 and g.n_vertices == 0 and not any(len(s) >= c.h.K for s in list(M.edge_seqs(c.h)) + c.new)
+        g = dataclasses.replace(g, K=c.h.K)
+    return AddRecord(g, inv, po, pf, pe)
 
 
 def recorded_rebuilt(name, workdir):

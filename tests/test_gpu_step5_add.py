@@ -1,5 +1,6 @@
-"""AddNewStuff on the GPU (w2rap_step5_add_new_stuff, step5.add_new_stuff / finish) against the recorded runs of the reference's builder,
-the literal outcomes of the hand-made cases and the model (step5_add_model), array for array and counter for counter."""
+"""AddNewStuff on the GPU (w2rap_step5_add_new_stuff, step5.add_new_stuff / finish) against the recorded runs of the reference's own
+AddNewStuff (graph, involution and paths, id for id), the recorded runs of the reference's builder, the literal outcomes of the hand-made
+cases and the model (step5_add_model), array for array and counter for counter.  Records are replayed: no reference binary runs here."""
 import numpy as np
 import pytest
 
@@ -66,6 +67,29 @@ def test_library_equals_the_recorded_reference(name, tmp_path):
     assert np.array_equal(res.inv, B.inv)
     same_map(res, B.to3, B.left3)
     T.get(name).check(res)
+
+
+@pytest.mark.parametrize("name", T.add_recorded())
+def test_library_equals_the_recorded_add_new_stuff(name, tmp_path):
+    """the record's edge order replayed: the graph, the involution and every path are the reference's, id for id; without the hint they
+    are the same up to the numbering; the counters are the model's"""
+    from oracle import oracle as O
+    from w2rap_contigger_amd import hbvtool
+    rec = T.reference_add(name, str(tmp_path))
+    hc, ho = O.edge_hint_from_hbv(rec.hbv)
+    res = library(name, hint=F.pack_bases(hc, ho))
+    same_graph(res.hbv, rec.hbv)
+    assert np.array_equal(res.inv, rec.inv)
+    assert np.array_equal(res.path_offset, rec.path_offset)
+    assert np.array_equal(res.path_off, rec.path_off)
+    assert np.array_equal(res.path_edges, rec.path_edges)
+    assert res.counters == model_of(name).counters
+    plain = library(name)
+    ca, pa, _ = hbvtool.canonicalise(plain.hbv, (plain.path_offset, plain.path_off, plain.path_edges))
+    cb, pb, _ = hbvtool.canonicalise(rec.hbv, (rec.path_offset, rec.path_off, rec.path_edges))
+    same_graph(ca, cb)
+    assert all(np.array_equal(x, y) for x, y in zip(pa, pb))
+    assert plain.counters == res.counters
 
 
 @pytest.mark.parametrize("seed", T.SEEDS)

@@ -1,7 +1,7 @@
 """The yardstick of AddNewStuff on the CPU: step5_add_model (a restatement of BuildAll, TranslatePaths and ExtendPath, its graph from
-oracle3.run) against recorded runs of the reference's own builder on `allx` (tests/golden/refruns/step5_add_<case>/) and against the
-literal outcomes of the hand-made cases.  No reference binary reaches TranslatePaths or ExtendPath alone: those two rest on the model,
-the model on the literals."""
+oracle3.run) against recorded runs of the reference's own AddNewStuff (tests/golden/refruns/step5_addref_<case>/: the whole call, or
+for a case its Validate refuses TranslatePaths and ExtendPath behind the recorded builder), against recorded runs of the reference's
+builder on an encoding of `allx` (step5_add_<case>/) and against the literal outcomes of the hand-made cases."""
 import numpy as np
 import pytest
 
@@ -39,6 +39,40 @@ def test_builder_model_equals_the_recorded_reference(name, tmp_path):
     _, pb, _ = hbvtool.canonicalise(b.hbv, (b.path_offset, b.path_off, b.path_edges))
     assert all(np.array_equal(x, y) for x, y in zip(pa, pb))
     assert a.counters == b.counters
+
+
+def seq_paths(h, path_off, path_edges):
+    seqs = [x.tobytes() for x in M.edge_seqs(h)]
+    pf = np.asarray(path_off, np.int64)
+    return [[seqs[int(e)] for e in path_edges[pf[i]:pf[i + 1]]] for i in range(len(pf) - 1)]
+
+
+@pytest.mark.parametrize("name", T.add_recorded())
+def test_model_equals_the_recorded_add_new_stuff(name, tmp_path):
+    """the model against the reference's own call, numbering aside: graph, involution, every read's offset and its path in sequences;
+    and the record itself gives the case's literals"""
+    rec = T.reference_add(name, str(tmp_path))
+    c = T.get(name)
+    m = M.add_new_stuff(*c.inputs(), min_gain=c.min_gain, rebuilt=rec.rebuilt) if name in T.TAIL_ONLY else run_model(name)
+    ca, _, _ = hbvtool.canonicalise(rec.hbv)
+    cb, _, _ = hbvtool.canonicalise(m.hbv)
+    assert F.hbv_to_bytes(ca, zero_padding=True) == F.hbv_to_bytes(cb, zero_padding=True)
+    assert np.array_equal(rec.inv, T.involution(rec.hbv)) and np.array_equal(m.inv, T.involution(m.hbv))
+    assert len(rec.path_offset) == len(c.reads)
+    assert np.array_equal(rec.path_offset, m.path_offset)
+    assert seq_paths(rec.hbv, rec.path_off, rec.path_edges) == seq_paths(m.hbv, m.path_off, m.path_edges)
+    rec.counters = m.counters
+    c.check(rec)
+
+
+def test_every_case_has_a_recorded_add_new_stuff():
+    """nothing but what NOT_ADD_RECORDED names, with its reason, is left out"""
+    import os
+    from conftest import REFRUNS
+    assert all(n.startswith("empty_graph") and why for n, why in T.NOT_ADD_RECORDED)
+    for name in T.add_recorded():
+        assert os.path.exists(os.path.join(REFRUNS, f"step5_addref_{name}", "run.json")), name
+    assert set(T.add_recorded()) | {n for n, _ in T.NOT_ADD_RECORDED} == set(T.cases()) | {f"random_{s}" for s in T.SEEDS}
 
 
 @pytest.mark.parametrize("seed", T.SEEDS)
