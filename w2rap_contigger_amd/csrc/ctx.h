@@ -6,6 +6,7 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <cstdlib>
+#include <cstring>
 #include <string>
 #include <utility>
 #include <vector>
@@ -321,6 +322,18 @@ struct Timer {
 // a fresh malloc'ed GB takes a page fault per 4 KB at its first touch, which was most of the 59 ms the 0.9 GB of read paths took to come
 // down (round 5 trace: 15.7 GB/s); with huge pages the first touch is 512x rarer
 void* host_result_alloc(size_t bytes);                                  // step2_run.hip
+// ... holding a copy of a host array (null: out of memory) / zeros
+template <class T> T* host_dup(const T* src, uint64_t n) {
+    T* p = (T*)host_result_alloc((n ? n : 1) * sizeof(T));
+    if (p && n) std::memcpy(p, src, n * sizeof(T));
+    return p;
+}
+template <class T> int host_zeros(Ctx& c, T** p, uint64_t n) {
+    *p = (T*)host_result_alloc((n ? n : 1) * sizeof(T));
+    if (!*p) { c.err = "out of host memory"; return W2RAP_E_HIP; }
+    std::memset(*p, 0, (n ? n : 1) * sizeof(T));
+    return 0;
+}
 template <class T>
 inline int dl(Ctx& c, T** host, const T* dev, uint64_t n) {
     *host = (T*)host_result_alloc((n ? n : 1) * sizeof(T));
@@ -427,3 +440,34 @@ struct w2rap_step2_ctx { w2::Ctx c; };
 // that a second call in one process finds the pool of device blocks of the first
 extern "C" w2rap_step2_ctx* w2rap_step2_acquire(int device, char* err, size_t errlen);
 extern "C" void w2rap_step2_release(w2rap_step2_ctx*);
+extern "C" void w2rap_step2_destroy(w2rap_step2_ctx*);
+
+namespace w2 {
+// the per-kernel sums of everything queued on the context's stream so far, as the w2rap_*_profile calls of Steps 3-5 and the GFA dump
+// give them: "kernel_name total_ms launches\n" lines
+inline std::string profile_text(Ctx& c) {
+    (void)hipStreamSynchronize(c.stream);
+    c.presolve();
+    std::string text;
+    for (auto& s : c.prof_sums) { char line[256]; std::snprintf(line, sizeof line, "%s %.4f %llu\n", s.name.c_str(), s.ms, (unsigned long long)s.launches); text += line; }
+    return text;
+}
+// What a one-shot entry does once its arguments have passed: a context from the cache runs body(c); save_profile(c) keeps its kernel
+// times; a failed context is destroyed, not cached, and only then free_out() gives up what the body left in `out`.
+// Returns body's code, its message (c.err) in `err`
+template <class Body, class Save, class Free>
+int one_shot(int device, char* err, size_t errlen, Body body, Save save_profile, Free free_out) {
+    auto fail = [&](int code, const std::string& m) { if (err && errlen) std::snprintf(err, errlen, "%s", m.c_str()); return code; };
+    char ebuf[512] = {0};
+    w2rap_step2_ctx* h = w2rap_step2_acquire(device, ebuf, sizeof ebuf);
+    if (!h) return fail(W2RAP_E_NO_DEVICE, ebuf);
+    Ctx& c = h->c;
+    c.prof_sums.clear();
+    const int rc = body(c);
+    const std::string msg = c.err;
+    save_profile(c);
+    if (rc) w2rap_step2_destroy(h); else w2rap_step2_release(h);
+    if (rc) { free_out(); return fail(rc, msg); }
+    return 0;
+}
+}  // namespace w2

@@ -391,10 +391,7 @@ int w2rap_gfa_dump(const w2rap_gfa_in* in, const w2rap_gfa_params* P, w2rap_gfa_
     if (!h) return fail(W2RAP_E_NO_DEVICE, ebuf);
     int rc = gfa(h->c, *in, *P, *out);
     std::string msg = h->c.err;
-    (void)hipStreamSynchronize(h->c.stream);
-    h->c.presolve();
-    g_profile_gfa.clear();
-    for (auto& s : h->c.prof_sums) { char line[256]; std::snprintf(line, sizeof line, "%s %.4f %llu\n", s.name.c_str(), s.ms, (unsigned long long)s.launches); g_profile_gfa += line; }
+    g_profile_gfa = profile_text(h->c);
     if (rc) w2rap_step2_destroy(h); else w2rap_step2_release(h);     // (a failed context is not cached)
     if (rc) { w2rap_gfa_free(out); return fail(rc, msg); }
     return 0;

@@ -34,12 +34,12 @@
 #include <cstring>
 #include <string>
 #include <vector>
+#include "args.h"
 #include "ctx.h"
 #include "../../include/w2rap_step3.h"
 #include "step3_back.h"
 
 extern "C" w2rap_step2_ctx* w2rap_step2_create(int device, char* err, size_t errlen);
-extern "C" void w2rap_step2_destroy(w2rap_step2_ctx*);
 
 namespace w2 {
 namespace {
@@ -2118,12 +2118,7 @@ int step3(Ctx& c, const DevIn& in, const w2rap_step3_params& P, w2rap_step3_out&
 
 using namespace w2;
 
-static void save_profile(Ctx& c) {      // per-kernel times of this run -> w2rap_step3_profile
-    (void)hipStreamSynchronize(c.stream);
-    c.presolve();
-    g_profile.clear();
-    for (auto& s : c.prof_sums) { char line[256]; std::snprintf(line, sizeof line, "%s %.4f %llu\n", s.name.c_str(), s.ms, (unsigned long long)s.launches); g_profile += line; }
-}
+static void save_profile(Ctx& c) { g_profile = profile_text(c); }      // per-kernel times of this run -> w2rap_step3_profile
 
 extern "C" {
 
@@ -2141,24 +2136,15 @@ int w2rap_step3_run(const w2rap_step3_in* in, const w2rap_step3_params* P, w2rap
     if (in->n_edge_objs >= (1ull << 31) || in->n_paths >= (1ull << 32) - 2) return fail(W2RAP_E_LIMIT, "more than 2^31 edge objects or 2^32 reads");
     if ((in->n_edge_objs && (!in->edge_packed || !in->edge_byte_off || !in->edge_len)) || (in->n_paths && (!in->path_offset || !in->path_off)))
         return fail(W2RAP_E_ARG, "null input array");
-    if (in->n_paths && in->path_off[0] != 0) return fail(W2RAP_E_ARG, "path_off must start at 0");
-    if (in->n_paths && in->path_off[in->n_paths] && !in->path_edges) return fail(W2RAP_E_ARG, "null path_edges");
-    if (in->n_edge_objs && in->edge_byte_off[0] != 0) return fail(W2RAP_E_ARG, "edge_byte_off must start at 0");
-    for (uint64_t r = 0; r < in->n_paths; ++r) {
-        if (in->path_off[r + 1] < in->path_off[r]) return fail(W2RAP_E_ARG, "path_off is not ascending");
-    }
+    // (the shared pieces of args.h, in the order this entry has always had: the paths in front of the edges)
+    W2_ARGS(args::path_off_start(*in));
+    W2_ARGS(args::null_path_edges(*in));
+    W2_ARGS(args::edge_off_start(*in));
+    W2_ARGS(args::path_off_ascends(*in));
+    W2_ARGS(args::path_entries(*in));
+    W2_ARGS(args::edge_lens(*in));
     const uint64_t npe = in->n_paths ? in->path_off[in->n_paths] : 0;
-    for (uint64_t i = 0; i < npe; ++i) if (in->path_edges[i] < 0 || (uint64_t)in->path_edges[i] >= in->n_edge_objs) return fail(W2RAP_E_ARG, "a path names an edge object that does not exist");
-    for (uint64_t o = 0; o < in->n_edge_objs; ++o) {
-        if (in->edge_len[o] < (uint32_t)in->K) return fail(W2RAP_E_ARG, "an edge object shorter than K bases");
-        if (in->edge_byte_off[o + 1] < in->edge_byte_off[o] || in->edge_byte_off[o + 1] - in->edge_byte_off[o] != ((uint64_t)in->edge_len[o] + 3) / 4)
-            return fail(W2RAP_E_ARG, "edge_byte_off does not match edge_len");
-    }
-    char ebuf[512] = {0};
-    w2rap_step2_ctx* h = w2rap_step2_acquire(P->device, ebuf, sizeof ebuf);
-    if (!h) return fail(W2RAP_E_NO_DEVICE, ebuf);
-    Ctx& c = h->c;
-    auto body = [&]() -> int {
+    auto body = [&](Ctx& c) -> int {
         uint8_t* obits = nullptr; uint64_t* obyte = nullptr; uint32_t* olen = nullptr; int32_t *p_offset = nullptr, *p_edges = nullptr; uint64_t* p_off = nullptr;
         const uint64_t NO = in->n_edge_objs, n = in->n_paths;
         W2_TRY(up_pooled(c, &obits, in->edge_packed, NO ? in->edge_byte_off[NO] : 0, 32));
@@ -2173,12 +2159,7 @@ int w2rap_step3_run(const w2rap_step3_in* in, const w2rap_step3_params* P, w2rap
         if (P->extend_paths && NO) { W2_TRY(up_pooled(c, &vleft, in->vleft, NO)); W2_TRY(up_pooled(c, &vright, in->vright, NO)); }
         return step3(c, DevIn{(unsigned)in->K, NO, obits, obyte, olen, n, p_offset, p_off, p_edges, in->n_vertices, vleft, vright}, *P, *out);
     };
-    int rc = body();
-    std::string msg = c.err;
-    save_profile(c);
-    if (rc) w2rap_step2_destroy(h); else w2rap_step2_release(h);     // (a failed context is not cached)
-    if (rc) { w2rap_step3_free(out); return fail(rc, msg); }
-    return 0;
+    return one_shot(P->device, err, errlen, body, save_profile, [&] { w2rap_step3_free(out); });
 }
 
 // Step 3 straight behind Step 2 in one process (the reference's default flow, w2rap-contigger.cc:338-371): the graph and the read

@@ -21,6 +21,7 @@
 #include <cstring>
 #include <string>
 #include <vector>
+#include "args.h"
 #include "step4_edit.h"
 #include "../../include/w2rap_step4.h"
 
@@ -304,21 +305,11 @@ __global__ __launch_bounds__(256) void k4_path_write(uint64_t n, const uint64_t*
     noffs[r] = off;
 }
 
-template <class T> T* host_copy(const std::vector<T>& v) {
-    T* p = (T*)host_result_alloc((v.size() ? v.size() : 1) * sizeof(T));
-    if (p && !v.empty()) std::memcpy(p, v.data(), v.size() * sizeof(T));
-    return p;
-}
-
 std::string g_profile4;
 
 // per-kernel times of this run and which editor ran -> w2rap_step4_profile
 void save_profile4(Ctx& c, bool on_device) {
-    (void)hipStreamSynchronize(c.stream);
-    c.presolve();
-    g_profile4.clear();
-    for (auto& s : c.prof_sums) { char line[256]; std::snprintf(line, sizeof line, "%s %.4f %llu\n", s.name.c_str(), s.ms, (unsigned long long)s.launches); g_profile4 += line; }
-    { char line[64]; std::snprintf(line, sizeof line, "edit_path_device %d %d\n", on_device ? 1 : 0, on_device ? 2 : 0); g_profile4 += line; }
+    g_profile4 = profile_text(c) + (on_device ? "edit_path_device 1 2\n" : "edit_path_device 0 0\n");
 }
 
 struct Ms { float index = 0, vote = 0, paths = 0, host = 0; };
@@ -428,11 +419,8 @@ int upload(Ctx& c, const w2rap_step4_in& in, Graph4& g, ReadsDev& R, PathsDev& P
     hg.K = in.K;
     std::vector<int> inv;
     if (!in.inv) { unpack_edges(E, in.edge_packed, in.edge_byte_off, in.edge_len, hg.edges); W2_TRY(host_involution(hg, inv, c.err)); }
-    std::vector<int32_t> vleft(E, -1), vright(E, -1), to_v(E, -1);
-    for (uint64_t v = 0; v < NV; ++v) {
-        for (uint64_t i = in.from_off[v]; i < in.from_off[v + 1]; ++i) vleft[in.from_e[i]] = (int32_t)v;
-        for (uint64_t i = in.to_off[v]; i < in.to_off[v + 1]; ++i) vright[in.to_e[i]] = (int32_t)v;
-    }
+    std::vector<int32_t> vleft, vright, to_v(E, -1);
+    args::edge_ends(in, vleft, vright);
     for (uint64_t i = 0; i < E; ++i) to_v[i] = vleft[in.to_e[i]];
     g = Graph4{}; g.K = (unsigned)in.K; g.E = E; g.NV = NV; g.ebytes_cap = E ? in.edge_byte_off[E] : 0;
     W2_TRY(upload_graph4(c, g, in.edge_packed, in.edge_byte_off, in.edge_len, in.from_off, in.from_v, in.from_e, in.to_off, to_v.data(), in.to_e,
@@ -571,7 +559,7 @@ int download(Ctx& c, const Graph4& g, const PathsDev& pd, const std::vector<int3
     W2_HIP(hipStreamSynchronize(c.stream));
     W2_TRY(dl(c, &out.edge_packed, (const uint8_t*)g.ebits, out.edge_byte_off[E]));
     for (int k = 0; k < 2; ++k) {
-        out.n_deleted[k] = deleted[k].size(); out.deleted[k] = host_copy(deleted[k]);
+        out.n_deleted[k] = deleted[k].size(); out.deleted[k] = host_dup(deleted[k].data(), deleted[k].size());
         out.ms_index[k] = ms[k].index; out.ms_vote[k] = ms[k].vote; out.ms_paths[k] = ms[k].paths; out.ms_graph_edit_host[k] = ms[k].host;
     }
     out.n_paths = pd.n;
@@ -616,74 +604,36 @@ int w2rap_step4_run(const w2rap_step4_in* in, const w2rap_step4_params* P, w2rap
     std::memset(out, 0, sizeof(*out));
     if (in->K < 16 || in->K > 640) return fail(W2RAP_E_ARG, "K must be in [16, 640] (the reference runs Step 4 at the large K, 200 by default)");
     if (P->flags & ~(W2RAP_STEP4_VOTE_ONLY | W2RAP_STEP4_EDIT_ON_HOST)) return fail(W2RAP_E_ARG, "unknown flag");
-    const uint64_t E = in->n_edge_objs, NV = in->n_vertices, n = in->n_paths;
-    if (E >= (1ull << 31) || NV >= (1ull << 31) || n >= (1ull << 32) - 2) return fail(W2RAP_E_LIMIT, "more than 2^31 edge objects or vertices, or 2^32 reads");
-    if (in->n_reads != n) return fail(W2RAP_E_ARG, "n_reads differs from n_paths: Step 4 needs the bases and qualities of every pathed read");
-    if (E && (!in->edge_packed || !in->edge_byte_off || !in->edge_len || !in->from_v || !in->from_e || !in->to_e)) return fail(W2RAP_E_ARG, "null graph array");
-    if (NV && (!in->from_off || !in->to_off)) return fail(W2RAP_E_ARG, "null adjacency offsets");
-    if (E && !NV) return fail(W2RAP_E_ARG, "edge objects without vertices");
-    if (n && (!in->path_offset || !in->path_off || !in->read_byte_off || !in->read_len || !in->qual_off)) return fail(W2RAP_E_ARG, "null input array");
-    if (E && in->edge_byte_off[0] != 0) return fail(W2RAP_E_ARG, "edge_byte_off must start at 0");
-    for (uint64_t o = 0; o < E; ++o) {
-        if (in->edge_len[o] < (uint32_t)in->K) return fail(W2RAP_E_ARG, "an edge object shorter than K bases");
-        if (in->edge_byte_off[o + 1] < in->edge_byte_off[o] || in->edge_byte_off[o + 1] - in->edge_byte_off[o] != ((uint64_t)in->edge_len[o] + 3) / 4)
-            return fail(W2RAP_E_ARG, "edge_byte_off does not match edge_len");
-    }
-    if (NV) {
-        if (in->from_off[0] != 0 || in->to_off[0] != 0) return fail(W2RAP_E_ARG, "from_off / to_off must start at 0");
-        for (uint64_t v = 0; v < NV; ++v) if (in->from_off[v + 1] < in->from_off[v] || in->to_off[v + 1] < in->to_off[v]) return fail(W2RAP_E_ARG, "from_off / to_off is not ascending");
-        if (in->from_off[NV] != E || in->to_off[NV] != E) return fail(W2RAP_E_ARG, "the adjacency lists do not hold every edge object once");
-        std::vector<char> sf(E, 0), st(E, 0);
-        for (uint64_t i = 0; i < E; ++i) {
-            if (in->from_v[i] < 0 || (uint64_t)in->from_v[i] >= NV) return fail(W2RAP_E_ARG, "from_v names a vertex that does not exist");
-            if (in->from_e[i] < 0 || (uint64_t)in->from_e[i] >= E || in->to_e[i] < 0 || (uint64_t)in->to_e[i] >= E) return fail(W2RAP_E_ARG, "the adjacency lists name an edge object that does not exist");
-            if (sf[in->from_e[i]]++ || st[in->to_e[i]]++) return fail(W2RAP_E_ARG, "the adjacency lists do not hold every edge object once");
-        }
-        std::vector<int32_t> right(E, -1);
-        for (uint64_t v = 0; v < NV; ++v) for (uint64_t i = in->to_off[v]; i < in->to_off[v + 1]; ++i) right[in->to_e[i]] = (int32_t)v;
-        for (uint64_t i = 0; i < E; ++i) if (right[in->from_e[i]] != in->from_v[i]) return fail(W2RAP_E_ARG, "from_v and to_e disagree about the vertex an edge enters");
-    }
+    const uint64_t E = in->n_edge_objs;
+    if (args::too_large(*in, args::READS_END)) return fail(W2RAP_E_LIMIT, args::TOO_LARGE);
+    if (in->n_reads != in->n_paths) return fail(W2RAP_E_ARG, "n_reads differs from n_paths: Step 4 needs the bases and qualities of every pathed read");
+    W2_ARGS(args::null_arrays(*in));
+    W2_ARGS(args::edge_off_start(*in));
+    W2_ARGS(args::edge_lens(*in));
+    W2_ARGS(args::adjacency(*in));
+    W2_ARGS(args::from_v_agrees(*in));
     if (in->inv) for (uint64_t e = 0; e < E; ++e) {
         if (in->inv[e] < 0 || (uint64_t)in->inv[e] >= E || in->inv[in->inv[e]] != (int32_t)e) return fail(W2RAP_E_ARG, "inv is not an involution of the edge objects");
         if (in->edge_len[in->inv[e]] != in->edge_len[e]) return fail(W2RAP_E_ARG, "inv pairs edge objects of different lengths");
     }
-    if (n) {
-        if (in->path_off[0] != 0 || in->read_byte_off[0] != 0 || in->qual_off[0] != 0) return fail(W2RAP_E_ARG, "path_off, read_byte_off and qual_off must start at 0");
-        for (uint64_t r = 0; r < n; ++r) {
-            if (in->path_off[r + 1] < in->path_off[r]) return fail(W2RAP_E_ARG, "path_off is not ascending");
-            if (in->read_byte_off[r + 1] < in->read_byte_off[r] || in->read_byte_off[r + 1] - in->read_byte_off[r] != ((uint64_t)in->read_len[r] + 3) / 4)
-                return fail(W2RAP_E_ARG, "read_byte_off does not match read_len");
-            if (in->qual_off[r + 1] < in->qual_off[r] || in->qual_off[r + 1] - in->qual_off[r] != in->read_len[r]) return fail(W2RAP_E_ARG, "qual_off does not match read_len");
-        }
-        const uint64_t npe = in->path_off[n];
-        if (npe && !in->path_edges) return fail(W2RAP_E_ARG, "null path_edges");
-        if (in->read_byte_off[n] && !in->read_packed) return fail(W2RAP_E_ARG, "null read_packed");
-        if (in->qual_off[n] && !in->quals) return fail(W2RAP_E_ARG, "null quals");
-        for (uint64_t i = 0; i < npe; ++i) if (in->path_edges[i] < 0 || (uint64_t)in->path_edges[i] >= E) return fail(W2RAP_E_ARG, "a path names an edge object that does not exist");
-    }
-    char ebuf[512] = {0};
-    w2rap_step2_ctx* h = w2rap_step2_acquire(P->device, ebuf, sizeof ebuf);
-    if (!h) return fail(W2RAP_E_NO_DEVICE, ebuf);
-    Ctx& c = h->c;
-    c.prof_sums.clear();
+    W2_ARGS(args::reads_and_paths(*in));
     // VOTE_ONLY edits nothing, on either path
     bool on_device = !(P->flags & (W2RAP_STEP4_EDIT_ON_HOST | W2RAP_STEP4_VOTE_ONLY));
-    int rc = step4(c, *in, *P, on_device, *out);
-    if (rc == EDIT4_FALLBACK) {                                  // start over with the host edit: same result, nothing kept from this attempt
-        on_device = false;
-        (void)hipStreamSynchronize(c.stream);
-        c.presolve();
-        c.prof_sums.clear();
-        c.free_all();
-        c.err.clear();
-        w2rap_step4_free(out);
-        rc = step4(c, *in, *P, false, *out);
-    }
-    std::string msg = c.err;
-    save_profile4(c, on_device);
-    if (rc) w2rap_step2_destroy(h); else w2rap_step2_release(h);     // (a failed context is not cached)
-    if (rc) { w2rap_step4_free(out); return fail(rc, msg); }
-    return 0;
+    auto body = [&](Ctx& c) -> int {
+        int rc = step4(c, *in, *P, on_device, *out);
+        if (rc == EDIT4_FALLBACK) {                              // start over with the host edit: same result, nothing kept from this attempt
+            on_device = false;
+            (void)hipStreamSynchronize(c.stream);
+            c.presolve();
+            c.prof_sums.clear();
+            c.free_all();
+            c.err.clear();
+            w2rap_step4_free(out);
+            rc = step4(c, *in, *P, false, *out);
+        }
+        return rc;
+    };
+    return one_shot(P->device, err, errlen, body, [&](Ctx& c) { save_profile4(c, on_device); }, [&] { w2rap_step4_free(out); });
 }
 
 // Step 4 straight behind Step 3 in one process (the reference's default flow, w2rap-contigger.cc:395-399 on the objects Steps 1-3 left in

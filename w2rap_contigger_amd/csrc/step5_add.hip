@@ -20,13 +20,10 @@
 #include <vector>
 #include "ctx.h"
 #include "step3_back.h"
+#include "step5_runs.h"
 #include "../../include/w2rap_step5.h"
 
-extern "C" void w2rap_step2_destroy(w2rap_step2_ctx*);
-
 namespace w2 {
-void save_profile5(Ctx& c);          // step5_partners.hip
-
 namespace {
 
 static inline unsigned grid_a(uint64_t n) { return (unsigned)((n + 255) / 256); }
@@ -451,65 +448,23 @@ int w2rap_step5_add_new_stuff(const w2rap_step5_in* in, uint64_t n_new, const ui
     if (P->ext_mode != 1) return fail(W2RAP_E_ARG, "ext_mode must be 1: ExtendPath's mode 2 is not built");
     if (P->min_gain < 1) return fail(W2RAP_E_ARG, "min_gain must be at least 1: below it a tie for the best extension would extend, by an order the reference leaves unspecified");
     if (P->flags & ~W2RAP_STEP5_ADD_KEEP_MAP) return fail(W2RAP_E_ARG, "unknown flag");
-    const uint64_t E = in->n_edge_objs, NV = in->n_vertices, n = in->n_paths;
-    if (E >= (1ull << 31) || NV >= (1ull << 31) || n >= (1ull << 32) - 2 || n_new >= (1ull << 31)) return fail(W2RAP_E_LIMIT, "more than 2^31 edge objects, vertices or patches, or 2^32 reads");
-    if (in->n_reads != n) return fail(W2RAP_E_ARG, "n_reads differs from n_paths: ExtendPath needs the bases and qualities of every read");
-    if (E && (!in->edge_packed || !in->edge_byte_off || !in->edge_len || !in->from_v || !in->from_e || !in->to_e)) return fail(W2RAP_E_ARG, "null graph array");
-    if (NV && (!in->from_off || !in->to_off)) return fail(W2RAP_E_ARG, "null adjacency offsets");
-    if (E && !NV) return fail(W2RAP_E_ARG, "edge objects without vertices");
-    if (n && (!in->path_offset || !in->path_off || !in->read_byte_off || !in->read_len || !in->qual_off)) return fail(W2RAP_E_ARG, "null input array");
+    if (args::too_large(*in, args::READS_END) || n_new >= (1ull << 31)) return fail(W2RAP_E_LIMIT, "more than 2^31 edge objects, vertices or patches, or 2^32 reads");
+    if (in->n_reads != in->n_paths) return fail(W2RAP_E_ARG, "n_reads differs from n_paths: ExtendPath needs the bases and qualities of every read");
+    W2_ARGS(args::null_arrays(*in));
     if (n_new && (!new_byte_off || !new_len)) return fail(W2RAP_E_ARG, "null new_stuff array");
-    if (E && in->edge_byte_off[0] != 0) return fail(W2RAP_E_ARG, "edge_byte_off must start at 0");
-    for (uint64_t o = 0; o < E; ++o) {
-        if (in->edge_len[o] < (uint32_t)in->K) return fail(W2RAP_E_ARG, "an edge object shorter than K bases");
-        if (in->edge_byte_off[o + 1] < in->edge_byte_off[o] || in->edge_byte_off[o + 1] - in->edge_byte_off[o] != ((uint64_t)in->edge_len[o] + 3) / 4)
-            return fail(W2RAP_E_ARG, "edge_byte_off does not match edge_len");
-    }
+    W2_ARGS(args::edge_off_start(*in));
+    W2_ARGS(args::edge_lens(*in));
     if (n_new) {
         if (new_byte_off[0] != 0) return fail(W2RAP_E_ARG, "new_byte_off must start at 0");
         for (uint64_t i = 0; i < n_new; ++i)
             if (new_byte_off[i + 1] < new_byte_off[i] || new_byte_off[i + 1] - new_byte_off[i] != ((uint64_t)new_len[i] + 3) / 4) return fail(W2RAP_E_ARG, "new_byte_off does not match new_len");
         if (new_byte_off[n_new] && !new_packed) return fail(W2RAP_E_ARG, "null new_packed");
     }
-    if (NV) {
-        if (in->from_off[0] != 0 || in->to_off[0] != 0) return fail(W2RAP_E_ARG, "from_off / to_off must start at 0");
-        for (uint64_t v = 0; v < NV; ++v) if (in->from_off[v + 1] < in->from_off[v] || in->to_off[v + 1] < in->to_off[v]) return fail(W2RAP_E_ARG, "from_off / to_off is not ascending");
-        if (in->from_off[NV] != E || in->to_off[NV] != E) return fail(W2RAP_E_ARG, "the adjacency lists do not hold every edge object once");
-        std::vector<char> sf(E, 0), stt(E, 0);
-        for (uint64_t i = 0; i < E; ++i) {
-            if (in->from_v[i] < 0 || (uint64_t)in->from_v[i] >= NV) return fail(W2RAP_E_ARG, "from_v names a vertex that does not exist");
-            if (in->from_e[i] < 0 || (uint64_t)in->from_e[i] >= E || in->to_e[i] < 0 || (uint64_t)in->to_e[i] >= E) return fail(W2RAP_E_ARG, "the adjacency lists name an edge object that does not exist");
-            if (sf[in->from_e[i]]++ || stt[in->to_e[i]]++) return fail(W2RAP_E_ARG, "the adjacency lists do not hold every edge object once");
-        }
-        for (uint64_t v = 0; v < NV; ++v)
-            if ((in->to_off[v + 1] - in->to_off[v]) * (in->from_off[v + 1] - in->from_off[v]) >= (1ull << 32)) return fail(W2RAP_E_LIMIT, "more than 2^32 crossings of one vertex");
-    }
-    if (n) {
-        if (in->path_off[0] != 0 || in->read_byte_off[0] != 0 || in->qual_off[0] != 0) return fail(W2RAP_E_ARG, "path_off, read_byte_off and qual_off must start at 0");
-        for (uint64_t r = 0; r < n; ++r) {
-            if (in->path_off[r + 1] < in->path_off[r]) return fail(W2RAP_E_ARG, "path_off is not ascending");
-            if (in->read_byte_off[r + 1] < in->read_byte_off[r] || in->read_byte_off[r + 1] - in->read_byte_off[r] != ((uint64_t)in->read_len[r] + 3) / 4)
-                return fail(W2RAP_E_ARG, "read_byte_off does not match read_len");
-            if (in->qual_off[r + 1] < in->qual_off[r] || in->qual_off[r + 1] - in->qual_off[r] != in->read_len[r]) return fail(W2RAP_E_ARG, "qual_off does not match read_len");
-            if (in->read_len[r] >= (1u << 31)) return fail(W2RAP_E_LIMIT, "a read of 2^31 bases");
-        }
-        const uint64_t npe = in->path_off[n];
-        if (npe && !in->path_edges) return fail(W2RAP_E_ARG, "null path_edges");
-        if (in->read_byte_off[n] && !in->read_packed) return fail(W2RAP_E_ARG, "null read_packed");
-        if (in->qual_off[n] && !in->quals) return fail(W2RAP_E_ARG, "null quals");
-        for (uint64_t i = 0; i < npe; ++i) if (in->path_edges[i] < 0 || (uint64_t)in->path_edges[i] >= E) return fail(W2RAP_E_ARG, "a path names an edge object that does not exist");
-    }
-    char ebuf[512] = {0};
-    w2rap_step2_ctx* h = w2rap_step2_acquire(P->device, ebuf, sizeof ebuf);
-    if (!h) return fail(W2RAP_E_NO_DEVICE, ebuf);
-    Ctx& c = h->c;
-    c.prof_sums.clear();
-    const int rc = add_new_stuff(c, *in, n_new, new_packed, new_byte_off, new_len, *P, *out);
-    const std::string msg = c.err;
-    save_profile5(c);
-    if (rc) w2rap_step2_destroy(h); else w2rap_step2_release(h);     // (a failed context is not cached)
-    if (rc) { w2rap_step5_add_free(out); return fail(rc, msg); }
-    return 0;
+    W2_ARGS(args::adjacency(*in));
+    W2_ARGS(args::crossings(*in));
+    W2_ARGS(args::reads_and_paths(*in, [&](uint64_t r) { return in->read_len[r] >= (1u << 31) ? args::Err{W2RAP_E_LIMIT, "a read of 2^31 bases"} : args::OK; }));
+    return one_shot(P->device, err, errlen, [&](Ctx& c) { return add_new_stuff(c, *in, n_new, new_packed, new_byte_off, new_len, *P, *out); }, save_profile5,
+                    [&] { w2rap_step5_add_free(out); });
 }
 
 void w2rap_step5_add_free(w2rap_step5_add_out* o) {

@@ -216,13 +216,6 @@ __global__ __launch_bounds__(256) void k5o_layout_out(uint64_t n, const uint64_t
 }
 
 // ---- the host side -------------------------------------------------------------------------------------------------------------
-template <class T> int host_zeros(Ctx& c, T** p, uint64_t n) {
-    *p = (T*)host_result_alloc((n ? n : 1) * sizeof(T));
-    if (!*p) { c.err = "out of host memory"; return W2RAP_E_HIP; }
-    std::memset(*p, 0, (n ? n : 1) * sizeof(T));
-    return 0;
-}
-
 struct Dev {                                                   // the inputs on the device (each part uploads what it reads)
     uint64_t* poff = nullptr; int32_t* pe = nullptr; int32_t* inv = nullptr;
 };
@@ -253,11 +246,8 @@ int open_links(Ctx& c, const w2rap_step5_open_in& in, const Dev& d, w2rap_step5_
     };
     if (!NP || !E) return empty();
     // each edge's two vertices, from the adjacency lists (the argument checks have seen every edge once in each)
-    std::vector<int32_t> vleft(E, -1), vright(E, -1);
-    for (uint64_t v = 0; v < NV; ++v) {
-        for (uint64_t i = in.from_off[v]; i < in.from_off[v + 1]; ++i) vleft[in.from_e[i]] = (int32_t)v;
-        for (uint64_t i = in.to_off[v]; i < in.to_off[v + 1]; ++i) vright[in.to_e[i]] = (int32_t)v;
-    }
+    std::vector<int32_t> vleft, vright;
+    args::edge_ends(in, vleft, vright);
     int32_t *d_vleft = nullptr, *d_vright = nullptr, *d_from_v = nullptr; uint64_t* d_from_off = nullptr;
     W2_TRY(up_pooled(c, &d_vleft, (const int32_t*)vleft.data(), E)); W2_TRY(up_pooled(c, &d_vright, (const int32_t*)vright.data(), E));
     W2_TRY(up_pooled(c, &d_from_off, in.from_off, NV + 1)); W2_TRY(up_pooled(c, &d_from_v, in.from_v, E));
@@ -382,38 +372,19 @@ int opening(Ctx& c, const w2rap_step5_open_in& in, uint32_t parts, w2rap_step5_o
 
 // The argument checks: 0, or W2RAP_E_ARG with the message in `err`.  Everything a kernel uses as an index is looked at here
 int open_check(const w2rap_step5_open_in* in, const w2rap_step5_params* P, char* err, size_t errlen) {
-    auto fail = [&](const char* m) { if (err && errlen) std::snprintf(err, errlen, "%s", m); return (int)W2RAP_E_ARG; };
-    if (!in || !P) return fail("null argument");
-    if (P->flags & ~(W2RAP_STEP5_OPEN_INDEX | W2RAP_STEP5_OPEN_LINKS | W2RAP_STEP5_OPEN_LAYOUT)) return fail("unknown flag");
-    if (in->K < 16 || in->K > 640) return fail("K must be in [16, 640]");
-    const uint64_t E = in->n_edge_objs, NV = in->n_vertices, n = in->n_paths;
-    if (E >= (1ull << 31) || NV >= (1ull << 31) || n >= (1ull << 30)) return fail("more than 2^31 edge objects or vertices, or 2^30 reads: ids are 32-bit");
-    if (n & 1) return fail("n_paths is odd: reads r and r ^ 1 are mates");
-    if (E && (!in->edge_len || !in->from_v || !in->from_e || !in->to_e || !in->inv)) return fail("null graph array");
-    if (NV && (!in->from_off || !in->to_off)) return fail("null adjacency offsets");
-    if (E && !NV) return fail("edge objects without vertices");
-    if (n && (!in->path_offset || !in->path_off || !in->read_len)) return fail("null input array");
-    for (uint64_t o = 0; o < E; ++o) if (in->edge_len[o] < (uint32_t)in->K || in->edge_len[o] >= (1u << 31)) return fail("an edge object shorter than K bases");
-    if (NV) {
-        if (in->from_off[0] != 0 || in->to_off[0] != 0) return fail("from_off / to_off must start at 0");
-        for (uint64_t v = 0; v < NV; ++v) if (in->from_off[v + 1] < in->from_off[v] || in->to_off[v + 1] < in->to_off[v]) return fail("from_off / to_off is not ascending");
-        if (in->from_off[NV] != E || in->to_off[NV] != E) return fail("the adjacency lists do not hold every edge object once");
-        std::vector<char> sf(E, 0), st(E, 0);
-        for (uint64_t i = 0; i < E; ++i) {
-            if (in->from_v[i] < 0 || (uint64_t)in->from_v[i] >= NV) return fail("from_v names a vertex that does not exist");
-            if (in->from_e[i] < 0 || (uint64_t)in->from_e[i] >= E || in->to_e[i] < 0 || (uint64_t)in->to_e[i] >= E) return fail("the adjacency lists name an edge object that does not exist");
-            if (sf[in->from_e[i]]++ || st[in->to_e[i]]++) return fail("the adjacency lists do not hold every edge object once");
-        }
-    }
-    for (uint64_t e = 0; e < E; ++e) if (in->inv[e] < 0 || (uint64_t)in->inv[e] >= E) return fail("inv names an edge object that does not exist");
-    for (uint64_t e = 0; e < E; ++e) if ((uint64_t)in->inv[in->inv[e]] != e) return fail("inv is not an involution: inv[inv[e]] != e");
-    if (n) {
-        if (in->path_off[0] != 0) return fail("path_off must start at 0");
-        for (uint64_t r = 0; r < n; ++r) if (in->path_off[r + 1] < in->path_off[r]) return fail("path_off is not ascending");
-        const uint64_t npe = in->path_off[n];
-        if (npe && !in->path_edges) return fail("null path_edges");
-        for (uint64_t i = 0; i < npe; ++i) if (in->path_edges[i] < 0 || (uint64_t)in->path_edges[i] >= E) return fail("a path names an edge object that does not exist");
-    }
+    auto fail = [&](int code, const char* m) { if (err && errlen) std::snprintf(err, errlen, "%s", m); return code; };
+    if (!in || !P) return fail(W2RAP_E_ARG, "null argument");
+    if (P->flags & ~(W2RAP_STEP5_OPEN_INDEX | W2RAP_STEP5_OPEN_LINKS | W2RAP_STEP5_OPEN_LAYOUT)) return fail(W2RAP_E_ARG, "unknown flag");
+    if (in->K < 16 || in->K > 640) return fail(W2RAP_E_ARG, "K must be in [16, 640]");
+    const uint64_t E = in->n_edge_objs;
+    if (args::too_large(*in, 1ull << 30)) return fail(W2RAP_E_ARG, "more than 2^31 edge objects or vertices, or 2^30 reads: ids are 32-bit");
+    if (in->n_paths & 1) return fail(W2RAP_E_ARG, args::ODD_PATHS);
+    W2_ARGS(args::null_arrays(*in, !in->inv));
+    W2_ARGS(args::edge_lens(*in, 1ull << 31));
+    W2_ARGS(args::adjacency(*in));
+    for (uint64_t e = 0; e < E; ++e) if (in->inv[e] < 0 || (uint64_t)in->inv[e] >= E) return fail(W2RAP_E_ARG, "inv names an edge object that does not exist");
+    for (uint64_t e = 0; e < E; ++e) if ((uint64_t)in->inv[in->inv[e]] != e) return fail(W2RAP_E_ARG, "inv is not an involution: inv[inv[e]] != e");
+    W2_ARGS(args::reads_and_paths(*in));
     return 0;
 }
 
@@ -428,17 +399,7 @@ extern "C" int w2rap_step5_open(const w2rap_step5_open_in* in, const w2rap_step5
     std::memset(out, 0, sizeof(*out));
     if (const int rc = open_check(in, P, err, errlen)) return rc;
     const uint32_t parts = P->flags ? P->flags : (W2RAP_STEP5_OPEN_INDEX | W2RAP_STEP5_OPEN_LINKS | W2RAP_STEP5_OPEN_LAYOUT);
-    char ebuf[512] = {0};
-    w2rap_step2_ctx* h = w2rap_step2_acquire(P->device, ebuf, sizeof ebuf);
-    if (!h) return fail(W2RAP_E_NO_DEVICE, ebuf);
-    Ctx& c = h->c;
-    c.prof_sums.clear();
-    const int rc = opening(c, *in, parts, *out);
-    const std::string msg = c.err;
-    save_profile5(c);
-    if (rc) w2rap_step2_destroy(h); else w2rap_step2_release(h);     // (a failed context is not cached)
-    if (rc) { w2rap_step5_open_free(out); return fail(rc, msg); }
-    return 0;
+    return one_shot(P->device, err, errlen, [&](Ctx& c) { return opening(c, *in, parts, *out); }, save_profile5, [&] { w2rap_step5_open_free(out); });
 }
 
 extern "C" void w2rap_step5_open_free(w2rap_step5_open_out* o) {

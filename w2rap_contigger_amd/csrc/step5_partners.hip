@@ -279,20 +279,9 @@ std::string g_profile5;
 }  // namespace
 
 // (also called by step5_open.hip: w2rap_step5_profile reports the last Step-5 call of either kind)
-void save_profile5(Ctx& c) {
-    (void)hipStreamSynchronize(c.stream);
-    c.presolve();
-    g_profile5.clear();
-    for (auto& s : c.prof_sums) { char line[256]; std::snprintf(line, sizeof line, "%s %.4f %llu\n", s.name.c_str(), s.ms, (unsigned long long)s.launches); g_profile5 += line; }
-}
+void save_profile5(Ctx& c) { g_profile5 = profile_text(c); }
 
 namespace {
-
-template <class T> T* host_dup(const T* src, uint64_t n) {
-    T* p = (T*)host_result_alloc((n ? n : 1) * sizeof(T));
-    if (p && n) std::memcpy(p, src, n * sizeof(T));
-    return p;
-}
 
 int partners(Ctx& c, const w2rap_step5_in& in, uint32_t max_len, w2rap_step5_out& out) {
     const uint64_t E = in.n_edge_objs, NV = in.n_vertices, n = in.n_paths, npe = n ? in.path_off[n] : 0;
@@ -307,11 +296,8 @@ int partners(Ctx& c, const w2rap_step5_in& in, uint32_t max_len, w2rap_step5_out
     };
     if (!n || !E) return unchanged();                          // no reads, or no edge a mate could lie on
     // ---- upload
-    std::vector<int32_t> vleft(E, -1), vright(E, -1);
-    for (uint64_t v = 0; v < NV; ++v) {
-        for (uint64_t i = in.from_off[v]; i < in.from_off[v + 1]; ++i) vleft[in.from_e[i]] = (int32_t)v;
-        for (uint64_t i = in.to_off[v]; i < in.to_off[v + 1]; ++i) vright[in.to_e[i]] = (int32_t)v;
-    }
+    std::vector<int32_t> vleft, vright;
+    args::edge_ends(in, vleft, vright);
     uint8_t *d_ebits = nullptr, *d_rbits = nullptr, *d_quals = nullptr;
     uint64_t *d_ebyte = nullptr, *d_rbyte = nullptr, *d_qoff = nullptr, *d_poff = nullptr;
     uint32_t *d_elen = nullptr, *d_rlen = nullptr;
@@ -502,58 +488,16 @@ int w2rap_step5_partners_to_ends(const w2rap_step5_in* in, const w2rap_step5_par
     std::memset(out, 0, sizeof(*out));
     if (in->K < 16 || in->K > 640) return fail(W2RAP_E_ARG, "K must be in [16, 640]");
     if (P->flags) return fail(W2RAP_E_ARG, "unknown flag");
-    const uint64_t E = in->n_edge_objs, NV = in->n_vertices, n = in->n_paths;
-    if (E >= (1ull << 31) || NV >= (1ull << 31) || n >= (1ull << 32) - 2) return fail(W2RAP_E_LIMIT, "more than 2^31 edge objects or vertices, or 2^32 reads");
-    if (n & 1) return fail(W2RAP_E_ARG, "n_paths is odd: reads r and r ^ 1 are mates");
-    if (in->n_reads != n) return fail(W2RAP_E_ARG, "n_reads differs from n_paths: PartnersToEnds needs the bases and qualities of every read");
-    if (E && (!in->edge_packed || !in->edge_byte_off || !in->edge_len || !in->from_v || !in->from_e || !in->to_e)) return fail(W2RAP_E_ARG, "null graph array");
-    if (NV && (!in->from_off || !in->to_off)) return fail(W2RAP_E_ARG, "null adjacency offsets");
-    if (E && !NV) return fail(W2RAP_E_ARG, "edge objects without vertices");
-    if (n && (!in->path_offset || !in->path_off || !in->read_byte_off || !in->read_len || !in->qual_off)) return fail(W2RAP_E_ARG, "null input array");
-    if (E && in->edge_byte_off[0] != 0) return fail(W2RAP_E_ARG, "edge_byte_off must start at 0");
-    for (uint64_t o = 0; o < E; ++o) {
-        if (in->edge_len[o] < (uint32_t)in->K) return fail(W2RAP_E_ARG, "an edge object shorter than K bases");
-        if (in->edge_byte_off[o + 1] < in->edge_byte_off[o] || in->edge_byte_off[o + 1] - in->edge_byte_off[o] != ((uint64_t)in->edge_len[o] + 3) / 4)
-            return fail(W2RAP_E_ARG, "edge_byte_off does not match edge_len");
-    }
-    if (NV) {
-        if (in->from_off[0] != 0 || in->to_off[0] != 0) return fail(W2RAP_E_ARG, "from_off / to_off must start at 0");
-        for (uint64_t v = 0; v < NV; ++v) if (in->from_off[v + 1] < in->from_off[v] || in->to_off[v + 1] < in->to_off[v]) return fail(W2RAP_E_ARG, "from_off / to_off is not ascending");
-        if (in->from_off[NV] != E || in->to_off[NV] != E) return fail(W2RAP_E_ARG, "the adjacency lists do not hold every edge object once");
-        std::vector<char> sf(E, 0), st(E, 0);
-        for (uint64_t i = 0; i < E; ++i) {
-            if (in->from_v[i] < 0 || (uint64_t)in->from_v[i] >= NV) return fail(W2RAP_E_ARG, "from_v names a vertex that does not exist");
-            if (in->from_e[i] < 0 || (uint64_t)in->from_e[i] >= E || in->to_e[i] < 0 || (uint64_t)in->to_e[i] >= E) return fail(W2RAP_E_ARG, "the adjacency lists name an edge object that does not exist");
-            if (sf[in->from_e[i]]++ || st[in->to_e[i]]++) return fail(W2RAP_E_ARG, "the adjacency lists do not hold every edge object once");
-        }
-    }
+    if (args::too_large(*in, args::READS_END)) return fail(W2RAP_E_LIMIT, args::TOO_LARGE);
+    if (in->n_paths & 1) return fail(W2RAP_E_ARG, args::ODD_PATHS);
+    if (in->n_reads != in->n_paths) return fail(W2RAP_E_ARG, "n_reads differs from n_paths: PartnersToEnds needs the bases and qualities of every read");
+    W2_ARGS(args::null_arrays(*in));
+    W2_ARGS(args::edge_off_start(*in));
+    W2_ARGS(args::edge_lens(*in));
+    W2_ARGS(args::adjacency(*in));
     uint32_t max_len = 0;
-    if (n) {
-        if (in->path_off[0] != 0 || in->read_byte_off[0] != 0 || in->qual_off[0] != 0) return fail(W2RAP_E_ARG, "path_off, read_byte_off and qual_off must start at 0");
-        for (uint64_t r = 0; r < n; ++r) {
-            if (in->path_off[r + 1] < in->path_off[r]) return fail(W2RAP_E_ARG, "path_off is not ascending");
-            if (in->read_byte_off[r + 1] < in->read_byte_off[r] || in->read_byte_off[r + 1] - in->read_byte_off[r] != ((uint64_t)in->read_len[r] + 3) / 4)
-                return fail(W2RAP_E_ARG, "read_byte_off does not match read_len");
-            if (in->qual_off[r + 1] < in->qual_off[r] || in->qual_off[r + 1] - in->qual_off[r] != in->read_len[r]) return fail(W2RAP_E_ARG, "qual_off does not match read_len");
-            max_len = std::max(max_len, in->read_len[r]);
-        }
-        const uint64_t npe = in->path_off[n];
-        if (npe && !in->path_edges) return fail(W2RAP_E_ARG, "null path_edges");
-        if (in->read_byte_off[n] && !in->read_packed) return fail(W2RAP_E_ARG, "null read_packed");
-        if (in->qual_off[n] && !in->quals) return fail(W2RAP_E_ARG, "null quals");
-        for (uint64_t i = 0; i < npe; ++i) if (in->path_edges[i] < 0 || (uint64_t)in->path_edges[i] >= E) return fail(W2RAP_E_ARG, "a path names an edge object that does not exist");
-    }
-    char ebuf[512] = {0};
-    w2rap_step2_ctx* h = w2rap_step2_acquire(P->device, ebuf, sizeof ebuf);
-    if (!h) return fail(W2RAP_E_NO_DEVICE, ebuf);
-    Ctx& c = h->c;
-    c.prof_sums.clear();
-    const int rc = partners(c, *in, max_len, *out);
-    const std::string msg = c.err;
-    save_profile5(c);
-    if (rc) w2rap_step2_destroy(h); else w2rap_step2_release(h);     // (a failed context is not cached)
-    if (rc) { w2rap_step5_free(out); return fail(rc, msg); }
-    return 0;
+    W2_ARGS(args::reads_and_paths(*in, [&](uint64_t r) { max_len = std::max(max_len, in->read_len[r]); return args::OK; }));
+    return one_shot(P->device, err, errlen, [&](Ctx& c) { return partners(c, *in, max_len, *out); }, save_profile5, [&] { w2rap_step5_free(out); });
 }
 
 void w2rap_step5_free(w2rap_step5_out* o) {

@@ -1,6 +1,8 @@
-// step5_runs.h -- what the Step-5 files share (step5_partners.hip, step5_open.hip): the heads of the runs of equal keys
-// in a sorted array, their ranks, their number.  Each file that includes it gets its own copy of the kernel.
+// step5_runs.h -- what the Step-5 files share (step5_partners.hip, step5_open.hip, step5_add.hip): the argument checks (args.h), the
+// profile of the last Step-5 call, and the heads of the runs of equal keys in a sorted array, their ranks, their number.  Each file
+// that includes it gets its own copy of the kernel.
 #pragma once
+#include "args.h"
 #include "ctx.h"
 
 namespace w2 {
