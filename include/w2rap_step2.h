@@ -330,6 +330,11 @@ int w2rap_step2_shard_info(w2rap_step2_ctx*, uint64_t out[8]);
 /* test aid: the library's own device-wide primitives (scans, maximum, stable radix sort of pairs; csrc/step2_prims.hip) on n pseudo-random
  * elements against host-side references; 0 = all equal, k > 0 = check k failed, < 0 = could not run */
 int w2rap_step2_selftest_prims(w2rap_step2_ctx*, uint64_t n, uint64_t seed, int key_bits);
+/* test aid: the 31-mer absence filter of a pseudo-random stream of nbases bases (31 .. 2^33), built by the graph phase's own launch code,
+ * against a host loop over the same key function.  A filter has fw words; the call builds and compares the words
+ * [fw * w_lo_frac16 / 16, fw * w_hi_frac16 / 16) -- (0, 16) is the whole filter, anything else a slice as the sharded graph phase builds
+ * it.  0 = equal, 1 = a word differs, 2 = the word behind the slice was written, < 0 = could not run */
+int w2rap_step2_selftest_filter32(w2rap_step2_ctx*, uint64_t nbases, uint64_t seed, uint32_t w_lo_frac16, uint32_t w_hi_frac16);
 /* device bytes the context holds at the moment (live blocks of its pool): what the per-rank share of the dictionary is measured by */
 uint64_t w2rap_step2_device_bytes(w2rap_step2_ctx*);
 /* ... and their maximum since the context was created or since the last call with reset != 0 (which restarts the maximum at the current

@@ -194,6 +194,31 @@ __device__ inline void rank_of(const uint32_t* __restrict__ own, const unsigned 
     end = (Id)RankW<Id>::next(x);
     dist = end == v ? 0u : (uint32_t)RankW<Id>::dist(x) - (o >> 12);    // (a chain end's distance field is not a distance: edge_of_end)
 }
+// rank_of for both nodes of U k-mers, one hop at a time: all own[] loads (a k-mer's two as one 8-byte load) are asked for before the
+// first owner word, all owner words before the first load from at_end[] (what the caller wants to know about every chain end: its own
+// word, or its successor) -- the U chains of dependent round trips of a thread overlap instead of following one another.  Node 2 i[j] + q
+// is entry 2 j + q; nothing is loaded conditionally (a circle's node reads its own word for nothing), so the caller clamps i[] to valid
+// k-mers and ignores the entries it does not own.
+template <class Id, unsigned U, class T>
+__device__ inline void rank_of_staged(const uint32_t* __restrict__ own, const unsigned long long* __restrict__ w, const T* __restrict__ at_end,
+                                      const uint64_t (&i)[U], Id (&end)[2 * U], uint32_t (&dist)[2 * U], T (&end_val)[2 * U]) {
+    uint32_t o[2 * U]; unsigned long long x[2 * U];
+#pragma unroll
+    for (unsigned j = 0; j < U; ++j) { const uint2 t = *reinterpret_cast<const uint2*>(&own[2 * i[j]]); o[2 * j] = t.x; o[2 * j + 1] = t.y; }
+#pragma unroll
+    for (unsigned n = 0; n < 2 * U; ++n) {
+        const uint64_t v = 2 * i[n / 2] + (n & 1);
+        x[n] = w[o[n] == OWN_CIRCLE ? v : v + RT_NODES - (o[n] & 0xFFFu)];
+    }
+#pragma unroll
+    for (unsigned n = 0; n < 2 * U; ++n) {
+        const Id v = (Id)(2 * i[n / 2] + (n & 1));
+        end[n] = o[n] == OWN_CIRCLE ? v : (Id)RankW<Id>::next(x[n]);
+        dist[n] = end[n] == v ? 0u : (uint32_t)RankW<Id>::dist(x[n]) - (o[n] >> 12);
+    }
+#pragma unroll
+    for (unsigned n = 0; n < 2 * U; ++n) end_val[n] = at_end[end[n]];
+}
 // the unipath whose canonical head is the flip of chain end t (k_edge_from_sorted / k_edge_from_hint put id + 1 into the distance field
 // of the end's own word, which is (0, t) after the ranking); NONE32: t^1 is not a canonical head
 template <class Id>

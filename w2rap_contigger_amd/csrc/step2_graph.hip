@@ -19,6 +19,8 @@
 // hash-set walk, :275-286); we number by the lexicographic order of the sequences
 // (== order of their first 60-mers, which are unique) or replay a given order.
 #include <algorithm>
+#include <cstring>
+#include <vector>
 #include "ctx.h"
 
 namespace w2 {
@@ -331,35 +333,57 @@ __global__ void __launch_bounds__(256) k_split_walk2(uint64_t n, const Id* __res
 // every k-mer evaluates the finished ranks of its two nodes once: the circle test (a node whose "end" still has a successor lies on a
 // circle) and the middle base of odd-length unipaths, as seen from each of the two heads (orientation by getCanonicalForm,
 // feudal/BaseVec.h:326); Step 3 also wants the ranks as arrays (nxt, rnk; null for Step 2, which re-evaluates rank_of where needed)
+// A thread takes RANK_U k-mers, 256 apart (every round of the block is 256 consecutive k-mers: coalesced), and walks their chains of
+// dependent loads -- own, owner word, the end's successor -- hop by hop for all of them at once (rank_of_staged, common.h).
+constexpr unsigned RANK_U = 4;
+static inline unsigned grid_per_thread(uint64_t n, unsigned per_thread) { return (unsigned)((n + 256ull * per_thread - 1) / (256ull * per_thread)); }
+// (FULL: all 256 RANK_U k-mers of the block exist -- every block but the last: straight-line code, or the compiler moves the loads of a
+// k-mer that may lie past the end behind that test and out of their stages)
+template <class Id, bool FULL>
+__device__ inline void rank_finish_block(uint64_t S, const unsigned long long* __restrict__ w,
+                                         const uint32_t* __restrict__ own, const Id* __restrict__ nxt0,
+                                         const uint64_t* __restrict__ shi, const uint64_t* __restrict__ slo,
+                                         Id* __restrict__ nxt, uint32_t* __restrict__ rnk, uint8_t* __restrict__ cyc,
+                                         uint8_t* __restrict__ mid, uint32_t* __restrict__ flags) {
+    constexpr Id NONE = NodeId<Id>::NONE;
+    constexpr unsigned U = RANK_U;
+    const uint64_t i0 = (uint64_t)blockIdx.x * (256 * U) + threadIdx.x;
+    uint64_t ii[U];
+#pragma unroll
+    for (unsigned j = 0; j < U; ++j) ii[j] = FULL || i0 + 256 * j < S ? i0 + 256 * j : S - 1;       // (past the end: the last k-mer again, nothing stored)
+    Id nx[2 * U], succ[2 * U]; uint32_t rk[2 * U];
+    rank_of_staged<Id, U, Id>(own, w, nxt0, ii, nx, rk, succ);
+#pragma unroll
+    for (unsigned j = 0; j < U; ++j) {
+        const uint64_t i = i0 + 256 * j;
+        if (!FULL && i >= S) break;
+        if (nxt) { nxt[2 * i] = nx[2 * j]; nxt[2 * i + 1] = nx[2 * j + 1]; }
+        if (rnk) *reinterpret_cast<uint2*>(&rnk[2 * i]) = make_uint2(rk[2 * j], rk[2 * j + 1]);
+        const bool c0 = succ[2 * j] != NONE, c1 = succ[2 * j + 1] != NONE;
+        *reinterpret_cast<uchar2*>(&cyc[2 * i]) = make_uchar2(c0, c1);
+        if (c0 || c1) flags[2] = 1;
+        // middle base
+        if (!shi) continue;
+        const uint32_t r0 = rk[2 * j], r1 = rk[2 * j + 1];
+        const uint64_t n = (uint64_t)r0 + r1 + 1;
+        if (n & 1) continue;                             // even number of bases: decided by the end k-mers
+        const uint64_t q = n / 2 + 29;                   // (n+59)/2
+        const uint64_t x = q < n - 1 ? q : n - 1;
+        if (r1 != x && r0 != x) continue;
+        const unsigned off = (unsigned)(q - x);
+        const Kmer k{shi[i], slo[i]};
+        if (r1 == x) mid[nx[2 * j + 1] ^ (Id)1] = (uint8_t)kmer_base(k, off);                // traversed forward
+        if (r0 == x) mid[nx[2 * j] ^ (Id)1] = (uint8_t)kmer_base(kmer_rc(k), off);          // traversed reversed
+    }
+}
 template <class Id>
 __global__ void __launch_bounds__(256) k_rank_finish(uint64_t S, const unsigned long long* __restrict__ w,
                                                       const uint32_t* __restrict__ own, const Id* __restrict__ nxt0,
                                                       const uint64_t* __restrict__ shi, const uint64_t* __restrict__ slo,
                                                       Id* __restrict__ nxt, uint32_t* __restrict__ rnk, uint8_t* __restrict__ cyc,
                                                       uint8_t* __restrict__ mid, uint32_t* __restrict__ flags) {
-    constexpr Id NONE = NodeId<Id>::NONE;
-    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= S) return;
-    Id nx[2]; uint32_t rk[2];
-#pragma unroll
-    for (unsigned q = 0; q < 2; ++q) rank_of<Id>(own, w, (Id)(2 * i + q), nx[q], rk[q]);
-    if (nxt) { nxt[2 * i] = nx[0]; nxt[2 * i + 1] = nx[1]; }
-    if (rnk) *reinterpret_cast<uint2*>(&rnk[2 * i]) = make_uint2(rk[0], rk[1]);
-    const bool c0 = nxt0[nx[0]] != NONE, c1 = nxt0[nx[1]] != NONE;
-    *reinterpret_cast<uchar2*>(&cyc[2 * i]) = make_uchar2(c0, c1);
-    if (c0 || c1) flags[2] = 1;
-    // middle base
-    if (!shi) return;
-    const uint32_t r0 = rk[0], r1 = rk[1];
-    const uint64_t n = (uint64_t)r0 + r1 + 1;
-    if (n & 1) return;                               // even number of bases: decided by the end k-mers
-    const uint64_t q = n / 2 + 29;                   // (n+59)/2
-    const uint64_t x = q < n - 1 ? q : n - 1;
-    if (r1 != x && r0 != x) return;
-    const unsigned off = (unsigned)(q - x);
-    const Kmer k{shi[i], slo[i]};
-    if (r1 == x) mid[nx[1] ^ (Id)1] = (uint8_t)kmer_base(k, off);                    // traversed forward
-    if (r0 == x) mid[nx[0] ^ (Id)1] = (uint8_t)kmer_base(kmer_rc(k), off);          // traversed reversed
+    if (((uint64_t)blockIdx.x + 1) * (256 * RANK_U) <= S) rank_finish_block<Id, true>(S, w, own, nxt0, shi, slo, nxt, rnk, cyc, mid, flags);
+    else rank_finish_block<Id, false>(S, w, own, nxt0, shi, slo, nxt, rnk, cyc, mid, flags);
 }
 // (kernels over the N = 2S oriented nodes run with one thread per K-MER, two nodes each: a grid has fewer than 2^32 threads, N may not)
 template <class Id>
@@ -516,29 +540,54 @@ __global__ void __launch_bounds__(256) k_edge_len(uint64_t E, const uint32_t* __
 // every k-mer learns (edge, offset) (addEdge :287-301) and deposits its base(s) of the edge sequence.  srec (may be null): the 32-B
 // record {key, KDef} per k-mer that read pathing through the dictionary reads (one GPU); with the pathing index (sharded dictionary) a
 // k-mer's (edge, offset) is wherever its 60 bases lie in the edge sequences and nothing is written per k-mer.
+template <class Id, bool FULL>
+__device__ inline void assign_block(uint64_t S, const uint64_t* __restrict__ shi, const uint64_t* __restrict__ slo,
+                                    const uint32_t* __restrict__ own, const unsigned long long* __restrict__ w,
+                                    const uint64_t* __restrict__ edge_off, KRec* __restrict__ srec,
+                                    uint8_t* __restrict__ codes, uint32_t* __restrict__ flags) {
+    // RANK_U k-mers per thread, 256 apart (k_rank_finish): the four dependent hops own -> owner word -> the ends' words -> edge_off, each
+    // for all of them before the next (the words of BOTH ends are asked for: the ends of a unipath's k-mers are the same two words)
+    constexpr unsigned U = RANK_U;
+    const uint64_t i0 = (uint64_t)blockIdx.x * (256 * U) + threadIdx.x;
+    uint64_t ii[U];
+#pragma unroll
+    for (unsigned j = 0; j < U; ++j) ii[j] = FULL || i0 + 256 * j < S ? i0 + 256 * j : S - 1;       // (past the end: the last k-mer again, nothing stored)
+    Kmer km[U];
+#pragma unroll
+    for (unsigned j = 0; j < U; ++j) km[j] = Kmer{shi[ii[j]], slo[ii[j]]};
+    Id end[2 * U]; uint32_t rk[2 * U]; unsigned long long wend[2 * U];
+    rank_of_staged<Id, U, unsigned long long>(own, w, w, ii, end, rk, wend);
+    // the chain through node 2i starts at head e1^1, the one through 2i+1 at e0^1: exactly one of the two is a canonical head
+    uint32_t e[U], off[U]; bool rev[U]; uint64_t eo[U];
+#pragma unroll
+    for (unsigned j = 0; j < U; ++j) {
+        e[j] = (uint32_t)RankW<Id>::dist(wend[2 * j + 1]) - 1u; off[j] = rk[2 * j + 1]; rev[j] = false;        // (edge_of_end)
+        if (e[j] == NONE32) { e[j] = (uint32_t)RankW<Id>::dist(wend[2 * j]) - 1u; off[j] = rk[2 * j]; rev[j] = true; }
+    }
+#pragma unroll
+    for (unsigned j = 0; j < U; ++j) eo[j] = edge_off[e[j] == NONE32 ? 0u : e[j]];
+#pragma unroll
+    for (unsigned j = 0; j < U; ++j) {
+        const uint64_t i = i0 + 256 * j;
+        if (!FULL && i >= S) break;
+        Kmer k = km[j];
+        if (e[j] == NONE32) { atomicOr(&flags[1], (uint32_t)GE_ASSIGN); if (srec) srec[i] = KRec{k.hi, k.lo, make_uint4(NONE32, 0, 0, 0)}; continue; }
+        if (srec) srec[i] = KRec{k.hi, k.lo, make_uint4(e[j] | (rev[j] ? 0x80000000u : 0u), off[j], (uint32_t)eo[j],
+                                                        (uint32_t)(eo[j] >> 32) | ((rk[2 * j] + rk[2 * j + 1] + 1u) << 8))};
+        if (rev[j]) k = kmer_rc(k);
+        uint8_t* dst = codes + eo[j];
+        if (off[j] == 0) {
+            for (unsigned t = 0; t < K; ++t) dst[t] = (uint8_t)kmer_base(k, t);
+        } else dst[K - 1 + off[j]] = (uint8_t)kmer_last(k);
+    }
+}
 template <class Id>
 __global__ void __launch_bounds__(256) k_assign(uint64_t S, const uint64_t* __restrict__ shi, const uint64_t* __restrict__ slo,
                                                  const uint32_t* __restrict__ own, const unsigned long long* __restrict__ w,
                                                  const uint64_t* __restrict__ edge_off, KRec* __restrict__ srec,
                                                  uint8_t* __restrict__ codes, uint32_t* __restrict__ flags) {
-    uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= S) return;
-    Id e0, e1; uint32_t rk0, rk1;
-    rank_of<Id>(own, w, (Id)(2 * i), e0, rk0);
-    rank_of<Id>(own, w, (Id)(2 * i + 1), e1, rk1);
-    // the chain through node 2i starts at head e1^1, the one through 2i+1 at e0^1: exactly one of the two is a canonical head
-    uint32_t e = edge_of_end<Id>(w, e1), off = rk1;
-    bool rev = false;
-    if (e == NONE32) { e = edge_of_end<Id>(w, e0); off = rk0; rev = true; }
-    Kmer k{shi[i], slo[i]};
-    if (e == NONE32) { atomicOr(&flags[1], (uint32_t)GE_ASSIGN); if (srec) srec[i] = KRec{k.hi, k.lo, make_uint4(NONE32, 0, 0, 0)}; return; }
-    const uint64_t eo = edge_off[e];
-    if (srec) srec[i] = KRec{k.hi, k.lo, make_uint4(e | (rev ? 0x80000000u : 0u), off, (uint32_t)eo, (uint32_t)(eo >> 32) | ((rk0 + rk1 + 1u) << 8))};
-    if (rev) k = kmer_rc(k);
-    uint8_t* dst = codes + eo;
-    if (off == 0) {
-        for (unsigned t = 0; t < K; ++t) dst[t] = (uint8_t)kmer_base(k, t);
-    } else dst[K - 1 + off] = (uint8_t)kmer_last(k);
+    if (((uint64_t)blockIdx.x + 1) * (256 * RANK_U) <= S) assign_block<Id, true>(S, shi, slo, own, w, edge_off, srec, codes, flags);      // (FULL: rank_finish_block)
+    else assign_block<Id, false>(S, shi, slo, own, w, edge_off, srec, codes, flags);
 }
 
 // all edge bases as one 2-bit stream (for 16-bases-per-load comparisons in read pathing)
@@ -1004,11 +1053,23 @@ int index_from_entries(Ctx& c, const uint4* d_all, uint64_t n_all, bool harden) 
     return harden ? index_harden(c) : 0;
 }
 // the absence filter's geometry for the current edge stream (0 words: no filter), and one rank's slice of its words
+static uint64_t filter32_words_for(uint64_t edge_bases) {
+    uint64_t fw = 1024;
+    while (fw * 4 < edge_bases) fw <<= 1;                              // one 64-bit word per 2-4 positions (a run of ~9 shares a word)
+    return fw;
+}
+// zeroes the words [lo, hi) of a filter of fw words at out[0 .. hi - lo) (out_words of them) and builds them from the stream of nbases bases, on st:
+// what the graph phase, filter32_slice and the self-test at the end of this file all call
+static int filter32_build(Ctx& c, hipStream_t st, const uint8_t* bits, uint64_t nbases, uint64_t fw, uint64_t lo, uint64_t hi, unsigned long long* out, uint64_t out_words) {
+    W2_HIP(hipMemsetAsync(out, 0, out_words * 8, st));
+    const uint64_t npos = nbases - (FMER - 1);
+    LAUNCH_ON(c, st, "k_filter32", k_filter32, dim3(grid_for(npos)), dim3(256), 0, npos, bits, out, (uint32_t)(fw - 1), (uint32_t)lo, (uint32_t)hi);
+    W2_HIP(hipGetLastError());
+    return 0;
+}
 uint64_t filter32_words(const Ctx& c) {
     if (c.edge_bases < FMER || getenv("W2RAP_NO_FILTER32") || c.edge_bases > (1ull << 33)) return 0;
-    uint64_t fw = 1024;
-    while (fw * 4 < c.edge_bases) fw <<= 1;
-    return fw;
+    return filter32_words_for(c.edge_bases);
 }
 // (on the SIDE stream, behind what the main stream has queued so far: the caller synchronises c.stream2 before it uses the slice -- the sharded
 //  graph phase lists, gathers and inserts the index entries meanwhile)
@@ -1027,10 +1088,7 @@ int filter32_slice(Ctx& c, unsigned rank, unsigned world, unsigned long long** d
         W2_HIP(hipStreamWaitEvent(st, ev, 0));
         (void)hipEventDestroy(ev);
     }
-    W2_HIP(hipMemsetAsync(p, 0, (hi - lo + 1) * 8, st));
-    const uint64_t npos = c.edge_bases - (FMER - 1);
-    LAUNCH_ON(c, st, "k_filter32", k_filter32, dim3(grid_for(npos)), dim3(256), 0, npos, c.d_edge_bits, p, (uint32_t)(fw - 1), (uint32_t)lo, (uint32_t)hi);
-    W2_HIP(hipGetLastError());
+    W2_TRY(filter32_build(c, st, c.d_edge_bits, c.edge_bases, fw, lo, hi, p, hi - lo + 1));
     *d_slice = p; *n_words = hi - lo;
     return 0;
 }
@@ -1380,7 +1438,7 @@ static int run_ranking_t(Ctx& c, uint64_t N, const Id* nxt0, Id* nxt, uint32_t* 
     if (getenv("W2RAP_TRACE")) fprintf(stderr, "[w2rap] list ranking: %d jump launches\n", rounds);
     c.release(spl); c.release(d_cnt);
     if (mid) W2_HIP(hipMemsetAsync(mid, 0, N, st));
-    LAUNCH(c, "k_rank_finish", k_rank_finish<Id>, dim3(grid_for(S)), dim3(256), 0, S, w, own, nxt0, shi, slo, nxt, rnk, cyc, mid, d_flags);
+    LAUNCH(c, "k_rank_finish", k_rank_finish<Id>, dim3(grid_per_thread(S, RANK_U)), dim3(256), 0, S, w, own, nxt0, shi, slo, nxt, rnk, cyc, mid, d_flags);
     W2_HIP(hipStreamSynchronize(st));
     return 0;
 }
@@ -1474,8 +1532,7 @@ int graph_finish(Ctx& c) {
     if (c.d_filter32) { c.release(c.d_filter32); c.d_filter32 = nullptr; }
     c.f32words = 0;
     if (c.edge_bases >= FMER && c.stream2 && !getenv("W2RAP_NO_FILTER32") && c.edge_bases <= (1ull << 33)) {
-        uint64_t fw = 1024;
-        while (fw * 4 < c.edge_bases) fw <<= 1;                        // one 64-bit word per 2-4 positions (a run of ~9 shares a word)
+        const uint64_t fw = filter32_words_for(c.edge_bases);
         W2_ALLOC(c.d_filter32, unsigned long long, fw);
         c.f32words = fw;
         hipEvent_t ev;
@@ -1483,9 +1540,7 @@ int graph_finish(Ctx& c) {
         W2_HIP(hipEventRecord(ev, st));
         W2_HIP(hipStreamWaitEvent(c.stream2, ev, 0));
         (void)hipEventDestroy(ev);
-        W2_HIP(hipMemsetAsync(c.d_filter32, 0, fw * 8, c.stream2));
-        const uint64_t npos = c.edge_bases - (FMER - 1);
-        LAUNCH_ON(c, c.stream2, "k_filter32", k_filter32, dim3(grid_for(npos)), dim3(256), 0, npos, c.d_edge_bits, c.d_filter32, (uint32_t)(fw - 1), 0u, (uint32_t)fw);
+        W2_TRY(filter32_build(c, c.stream2, c.d_edge_bits, c.edge_bases, fw, 0, fw, c.d_filter32, fw));
     }
     }
     // ---- a8: objects
@@ -1689,7 +1744,7 @@ static int phase_graph_t(Ctx& c, const w2rap_edge_hint* hint) {
     // (Tried in round 6: the bases first and the 8 GB of records as a second pass from graph_finish, beside the 31-mer filter -- which needs
     // only the bases and is 3.9 ms of nothing else running in front of read pathing.  Beside each other the filter takes 8.3 instead of 4.1 ms
     // and the two passes 7.9 instead of 5.3: graph phase +2 ms.  One pass it stays.)
-    if (S) LAUNCH(c, "k_assign", k_assign<Id>, dim3(grid_for(S)), dim3(256), 0, S, c.d_shi, c.d_slo, own, rankw,
+    if (S) LAUNCH(c, "k_assign", k_assign<Id>, dim3(grid_per_thread(S, RANK_U)), dim3(256), 0, S, c.d_shi, c.d_slo, own, rankw,
                               c.d_edge_off, c.d_srec, c.d_edge_codes, d_flags);
     W2_HIP(hipStreamSynchronize(st));
     c.release(rankw); c.release(own); rankw = nullptr; own = nullptr;
@@ -1706,3 +1761,44 @@ int phase_graph(Ctx& c, const w2rap_edge_hint* hint) {
 }
 
 }  // namespace w2
+
+// ------------------------------------------------------------------------------------------------ self test (tests/test_gpu_graph_thin.py)
+// A pseudo-random 2-bit stream of nbases bases, the words [fw lo/16, fw hi/16) of its absence filter built by filter32_build (what the
+// graph phase and filter32_slice call) against a host loop over fmer_key.  -> 0, 1 a word differs, 2 the word behind the range was
+// written, < 0 could not run
+extern "C" int w2rap_step2_selftest_filter32(w2rap_step2_ctx* h, uint64_t nbases, uint64_t seed, uint32_t w_lo_frac16, uint32_t w_hi_frac16) {
+    using namespace w2;
+    if (!h || nbases < FMER || nbases > (1ull << 33) || w_lo_frac16 > w_hi_frac16 || w_hi_frac16 > 16) return -1;
+    Ctx& c = h->c;
+    if (hipSetDevice(c.device) != hipSuccess) return -1;
+    const uint64_t nby = (nbases + 3) / 4;
+    std::vector<uint8_t> hb(nby + 16, 0);
+    uint64_t x = seed * 0x9E3779B97F4A7C15ull + 1;
+    for (uint64_t g = 0; g < nbases; ++g) {
+        x ^= x << 13; x ^= x >> 7; x ^= x << 17;
+        hb[g >> 2] |= (uint8_t)(((x >> 33) & 3) << (2 * (g & 3)));
+    }
+    const uint64_t fw = filter32_words_for(nbases), lo = fw * w_lo_frac16 / 16, hi = fw * w_hi_frac16 / 16, npos = nbases - (FMER - 1);
+    std::vector<unsigned long long> want(hi - lo + 1, 0), got(hi - lo + 1);
+    for (uint64_t g = 0; g < npos; ++g) {
+        const uint64_t b0 = g >> 2; const unsigned sh = 2 * (unsigned)(g & 3);
+        uint64_t v; std::memcpy(&v, &hb[b0], 8);
+        v >>= sh;
+        if (sh) v |= (uint64_t)hb[b0 + 8] << (64 - sh);
+        const FmerKey k = fmer_key(v);
+        const uint64_t word = k.word & (uint32_t)(fw - 1);
+        if (word >= lo && word < hi) want[word - lo] |= k.mask;
+    }
+    uint8_t* d_bits = c.alloc<uint8_t>(nby + 16, false);
+    unsigned long long* d_out = c.alloc<unsigned long long>(hi - lo + 1, false);
+    if (!d_bits || !d_out) return -1;
+    int bad = 0;
+    if (hipMemcpyAsync(d_bits, hb.data(), nby + 16, hipMemcpyHostToDevice, c.stream) != hipSuccess ||
+        filter32_build(c, c.stream, d_bits, nbases, fw, lo, hi, d_out, hi - lo + 1) ||
+        hipMemcpyAsync(got.data(), d_out, (hi - lo + 1) * 8, hipMemcpyDeviceToHost, c.stream) != hipSuccess ||
+        hipStreamSynchronize(c.stream) != hipSuccess) bad = -1;
+    for (uint64_t i = 0; i < hi - lo && !bad; ++i) if (got[i] != want[i]) bad = 1;
+    if (!bad && got[hi - lo] != 0) bad = 2;
+    c.release(d_bits); c.release(d_out);
+    return bad;
+}
