@@ -20,6 +20,7 @@
 #include "paths/long/ReadPath.h"
 #include "paths/long/large/GapToyTools.h"
 #include "paths/long/large/Repath.h"
+#include "system/SysConf.h"
 
 int main(int argc, char** argv) {
     if (argc < 3) { std::cerr << "usage: ref_step3 out_dir prefix [large_K] [threads] [extend_paths]\n"; return 2; }
@@ -28,6 +29,10 @@ int main(int argc, char** argv) {
     int threads = argc > 4 ? atoi(argv[4]) : 1;
     const bool extend_paths = argc > 5 && atoi(argv[5]) != 0;
     omp_set_num_threads(threads);
+    // The worklists and HashSet::parallelForEachHHS (BigKPather.cc:122) take their thread count from SysConf, not from OpenMP, and the
+    // reference's main() leaves it at every processor: the order of the large-K edges then changes from run to run.  A 1-thread run is
+    // the one the tests record, so that one runs on one thread throughout; with more threads everything is as main() has it.
+    if (threads == 1) configNumThreads(1);
     HyperBasevector hbv, hbvr; ReadPathVec paths, pathsr; vec<int> inv;
     BinaryReader::readFile(out_dir + "/" + prefix + ".small_K.hbv", &hbv);
     LoadReadPathVec(paths, (out_dir + "/" + prefix + ".small_K.paths").c_str());

@@ -18,6 +18,13 @@ and, for Step 1 (fastq ingest), step1_r1.fastq / step1_r2.fastq with the REAL re
 and, from the REAL reference hbv2gfa tool (oracle/_ref/ref_hbv2gfa -g 20; `make_golden.py gfa`), for the graphs named in GFA_GOLDENS
     <graph>.ref_raw.gfa and <graph>.ref_gfa_stats.txt (its stdout between "=== Graph stats === " and "Dumping gfa"),
 and (`make_golden.py refruns`) refruns/<case>/: the files and stdout of every reference run the tests make, with the SHA-256 of its inputs.
+For Step 3 (`make_golden.py refruns tests/test_step3_oracle.py`, oracle/_ref/ref_step3 at 1 thread: t.large_K.hbv, t.large_K.paths and, for the
+cases of tests/step3_cases.py, t.first.frags.dist) these are: step3_<fixture>_K<K2>[_extend] (Step-2 fixtures at other K2 and with
+--extend_paths), step3_case_<name>_K<K2> (circle, palindrome, chains), step3_mix_K<K2> (one graph at each of the 33 large K the reference
+runs), step3_fragdist_K200 (FragDist's bounds), step3_joined_K<K2>_extend (--extend_paths on a graph with its true adjacency) and
+step3_counts_<U>_<N2>_K100 (launch sizes).  ref_step3 runs every loop of the reference on one thread, so the cases of tests/step3_cases.py
+are reproduced byte for byte; the step3_<fixture>_* records were made when the reference's own worklists still took every processor, which
+numbers the large-K edges differently from run to run: they stay as recorded (the tests replay whatever order a record has).
 All of these are data (inputs and expected outputs); no reference source is stored.
 """
 import os

@@ -7,6 +7,7 @@ import os
 import numpy as np
 import pytest
 
+import step3_cases as SC
 from conftest import GOLDEN, FIXTURES, reference_outputs, relabel_compare
 from w2rap_contigger_amd import formats as F
 from oracle import oracle as O, oracle3 as O3
@@ -203,3 +204,89 @@ def test_the_lone_rule_needs_a_graph_of_unique_kmers():
         for t in range(len(seq) - K2 + 1):
             c = _canon(seq[t:t + K2]); count[c] = count.get(c, 0) + 1
     assert set(count.values()) == {2}
+
+
+# ---- Step 3's own edges (tests/step3_cases.py: mix, fragdist, counts, joined): the oracle pinned to recorded 1-thread reference runs at every
+# large K the reference runs, and held to a plain-numpy statement of the result where the reference cannot run
+def _replays(r, rh, paths_bytes, frags):
+    assert F.paths_to_bytes(r.path_offset, r.path_off, r.path_edges) == paths_bytes
+    assert F.hbv_to_bytes(O3.to_hbv(r), zero_padding=True) == F.hbv_to_bytes(rh, zero_padding=True)
+    assert O3.frags_text(r.frag) == frags
+
+
+def _mix_structure(h, p, K2, r):
+    """what mix(K2) must give at every K2: the invariants of step3_cases.check_invariants (n_distinct against a brute-force count among them),
+    exactly one self-inverse object (the palindromic K2-mer), a loop of the 97-circle and a loop of ONE K2-mer (the homopolymer)"""
+    objs = SC.objects_of(r.obj_codes, r.obj_off)
+    SC.check_invariants(h, p, K2, objs, r.inv2, r.left, r.right, (r.path_offset, r.path_off, r.path_edges), r.n_distinct)
+    self_inv = [o for o in range(len(objs)) if r.inv2[o] == o]
+    assert len(self_inv) == 1 and len(objs[self_inv[0]]) == K2
+    loops = [o for o in range(len(objs)) if r.left[o] == r.right[o]]
+    assert any(len(objs[o]) == K2 and not objs[o].any() for o in loops)                 # A^K2
+    assert any(len(objs[o]) == 97 + K2 - 1 for o in loops)                              # the circle: 97 K2-mers
+    assert sum(len(o) - K2 + 1 for o in objs) == 2 * r.n_distinct - 1
+
+
+def test_the_k2_lists_are_the_ones_the_reference_runs():
+    assert len(SC.REFERENCE_K2) == 33 and all(60 < k <= 640 and k % 4 == 0 for k in SC.REFERENCE_K2)
+    assert {k % 32 for k in SC.REFERENCE_K2} == {0, 4, 8, 12, 16, 20, 24, 28}                                   # KGeom::tail
+    assert {(k + 31) // 32 for k in SC.REFERENCE_K2} == {3, 4, 5, 6, 7, 8, 9, 10, 12, 13, 16, 17, 20}             # KGeom::NW
+    assert all(k % 4 == 2 for k in SC.ORACLE_ONLY_K2) and {(k - 1) % 8 for k in SC.ORACLE_ONLY_K2} == {1, 5}    # k3_end_hash's scalar tail
+    assert {62, 66, 94, 126, 130, 190, 254, 258, 638} <= set(SC.ORACLE_ONLY_K2)
+    assert {(k + 31) // 32 for k in SC.REFERENCE_K2 + SC.ORACLE_ONLY_K2} == set(range(2, 21))                  # every word count the library takes
+
+
+@pytest.mark.parametrize("K2", SC.REFERENCE_K2)
+def test_oracle3_mix_replays_the_recorded_reference_run(K2, tmp_path):
+    """mix(K2) at each of the 33 large K the reference runs (its -K list, w2rap-contigger.cc:60-62, within BigK's, LargeKDispatcher.h:22-27): a
+    palindromic K2-mer, circles of 97 and of ONE K2-mer, end edges of K2-1 / K2 / K2+1 bases (Repath.cc:113-122), a four-way fork.  The oracle
+    replays the reference's bytes; a failure here is an oracle bug (oracle/step3_oracle.cc), not a library bug"""
+    h, p = SC.mix(K2)
+    rh, pb, fd = SC.recorded_step3(f"step3_mix_K{K2}", h, p, tmp_path, K2)
+    r = O3.run(h, p, K2, *O.edge_hint_from_hbv(rh))
+    _replays(r, rh, pb, fd)
+    _mix_structure(h, p, K2, r)
+    _mix_structure(h, p, K2, O3.run(h, p, K2))
+
+
+@pytest.mark.parametrize("K2", SC.ORACLE_ONLY_K2)
+def test_oracle3_mix_where_the_reference_cannot_run(K2):
+    """K2 = 2 mod 4: the library takes it (step3_repath.hip, "K2 must be even, larger than K and at most 640"), BigK does not.  The oracle is
+    what the GPU is compared with there, so it is held to the plain-numpy invariants"""
+    h, p = SC.mix(K2)
+    _mix_structure(h, p, K2, O3.run(h, p, K2))
+
+
+def test_oracle3_fragdist_bounds_replay_the_recorded_reference_run(tmp_path):
+    """FragDist's bounds (GapToyTools3.cc:625-635): len >= 10000, 0 <= d < 1000, d / 10, e1 == inv[e2], an empty mate, a negative offset"""
+    h, p = SC.fragdist()
+    rh, pb, fd = SC.recorded_step3("step3_fragdist_K200", h, p, tmp_path, 200)
+    r = O3.run(h, p, 200, *O.edge_hint_from_hbv(rh))
+    _replays(r, rh, pb, fd)
+    assert {j: int(c) for j, c in enumerate(r.frag) if c} == SC.FRAGDIST_BINS
+    assert "-nan" not in fd and fd.splitlines()[4 + 50] == "505 %g" % (9 / 31)
+
+
+@pytest.mark.parametrize("U,N2,K2", SC.COUNTS)
+def test_oracle3_counts_cases_have_the_sizes_they_are_named_for(U, N2, K2, tmp_path):
+    """counts(U, N2, K2): U places, N2 occurrences, all distinct, U unipaths -- the sizes the GPU's blocks are sized by (1024 occurrences for
+    k3_kmer_keys, 4096 nodes for k3_head_cands, 4096 pairs for k3_dict_part, 256 elsewhere); the small ones also replay a recorded reference run"""
+    h, p = SC.counts(U, N2, K2)
+    r = O3.run(h, p, K2)
+    assert (len(r.place_off) - 1, r.n_instances, r.n_distinct, r.n_edges, len(r.inv2)) == (U, N2, N2, U, 2 * U)
+    if (U, N2, K2) in SC.COUNTS_RECORDED:
+        rh, pb, fd = SC.recorded_step3(f"step3_counts_{U}_{N2}_K{K2}", h, p, tmp_path, K2)
+        _replays(O3.run(h, p, K2, *O.edge_hint_from_hbv(rh)), rh, pb, fd)
+
+
+@pytest.mark.parametrize("K2", SC.JOINED_K2)
+def test_oracle3_extend_paths_on_a_joined_graph_replays_the_recorded_reference_run(K2, tmp_path):
+    """--extend_paths (Repath.cc:72-96) on a graph with its true adjacency: places extended along a chain, stopped by a fork, and the
+    Member(p, e) break on a one-edge circle (Repath.cc:84,88): 11 places become 17"""
+    h, p = SC.joined(K2)
+    rh, pb, fd = SC.recorded_step3(f"step3_joined_K{K2}_extend", h, p, tmp_path, K2, extend_paths=True)
+    r = O3.run(h, p, K2, *O.edge_hint_from_hbv(rh), extend_paths=True)
+    _replays(r, rh, pb, fd)
+    assert (len(O3.run(h, p, K2, stop_after=1).place_off) - 1, len(r.place_off) - 1) == (11, 17)
+    tl, tr = h.to_left_right()
+    assert h.n_vertices == 2 * 8 + 2 and (tl >= 0).all() and (tr >= 0).all()      # chain 6, fork ends 2, circle 1; and as many for the inverses
