@@ -33,6 +33,9 @@ with step2.Step2Context(0) as ctx:
     print(f"k-mer instances {int(nk.sum()):,}  after record dedup {int(first.sum()):,}  ({int(first.sum()) / int(nk.sum()):.3f})")
 
     # ---- a record and its reverse complement as one: on the records of the first buckets (a sample of whole buckets)
+    if dw != 9:                                        # (the unpacking below is that of the 36-B records, a header dword and eight of bases)
+        print(f"strand-normalised figures: only with 36-B records (-DW2RAP_REC36), these are {rb} B")
+        sys.exit(0)
     ns = min(nrec, 6_000_000)
     r = dev_bytes(recs, ns * rb, dev).view(ns, dw, 4).view(torch.int32).view(ns, dw).to(torch.int64) & 0xFFFFFFFF
     nk = (r[:, 0] & 63) + 1; hasL = (r[:, 0] >> 6) & 1; hasR = (r[:, 0] >> 7) & 1

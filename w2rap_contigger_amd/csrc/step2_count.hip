@@ -1242,7 +1242,14 @@ struct FpCfg {
     static constexpr unsigned OCAP = CAP;                                     // occupied slots a bucket can end with
     static constexpr unsigned LDS = 3 * MAXSEG * 8 +
                                     (2 * CAP + TILE * FP_TS + 8 + MAXK / 32 + 2 + MAXWIN + 2 + 2 * SC + NW * QCAP + 3 * (MAXSEG + 1) + 32 + 4 + 104 + 16 + 40 + (OCAP + 1) / 2) * 4;
+    // record dedup (NOTES.md section 18): a table of record ids, at most half full, and 16-bit counts of each record's further copies; both are needed
+    // from barrier S1 to the flatten only and lie over stcc / stref / the parking queues, which the window loop and the emit use.  What
+    // lives through the window loop is one word per DISTINCT record (record | copies << 16), behind olist
+    static constexpr unsigned DT = TILE <= 512 ? 1024 : 2048, LOG_DT = TILE <= 512 ? 10 : 11;
+    static constexpr unsigned DAREA = DT + (TILE + 1) / 2;
+    static constexpr unsigned LDS_DEDUP = LDS + TILE * 4;
     static_assert(TILE < 1023 && ROUNDS * NW <= 16 && (1u << LOG_CAP) == CAP, "FpCfg");
+    static_assert(DT >= 2 * TILE && DAREA <= 2 * SC + NW * QCAP && TILE * 64 < 65536 && (OCAP & 1) == 0, "FpCfg: record dedup");
 };
 enum { FP_FILL = 0, FP_OVF, FP_CNT, FP_BASELO, FP_BASEHI, FP_WIN, FP_DEPTH };
 #ifndef W2RAP_FP_TICKETS
@@ -1296,17 +1303,49 @@ __device__ inline bool fp_same(const uint32_t* tile, unsigned ref, const FpInst&
     return same == 0u || opp == 0xFFFFFFFFu;
 }
 
-template <unsigned THREADS, unsigned MINW, unsigned TILE_, unsigned SC_>
-__global__ void __launch_bounds__(THREADS, MINW) k_count_fp(uint32_t nb, uint32_t b_lo, uint32_t b_hi, uint32_t nseg, const uint64_t* __restrict__ roff,
-                                                            const uint32_t* __restrict__ recs, uint32_t min_freq, uint32_t* __restrict__ queue,
-                                                            uint64_t* __restrict__ shi, uint64_t* __restrict__ slo, uint32_t* __restrict__ scc, uint64_t solid_cap,
-                                                            unsigned long long* __restrict__ counters, unsigned long long* __restrict__ ghist,
-                                                            uint64_t* __restrict__ chunk_start, uint32_t* __restrict__ chunk_cnt, uint32_t chunk_cap,
-                                                            uint32_t* __restrict__ defer /* [0] count, [2..] deferred bucket ids */, uint32_t defer_cap,
-                                                            uint32_t fill_limit /* <= LIMIT */, uint32_t solid_limit /* <= SC: smaller values are test hooks */,
-                                                            uint8_t* __restrict__ sctx, uint8_t* __restrict__ unres, uint32_t* __restrict__ nbr /* all three or none:
-                                                            the chunk-local adjacency prune (k_prune_local's outputs) done here, while the table still holds every
-                                                            distinct k-mer of the bucket with its count */) {
+// Record dedup: is record `rec` of the tile byte-identical to a record that entered the table before it?  Then that record's copy count
+// goes up by one and this one is not flattened.  Equality is decided by the eight dwords, never by the hash.  The table holds record + 1
+// (0 = free), linear probing; it is at most half full, so a probe sequence always ends.
+template <unsigned DT, unsigned LOG_DT>
+__device__ inline bool fp_dedup(const uint32_t* tile, uint32_t* dtab, uint32_t* dmul, unsigned rec) {
+    const uint32_t* wp = tile + rec * FP_TS;
+    uint32_t w[REC_DWORDS];
+#pragma unroll
+    for (unsigned i = 0; i < REC_DWORDS; ++i) w[i] = wp[i];
+    auto rotl = [](uint32_t v, unsigned n) { return __funnelshift_l(v, v, n); };
+    uint32_t x = w[0], y = w[REC_DWORDS - 1];
+#pragma unroll
+    for (unsigned i = 1; i + 1 < REC_DWORDS; i += 2) { x = rotl(x, 9) + w[i]; y = rotl(y, 13) ^ w[i + 1]; }
+    uint32_t h = (x + rotl(y, 16)) * 0x9E3779B1u;
+    h ^= h >> 15;
+    unsigned s = (h * 0x85EBCA6Bu) >> (32 - LOG_DT);
+    for (;;) {
+        uint32_t a = ld32(&dtab[s]);
+        if (a == 0u) { a = atomicCAS(&dtab[s], 0u, rec + 1u); if (a == 0u) return false; }
+        const uint32_t* hp = tile + (a - 1u) * FP_TS;
+        uint32_t d = 0;
+#pragma unroll
+        for (unsigned i = 0; i < REC_DWORDS; ++i) d |= hp[i] ^ w[i];
+        if (d == 0u) { atomicAdd(&dmul[(a - 1u) >> 1], 1u << (16u * ((a - 1u) & 1u))); return true; }
+        s = (s + 1u) & (DT - 1u);
+    }
+}
+
+// The kernel's body.  DEDUP: byte-identical records of a bucket are counted once, with their multiplicity as the weight (k_count_fp_dedup);
+// false: every record on its own, the form before it (k_count_fp; W2RAP_FP_DEDUP=0 launches it)
+#define W2_FP_PARAMS                                                                                                                                  \
+    uint32_t nb, uint32_t b_lo, uint32_t b_hi, uint32_t nseg, const uint64_t* __restrict__ roff, const uint32_t* __restrict__ recs, uint32_t min_freq, \
+    uint32_t* __restrict__ queue, uint64_t* __restrict__ shi, uint64_t* __restrict__ slo, uint32_t* __restrict__ scc, uint64_t solid_cap,              \
+    unsigned long long* __restrict__ counters, unsigned long long* __restrict__ ghist, uint64_t* __restrict__ chunk_start,                            \
+    uint32_t* __restrict__ chunk_cnt, uint32_t chunk_cap, uint32_t* __restrict__ defer /* [0] count, [2..] deferred bucket ids */, uint32_t defer_cap, \
+    uint32_t fill_limit /* <= LIMIT */, uint32_t solid_limit /* <= SC: smaller values are test hooks */,                                               \
+    uint8_t* __restrict__ sctx, uint8_t* __restrict__ unres, uint32_t* __restrict__ nbr /* all three or none: the chunk-local adjacency prune         \
+    (k_prune_local's outputs) done here, while the table still holds every distinct k-mer of the bucket with its count */
+#define W2_FP_ARGS                                                                                                                                    \
+    nb, b_lo, b_hi, nseg, roff, recs, min_freq, queue, shi, slo, scc, solid_cap, counters, ghist, chunk_start, chunk_cnt, chunk_cap, defer, defer_cap, \
+    fill_limit, solid_limit, sctx, unres, nbr
+template <unsigned THREADS, unsigned TILE_, unsigned SC_, bool DEDUP>
+__device__ __forceinline__ void count_fp_body(W2_FP_PARAMS) {
     constexpr unsigned long long SMASK = (1ull << 40) - 1;
     using C = FpCfg<THREADS, TILE_, SC_>;
     constexpr unsigned CAP = C::CAP, NW = C::NW, TILE = C::TILE, ROUNDS = C::ROUNDS, NPF = C::NPF, SC = C::SC, MAXSEG = C::MAXSEG, PER = C::PER, QCAP = C::QCAP,
@@ -1329,6 +1368,9 @@ __global__ void __launch_bounds__(THREADS, MINW) k_count_fp(uint32_t nb, uint32_
     uint32_t* misc = lhist + 104;                                  // 16
     uint32_t* stk = misc + 16;                                     // (class, P) pairs of a bucket counted in hash classes, depth <= 18
     uint16_t* olist = reinterpret_cast<uint16_t*>(stk + 40);       // [OCAP] the occupied slots of the bucket being emitted
+    uint32_t* rinfo = reinterpret_cast<uint32_t*>(olist + C::OCAP); // [TILE] DEDUP: the j-th distinct record of the bucket | its copies << 16
+    uint32_t* dtab = stcc;                                         // [DT] DEDUP, S1 .. flatten: record + 1 by content hash (0 = free) ...
+    uint32_t* dmul = stcc + C::DT;                                 // [(TILE + 1) / 2] ... and the further copies of each record, 16 bits each
     const unsigned tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
 
     auto seg_load = [&](uint32_t bb, uint64_t& r0, uint32_t& cnt) {
@@ -1401,6 +1443,7 @@ __global__ void __launch_bounds__(THREADS, MINW) k_count_fp(uint32_t nb, uint32_
     for (unsigned i = tid; i < TILE * FP_TS + 8; i += THREADS) tile[i] = 0;
     for (unsigned i = tid; i < 104; i += THREADS) lhist[i] = 0;
     if (tid < 16) misc[tid] = 0;
+    if (DEDUP) for (unsigned i = tid; i < C::DAREA; i += THREADS) dtab[i] = 0;
     if (tid == 0) {
         const uint32_t t0 = atomicAdd(queue, 3u), nbk = b_hi - b_lo;
         bq[0] = t0 < nbk ? b_lo + t0 : NONE32; bq[1] = t0 + 1 < nbk ? b_lo + t0 + 1 : NONE32; bq[2] = t0 + 2 < nbk ? b_lo + t0 + 2 : NONE32; bq[3] = NONE32;
@@ -1422,8 +1465,8 @@ __global__ void __launch_bounds__(THREADS, MINW) k_count_fp(uint32_t nb, uint32_
     auto drain = [&](unsigned cnt) -> unsigned {
         wave_lds_fence();
         const bool live = lane < cnt;
-        const unsigned ref = live ? qref[qn - cnt + lane] : 0u;
-        const unsigned rec = ref >> 6, idx = ref & 63u;
+        const uint32_t qv = live ? qref[qn - cnt + lane] : 0u;         // DEDUP: the record's weight rides above the reference
+        const unsigned ref = qv & 0xFFFFu, rec = ref >> 6, idx = ref & 63u;
         const FpInst x = fp_fetch(tile, rec, idx);
         const FpKey k = fp_key(x);
         const unsigned ctx = ctx_of(x, k.rc, tile[rec * FP_TS], idx);
@@ -1443,7 +1486,7 @@ __global__ void __launch_bounds__(THREADS, MINW) k_count_fp(uint32_t nb, uint32_
                 s = (s + 1) & (CAP - 1);
                 if (--budget <= 0) break;
             }
-            if (ok) { atomicAdd(&cc[s], 1u); atomicOr(&cc[s], ctx << 24); }
+            if (ok) { atomicAdd(&cc[s], DEDUP ? qv >> 16 : 1u); atomicOr(&cc[s], ctx << 24); }
             else st32(&misc[FP_OVF], 1u);
         }
         qn -= cnt;
@@ -1474,28 +1517,35 @@ __global__ void __launch_bounds__(THREADS, MINW) k_count_fp(uint32_t nb, uint32_
         tile_load((it + 1) % 3, pf);
         __syncthreads();                                             // S1
         // ---- flatten: record rec occupies positions [e, e + nk) of the bucket-wide k-mer numbering (see k_count_buckets)
+        //      DEDUP: a record equal to one met before adds to that one's copies and takes no positions; the scans carry the number of
+        //      distinct records above bit 16 (k-mers below: TILE * 64 < 2^16), which numbers them j = 0, 1, .. in record order
         unsigned nkr[ROUNDS], inclr[ROUNDS];
 #pragma unroll
         for (unsigned r = 0; r < ROUNDS; ++r) {
             const unsigned rec = r * THREADS + tid;
-            nkr[r] = (!skip && rec < nrec) ? (tile[rec * FP_TS] & 63u) + 1u : 0u;
-            inclr[r] = wave_scan64(nkr[r]);
+            bool dup = false;
+            if (DEDUP && !skip && r * THREADS + (tid & ~63u) < nrec)             // (wave-uniform: waves without a record pass)
+                if (rec < nrec) dup = fp_dedup<C::DT, C::LOG_DT>(tile, dtab, dmul, rec);
+            nkr[r] = (!skip && rec < nrec && !dup) ? (tile[rec * FP_TS] & 63u) + 1u : 0u;
+            inclr[r] = wave_scan64(DEDUP ? nkr[r] | (nkr[r] ? 1u << 16 : 0u) : nkr[r]);
             if (lane == 63) wtot[r * NW + wv] = inclr[r];
         }
         if (tid == 0) { misc[FP_WIN] = 2 * NW; stk[0] = 0; stk[1] = 1; misc[FP_DEPTH] = 1; }
         __syncthreads();                                             // X1
         const unsigned wsum = lane < ROUNDS * NW ? wtot[lane] : 0u, wsc = row_scan16(wsum);
         const int wvu = __builtin_amdgcn_readfirstlane((int)wv);
-        const unsigned total = (unsigned)__builtin_amdgcn_readlane((int)wsc, ROUNDS * NW - 1);
+        const unsigned total = (unsigned)__builtin_amdgcn_readlane((int)wsc, ROUNDS * NW - 1) & (DEDUP ? 0xFFFFu : ~0u);
         skip |= total > MAXK;
 #pragma unroll
         for (unsigned r = 0; r < ROUNDS; ++r) {
             const unsigned base = (unsigned)__builtin_amdgcn_readlane((int)wsc, r * NW + wvu) - (unsigned)__builtin_amdgcn_readlane((int)wsum, r * NW + wvu);
             if (nkr[r] && !skip) {
-                const unsigned e = base + inclr[r] - nkr[r], rec = r * THREADS + tid;
+                const unsigned pe = base + inclr[r], rec = r * THREADS + tid;
+                const unsigned e = (DEDUP ? pe & 0xFFFFu : pe) - nkr[r], j = DEDUP ? (pe >> 16) - 1u : rec;
                 atomicOr(&bv32[e >> 5], 1u << (e & 31));
                 const unsigned w1 = (e + 63) >> 6;
-                if (64 * w1 < e + nkr[r]) Bw[w1] = (rec << 16) | e;
+                if (64 * w1 < e + nkr[r]) Bw[w1] = (j << 16) | e;
+                if (DEDUP) rinfo[j] = rec | ((1u + ((dmul[rec >> 1] >> (16u * (rec & 1u))) & 0xFFFFu)) << 16);     // (every copy was added before X1)
             }
         }
         __syncthreads();                                             // X2
@@ -1531,7 +1581,9 @@ __global__ void __launch_bounds__(THREADS, MINW) k_count_fp(uint32_t nb, uint32_
                 const unsigned c = (unsigned)__builtin_popcount(mle0 & ~1u) + (unsigned)__builtin_popcount(mle1);
                 const unsigned top = mle1 ? 63u - (unsigned)__builtin_clz(mle1) : 31u - (unsigned)__builtin_clz(mle0 | 1u);
                 const unsigned idx = active ? lane - (c ? top : (Bv & 0xFFFFu) - w * 64) : 0u;
-                const unsigned rec = active ? (Bv >> 16) + c : 0u;
+                const unsigned rj = active ? (Bv >> 16) + c : 0u;              // the rj-th record that is flattened ...
+                const uint32_t inf = DEDUP ? rinfo[rj] : rj;                   // ... is record `rec`, which stands for `inf >> 16` equal ones
+                const unsigned rec = inf & 0xFFFFu;
                 const uint32_t hdr = tile[rec * FP_TS];
                 // ---- B: cut out the k-mer, canonicalise, hash, look at its home slot
                 const FpInst x = fp_fetch(tile, rec, idx);
@@ -1556,7 +1608,7 @@ __global__ void __launch_bounds__(THREADS, MINW) k_count_fp(uint32_t nb, uint32_
                 const uint32_t old = atomicCAS(&tab[s], EMPTY, want ? ((tag << 16) | myref) : EMPTY);
                 const bool won = want & (old == EMPTY);
                 const bool done = hit | won;
-                atomicAdd(&cc[s], done ? 1u : 0u);
+                atomicAdd(&cc[s], done ? (DEDUP ? inf >> 16 : 1u) : 0u);
                 atomicOr(&cc[s], done ? ctx << 24 : 0u);
                 const bool parked = mine & !done;
                 unsigned nnew = (unsigned)__builtin_popcountll(__ballot(won));
@@ -1565,7 +1617,7 @@ __global__ void __launch_bounds__(THREADS, MINW) k_count_fp(uint32_t nb, uint32_
                     const unsigned below = (unsigned)__builtin_popcount((uint32_t)pm & lane_lt_lo) + (unsigned)__builtin_popcount((uint32_t)(pm >> 32) & lane_lt_hi);
                     const unsigned npark = (unsigned)__builtin_popcountll(pm);
                     // parked lanes take qn .. qn+npark-1, the others the (unused) entries behind them: qn + 63 <= 126 < QCAP
-                    qref[qn + (parked ? below : npark + lane - below)] = myref;
+                    qref[qn + (parked ? below : npark + lane - below)] = DEDUP ? myref | (inf & 0xFFFF0000u) : myref;
                     qn += npark;
                     if (qn >= 64) nnew += drain(64);
                 }
@@ -1735,6 +1787,8 @@ __global__ void __launch_bounds__(THREADS, MINW) k_count_fp(uint32_t nb, uint32_
         if (sp == 0) break;
         }
         for (unsigned i = tid; i < 2 * nwin + 2; i += THREADS) bv32[i] = 0;            // the next bucket's start bits (behind its barriers S1 and X1)
+        // the next bucket's record table and copy counts: the emit wrote over them, and its last reads of stcc / stref lie before barrier C
+        if (DEDUP) for (unsigned i = tid; i < C::DAREA; i += THREADS) dtab[i] = 0;
     }
     // ---- histogram, distinct count
     __syncthreads();
@@ -1742,6 +1796,16 @@ __global__ void __launch_bounds__(THREADS, MINW) k_count_fp(uint32_t nb, uint32_
     for (int o = 32; o > 0; o >>= 1) my_distinct += __shfl_down(my_distinct, o);
     if (lane == 0 && my_distinct) atomicAdd(&counters[1], my_distinct);
 }
+template <unsigned THREADS, unsigned MINW, unsigned TILE_, unsigned SC_>
+__global__ void __launch_bounds__(THREADS, MINW) k_count_fp(W2_FP_PARAMS) { count_fp_body<THREADS, TILE_, SC_, false>(W2_FP_ARGS); }
+// The dedup stage must not take the kernel past 120 VGPRs: a wavefront is given registers in steps of 8, and k_table_insert finds room beside
+// two resident 512-thread blocks of this kernel only while 4 x its allocation stays below the SIMD's 512 (round 4: at 128 it ran in the gaps,
+// 16 -> 33 ms).  Left alone the scheduler uses whatever occupancy 4 allows (124); the body needs 116.  (The attribute counts registers in
+// halves of the unified file: 60 = 120 VGPRs.  The 1024-thread shape with eight waves per SIMD keeps its bound of 64.)
+template <unsigned THREADS, unsigned MINW, unsigned TILE_, unsigned SC_>
+__global__ void __attribute__((amdgpu_num_vgpr(60))) __launch_bounds__(THREADS, MINW) k_count_fp_dedup(W2_FP_PARAMS) { count_fp_body<THREADS, TILE_, SC_, true>(W2_FP_ARGS); }
+#undef W2_FP_PARAMS
+#undef W2_FP_ARGS
 
 // =============================================================================== K4
 __global__ void __launch_bounds__(256) k_table_insert(uint64_t i0, uint64_t S, const uint64_t* __restrict__ shi, const uint64_t* __restrict__ slo,
@@ -2397,11 +2461,19 @@ int count_buckets_launch_slice(Ctx& c, unsigned k) {
     // 22 since K1 cuts 17 % fewer records (a 4500-k-mer bucket holds ~240): 512 resident records are enough -- 0.2 % of the buckets go to
     // the list kernel instead of 0.004 % -- and k_count_fp is 0.7 ms faster than with shape 20's 640 (three alternating runs, and the
     // planted workload within 0.2 ms: profiles/r04_sched_ab.txt)
-    if (cfg == 20) W2_TRY(launch_fp(k_count_fp<512, 4, 640, 768>, FpCfg<512, 640, 768>::LDS, 512, 2, FpCfg<512, 640, 768>::LIMIT, 768));
-    else if (cfg == 21) W2_TRY(launch_fp(k_count_fp<1024, 8, 576, 512>, FpCfg<1024, 576, 512>::LDS, 1024, 2, FpCfg<1024, 576, 512>::LIMIT, 512));
-    else if (cfg == 22) W2_TRY(launch_fp(k_count_fp<512, 4, 512, 1024>, FpCfg<512, 512, 1024>::LDS, 512, 2, FpCfg<512, 512, 1024>::LIMIT, 1024));
-    else if (cfg == 23) W2_TRY(launch_fp(k_count_fp<1024, 4, 576, 1024>, FpCfg<1024, 576, 1024>::LDS, 1024, 1, FpCfg<1024, 576, 1024>::LIMIT, 1024));
-    else if (cfg == 24) W2_TRY(launch_fp(k_count_fp<512, 4, 576, 1024>, FpCfg<512, 576, 1024>::LDS, 512, 2, FpCfg<512, 576, 1024>::LIMIT, 1024));
+    // Record dedup (NOTES.md section 18): byte-identical records of a bucket are counted once, with their multiplicity as the weight.  W2RAP_FP_DEDUP=0
+    // launches the form without it (the A/B, and the parity tests run both).
+    const char* ddv = getenv("W2RAP_FP_DEDUP");
+    const bool dedup = !(ddv && atoi(ddv) == 0);
+#define W2_FP_SHAPE(T, W, TL, S, BPC)                                                                                                                  \
+    W2_TRY(dedup ? launch_fp(k_count_fp_dedup<T, W, TL, S>, FpCfg<T, TL, S>::LDS_DEDUP, T, BPC, FpCfg<T, TL, S>::LIMIT, S)                             \
+                 : launch_fp(k_count_fp<T, W, TL, S>, FpCfg<T, TL, S>::LDS, T, BPC, FpCfg<T, TL, S>::LIMIT, S))
+    if (cfg == 20) W2_FP_SHAPE(512, 4, 640, 768, 2);
+    else if (cfg == 21) W2_FP_SHAPE(1024, 8, 576, 512, 2);
+    else if (cfg == 22) W2_FP_SHAPE(512, 4, 512, 1024, 2);
+    else if (cfg == 23) W2_FP_SHAPE(1024, 4, 576, 1024, 1);
+    else if (cfg == 24) W2_FP_SHAPE(512, 4, 576, 1024, 2);
+#undef W2_FP_SHAPE
     else if (cfg == 1) W2_TRY(launch(k_count_buckets<2048, 512>, K3Cfg<2048, 512>::LDS, 512, 2));
     else if (cfg == 2) W2_TRY(launch(k_count_buckets<4096, 512>, K3Cfg<4096, 512>::LDS, 512, 1));
     else if (cfg == 3) W2_TRY(launch(k_count_buckets<1024, 256>, K3Cfg<1024, 256>::LDS, 256, 4));
