@@ -9,7 +9,7 @@
  * 28-mers looked up against every edge object; every (edge, offset) hit is checked with a quality-aware sliding window, and the read is
  * placed -- path [edge], offset -- when exactly ONE candidate is good.  The graph is not edited; the output is the read paths.
  * AddNewStuff, the call in front of it, is w2rap_step5_add_new_stuff (at the end of this header).  The local assemblies, the clustering
- * half of Unsat and Steps 6-7 stay the reference's.
+ * half of Unsat and Step 6 stay the reference's (Step 7's read-sized passes: w2rap_step7.h).
  *
  * What runs where.  Everything runs in HIP kernels for gfx950 (the k5_* kernels of step5_partners.hip, the library's scans and radix sort);
  * there is no CPU fallback (W2RAP_E_NO_DEVICE).  The host checks the arguments and derives each edge's two vertices from the adjacency

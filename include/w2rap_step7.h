@@ -1,0 +1,176 @@
+/* w2rap_step7.h -- C ABI of the MI355X-native replacement for the read-sized passes of w2rap-contigger's Step 7 (PE scaffolding):
+ * the pairs of every line (GetLineNpairs, which Step 6 writes to .fin.lines.npairs and Step 7 reads back) and everything MakeGaps
+ * does up to its list of accepted gaps.  Exported by the same shared library as Steps 1-5 (w2rap_contigger_amd/libw2rap_step2.so).
+ *
+ *   LINES   GetTol, GetLineLengths, GetLineNpairs        src/paths/long/large/Lines.cc:329-355, Lines.h:74-117
+ *   LINKS   MakeGaps up to the accepted gaps             src/paths/long/large/MakeGaps.cc:25-427
+ * What stays the reference's: the graph edit and the truncation of the paths behind the accepted gaps (MakeGaps.cc:429-493),
+ * GAP_CLEANUP, FinalFiles, and FindLines -- the lines come in as data (the .fin.lines file, formats.read_lines).
+ *
+ * One call on host arrays; plain pointers and sizes; never throws; returns 0 or a W2RAP_E_* code (w2rap_step2.h) with a message in
+ * `err`.  There is no CPU fallback (W2RAP_E_NO_DEVICE).
+ *
+ * What runs where.  HIP kernels for gfx950 (the k7_* kernels of csrc/step7_links.hip, the library's scans and radix sort):
+ *   tol, llens and each line's end edges (a thread per line), npairs (a thread per pair), the nears (a thread per pair and pass:
+ *   count, 64-bit scan, fill, one radix sort of the packed (e1, e2) keys), their runs and the per-edge maxima, the bounded search
+ *   (a wavefront per distinct near), the links (compaction, sort by (first, second)) and the per-link filters (a thread per link).
+ * On the HOST, because they are E-sized or smaller, integer, and ORDER-DEPENDENT or tiny:
+ *   the edge groups tom / sink_like / source_like / dist_to_end (MakeGaps.cc:56-120) -- the two loops run in edge order, an edge reads
+ *   what an earlier edge of the same sweep has just written, and three passes do not converge that away, so a parallel sweep is wrong;
+ *   the set rules on the accepted links (MakeGaps.cc:353-427: one-to-one, bubble advance, UniqueSort, forced symmetry, overlinked) --
+ *   the list is no longer than the number of line ends.
+ *
+ * LINES.  tol[e] = the LAST line that names e (GetTol writes in line order).  llens[l] = the sum over the line's cells of: the one
+ *   path's K-mers; the mean of two paths ((a + b) / 2, integer); the median of three or more (for an even number the integer mean
+ *   of the two middle ones), kmers(e) = edge_len[e] - K + 1, an empty path 0.  npairs[l]: per pair (reads 2p, 2p+1) the SET of
+ *   tol[e] and tol[inv[e]] over both mates' edges; each line of the set counts once.  A pair counts even when one mate has no path.
+ *   The distinct-line step keeps a sorted list of up to W2RAP_STEP7_PAIR_LINES (16) lines per thread; a pair that names more lines
+ *   takes the spill path (every value is counted where it occurs first, found by rescanning; no storage) -- any number of lines, any
+ *   path length.  n_pairs_listed / n_pairs_spilled say which path the pairs took.
+ *
+ * LINKS.  Parameters min_line and min_link_count (the reference's main passes 5000 and 3); the other heuristics are the reference's
+ *   constants: max_hang 800, max_depth 2, max_int 1500, passes 3, max_cov_pc_off 20.0, max_line_to_ignore 500.
+ *   1. Edge groups (host): zpass 1 works on the REVERSED graph, zpass 2 on the graph as given (hb.Reverse() at the top of each,
+ *      six in all).  digraphE::Reverse swaps from_ with to_ and from_edge_obj_ with to_edge_obj_ per vertex, so the order inside an
+ *      adjacency list is kept: EdgeObjectIndexByIndexFrom(v, i) of the reversed graph is to_e[to_off[v] + i] of the graph as given.
+ *   2. Nears: per pair with both paths non-empty and per pass (pass 1: x = p1, y = inv of p2 reversed; pass 2: x = p2,
+ *      y = inv of p1 reversed): tom applied, consecutive duplicates compressed, edges on lines of llens <= 500 dropped, then
+ *      (x[j1], y[j2]) for every x[j1] that is not in y.  The per-thread list of y holds W2RAP_STEP7_NEAR_LIST (16) edges; a longer y
+ *      is rescanned from the path (any length).  nears1 / nears2 are only read as run lengths: near_max1[e] = the largest count of
+ *      any (e, .), near_max2[e] of any (., e), from the runs of the sorted nears.
+ *   3. Links: one candidate per distinct near, count = its run length.  close = e2 is met on a walk of at most 3 steps from e1 or
+ *      from e1's only predecessor (when to_left[e1] has exactly one in-edge); a step goes to an out-edge of the right vertex or an
+ *      in-edge of the left vertex; a node is stepped from only while its accumulated K-mers (the start not counted) are <= 1500.
+ *      The last step is not enumerated (e2 leaves v exactly when to_left[e2] == v).  Candidates that are not close are the links
+ *      (tom[e1], tom[e2], count) -- tom a second time, as the reference does -- sorted by (first, second); links equal after tom
+ *      stay separate entries, in the order of their nears.
+ *   4. Filters, in the reference's order; link_reason[i] = the first that rejects link i (W2RAP_STEP7_R_*), 0 = accepted.
+ *      The coverage test is IEEE double: cov = 100.0 * npairs / llens, c1 >= c2, rejected when c1 / c2 - 1.0 > 0.2: no pairs on one
+ *      side give inf and reject, none on both give NaN and pass.
+ *   5. Set rules (host) -> gap_from / gap_to sorted by (from, to), gap_inv[i] = the index of (inv[gap_to[i]], inv[gap_from[i]]), or
+ *      -1 where the overlinked rule has removed it (the reference asserts there).
+ *
+ * W2RAP_E_ARG before the device is touched: K outside [16, 640]; an unknown flag; min_line or min_link_count < 0; sizes beyond
+ * 32-bit ids (n_edge_objs, n_vertices, n_lines >= 2^31, n_paths >= 2^32 - 2); an odd n_paths; null arrays; edge_len < K; adjacency
+ * lists or inv that are not what they claim; path_off / path_edges faults; line offsets that do not start at 0, descend or do not end
+ * where the next level says; a line with an even number of cells (a line without cells included); a cell without a path (GetSegmentLength
+ * asserts there), so also an empty first or last cell; an empty first path in the first or last cell (MakeGaps reads
+ * lines[l].front()[0][0] and .back()[0][0]); a line edge outside [0, n_edge_objs); an edge object that belongs to no line (the
+ * reference indexes llens[-1] there); npairs given with n_npairs != n_lines, or LINKS asked without LINES and without npairs.
+ * W2RAP_E_LIMIT: a line whose paths, every path of every cell counted in full, hold 2^31 K-mers or more (llens is the reference's int).
+ */
+#ifndef W2RAP_STEP7_H_
+#define W2RAP_STEP7_H_
+
+#include "w2rap_step2.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+#define W2RAP_STEP7_LINES 1u
+#define W2RAP_STEP7_LINKS 2u
+
+#define W2RAP_STEP7_PAIR_LINES 16    /* LINES: distinct lines a pair's sorted list holds before the spill path takes over */
+#define W2RAP_STEP7_NEAR_LIST  16    /* LINKS: edges of y a thread keeps before it rescans the path instead */
+
+/* link_reason */
+#define W2RAP_STEP7_R_ACCEPTED   0
+#define W2RAP_STEP7_R_COUNT      1   /* count < min_link_count */
+#define W2RAP_STEP7_R_LINE       2   /* llens of either side < min_line */
+#define W2RAP_STEP7_R_COVERAGE   3   /* c1 / c2 - 1.0 > 0.2 */
+#define W2RAP_STEP7_R_ALT        4   /* max_alt > count */
+#define W2RAP_STEP7_R_LEFT_END   5   /* e1 (advanced past bubbles) is not the last edge of its line */
+#define W2RAP_STEP7_R_RIGHT_END  6   /* e2 (advanced) is not the first edge of its line */
+
+typedef struct w2rap_step7_in {
+    int32_t  K;                      /* hb.K(); 16 <= K <= 640 */
+    uint64_t n_edge_objs;
+    const uint32_t* edge_len;        /* [n_edge_objs] bases, >= K */
+    uint64_t n_vertices;
+    const uint64_t* from_off;        /* [n_vertices+1] */
+    const int32_t*  from_v;          /* [n_edge_objs] */
+    const int32_t*  from_e;          /* [n_edge_objs] */
+    const uint64_t* to_off;          /* [n_vertices+1] */
+    const int32_t*  to_e;            /* [n_edge_objs] */
+    const int32_t*  inv;             /* [n_edge_objs]; inv[inv[e]] == e */
+    uint64_t n_paths;                /* even: read r and read r ^ 1 are mates */
+    const uint64_t* path_off;        /* [n_paths+1] */
+    const int32_t*  path_edges;
+    /* the lines, vec<vec<vec<vec<int>>>> flattened: line -> cell -> path -> edge */
+    uint64_t n_lines;
+    const uint64_t* line_off;        /* [n_lines+1] into the cells */
+    const uint64_t* cell_off;        /* [n_cells+1] into the paths, n_cells = line_off[n_lines] */
+    const uint64_t* lpath_off;       /* [n_lpaths+1] into line_edges, n_lpaths = cell_off[n_cells] */
+    const int32_t*  line_edges;      /* [lpath_off[n_lpaths]] */
+    /* .fin.lines.npairs for LINKS without LINES; NULL: LINKS reads what LINES of this call counts.  With LINES and npairs both,
+       LINKS reads the GIVEN values */
+    uint64_t n_npairs;               /* == n_lines when npairs is given */
+    const int32_t*  npairs;
+} w2rap_step7_in;
+
+typedef struct w2rap_step7_params {
+    int32_t  device;                 /* HIP device ordinal */
+    uint32_t flags;                  /* any of W2RAP_STEP7_*, 0 = both */
+    int32_t  min_line;               /* MIN_LINE: the reference's main passes 5000 */
+    int32_t  min_link_count;         /* MIN_LINK_COUNT: the reference's main passes 3 */
+} w2rap_step7_params;
+
+/* outputs: library-allocated HOST memory, free with w2rap_step7_free.  A part that is not asked for launches no kernel of its own and
+ * leaves its pointers null, its counters and its time zero; tol and llens come back with either part */
+typedef struct w2rap_step7_out {
+    int32_t* tol;                    /* [n_edge_objs] */
+    int32_t* llens;                  /* [n_lines] */
+    int32_t* npairs;                 /* [n_lines]  LINES */
+    /* LINKS 1 */
+    int32_t* tom;                    /* [n_edge_objs] */
+    uint8_t* sink_like;              /* [n_edge_objs] */
+    uint8_t* source_like;            /* [n_edge_objs] */
+    int32_t* dist_to_end;            /* [n_edge_objs] */
+    /* LINKS 2 */
+    int32_t* near_max1;              /* [n_edge_objs] */
+    int32_t* near_max2;              /* [n_edge_objs] */
+    /* LINKS 3-4: every link, sorted by (from, to) */
+    int32_t* link_from;              /* [n_links] */
+    int32_t* link_to;
+    int32_t* link_count;
+    uint8_t* link_reason;            /* W2RAP_STEP7_R_* */
+    /* LINKS 5 */
+    int32_t* gap_from;               /* [n_gaps] */
+    int32_t* gap_to;
+    int32_t* gap_inv;
+    /* LINES counters: n_pairs = n_pairs_listed + n_pairs_spilled */
+    uint64_t n_pairs, n_pairs_listed, n_pairs_spilled;
+    uint64_t n_pairs_no_path;        /* of the listed: neither mate has a path (no line counted) */
+    uint64_t n_line_hits;            /* the sum of npairs */
+    /* LINKS counters */
+    uint64_t n_group_sink, n_group_source;     /* sink-like / source-like edges behind step 1 (dead ends and sources included) */
+    uint64_t n_group_loop1, n_group_loop2;     /* times the first / the second loop fired, over all six sweeps */
+    uint64_t n_pass_placed;          /* (pair, pass) with both paths non-empty = 2 x such pairs */
+    uint64_t n_pass_y_long;          /* of those: y longer than the per-thread list */
+    uint64_t n_pass_none;            /* of those: no near emitted */
+    uint64_t n_nears, n_near_kinds;  /* nears; distinct (e1, e2) = candidates */
+    uint64_t n_pred_start;           /* candidates whose search also starts from e1's only predecessor */
+    uint64_t n_close[4];             /* candidates found close, by the fewest steps: [0] e2 is that predecessor, [1..3] steps */
+    uint64_t n_links;                /* candidates that are not close */
+    uint64_t n_reason[7];            /* links per W2RAP_STEP7_R_* */
+    uint64_t n_not_one_to_one;       /* accepted links the one-to-one rule deleted */
+    uint64_t n_advanced;             /* of the remaining: moved past a bubble on either side */
+    uint64_t n_unique;               /* after UniqueSort (the reference's na) */
+    uint64_t n_sym_deleted;          /* "deleting N gaps ... */
+    int64_t  n_sym_added;            /* ... and adding M gaps to force symmetry": size after - na, as the reference prints it */
+    uint64_t n_overlinked;           /* gaps the overlinked rule deleted */
+    uint64_t n_gaps;
+    float ms_lines, ms_nears, ms_search, ms_filter;   /* device time per part, milliseconds (ms_lines: tol, llens, npairs) */
+} w2rap_step7_out;
+
+int  w2rap_step7_links(const w2rap_step7_in* in, const w2rap_step7_params* params, w2rap_step7_out* out, char* err, size_t errlen);
+void w2rap_step7_free(w2rap_step7_out* out);
+
+/* per-kernel device time of the last w2rap_step7_links in this process: "kernel_name total_ms launches\n" lines; returns the bytes needed */
+size_t w2rap_step7_profile(char* buf, size_t len);
+
+#ifdef __cplusplus
+}
+#endif
+#endif /* W2RAP_STEP7_H_ */

@@ -30,6 +30,8 @@ template <class In, class = void> struct has_bases : std::false_type {};
 template <class In> struct has_bases<In, std::void_t<decltype(In::edge_byte_off)>> : std::true_type {};
 template <class In, class = void> struct has_reads : std::false_type {};
 template <class In> struct has_reads<In, std::void_t<decltype(In::read_byte_off)>> : std::true_type {};
+template <class In, class = void> struct has_placements : std::false_type {};       // path_offset and read_len (w2rap_step7_in has neither)
+template <class In> struct has_placements<In, std::void_t<decltype(In::path_offset)>> : std::true_type {};
 
 // ---- sizes and null arrays.  (What a size beyond the limit is answered with differs from entry to entry: theirs to say)
 template <class In> bool too_large(const In& in, uint64_t reads_end) {
@@ -41,7 +43,8 @@ constexpr const char* ODD_PATHS = "n_paths is odd: reads r and r ^ 1 are mates";
 // graph_also_null: an array of the entry's own that every edge object needs is null
 template <class In> Err null_arrays(const In& in, bool graph_also_null = false) {
     const uint64_t E = in.n_edge_objs, NV = in.n_vertices, n = in.n_paths;
-    bool g = !in.edge_len || !in.from_v || !in.from_e || !in.to_e || graph_also_null, r = !in.path_offset || !in.path_off || !in.read_len;
+    bool g = !in.edge_len || !in.from_v || !in.from_e || !in.to_e || graph_also_null, r = !in.path_off;
+    if constexpr (has_placements<In>::value) r = r || !in.path_offset || !in.read_len;
     if constexpr (has_bases<In>::value) g = g || !in.edge_packed || !in.edge_byte_off;
     if constexpr (has_reads<In>::value) r = r || !in.read_byte_off || !in.qual_off;
     if (E && g) return bad("null graph array");
@@ -95,6 +98,67 @@ template <class In> Err crossings(const In& in) {
     for (uint64_t v = 0; v < in.n_vertices; ++v)
         if ((in.to_off[v + 1] - in.to_off[v]) * (in.from_off[v + 1] - in.from_off[v]) >= (1ull << 32)) return Err{W2RAP_E_LIMIT, "more than 2^32 crossings of one vertex"};
     return OK;
+}
+
+// ---- the involution: inv[e] in [0, E) and inv[inv[e]] == e (inv is not null)
+template <class In> Err involution(const In& in) {
+    const uint64_t E = in.n_edge_objs;
+    for (uint64_t e = 0; e < E; ++e) if (in.inv[e] < 0 || (uint64_t)in.inv[e] >= E) return bad("inv names an edge object that does not exist");
+    for (uint64_t e = 0; e < E; ++e) if ((uint64_t)in.inv[in.inv[e]] != e) return bad("inv is not an involution: inv[inv[e]] != e");
+    return OK;
+}
+
+// ---- the lines of Step 7 (w2rap_step7_in): three nested CSRs, line -> cell -> path -> edge
+// one level: off[0 .. n] starts at 0 and ascends
+inline Err csr_level(const uint64_t* off, uint64_t n, const char* null_msg, const char* start_msg, const char* order_msg) {
+    if (!off) return bad(null_msg);
+    if (off[0] != 0) return bad(start_msg);
+    for (uint64_t i = 0; i < n; ++i) if (off[i + 1] < off[i]) return bad(order_msg);
+    return OK;
+}
+// The shape MakeGaps and GetLineLengths rely on: an odd number of cells in every line; no cell without a path (so the first and the last
+// cell hold one); the first path of the first and of the last cell holds an edge; every edge id in [0, E)
+template <class In> Err lines(const In& in) {
+    const uint64_t NL = in.n_lines;
+    if (NL >= (1ull << 31)) return bad("2^31 lines or more: line ids are 32-bit");
+    if (!NL) return OK;
+    if (const Err e = csr_level(in.line_off, NL, "null line_off", "line_off must start at 0", "line_off is not ascending"); e.code) return e;
+    const uint64_t NC = in.line_off[NL];
+    if (const Err e = csr_level(in.cell_off, NC, "null cell_off", "cell_off must start at 0", "cell_off is not ascending"); e.code) return e;
+    const uint64_t NLP = in.cell_off[NC];
+    if (const Err e = csr_level(in.lpath_off, NLP, "null lpath_off", "lpath_off must start at 0", "lpath_off is not ascending"); e.code) return e;
+    const uint64_t NE = in.lpath_off[NLP];
+    if (NE && !in.line_edges) return bad("null line_edges");
+    for (uint64_t i = 0; i < NE; ++i) if (in.line_edges[i] < 0 || (uint64_t)in.line_edges[i] >= in.n_edge_objs) return bad("a line names an edge object that does not exist");
+    for (uint64_t l = 0; l < NL; ++l) {
+        const uint64_t c0 = in.line_off[l], c1 = in.line_off[l + 1];
+        if (((c1 - c0) & 1) == 0) return bad("a line with an even number of cells");
+        for (uint64_t cl = c0; cl < c1; ++cl) if (in.cell_off[cl + 1] == in.cell_off[cl]) return bad(cl == c0 || cl == c1 - 1 ? "the first or last cell of a line is empty" : "a cell without a path");
+        for (const uint64_t cl : {c0, c1 - 1}) { const uint64_t p = in.cell_off[cl]; if (in.lpath_off[p + 1] == in.lpath_off[p]) return bad("the first path of a line's first or last cell is empty"); }
+    }
+    return OK;
+}
+// behind lines(): every edge object belongs to a line (GetTol leaves -1 otherwise, and MakeGaps indexes llens with it)
+template <class In> Err lines_cover(const In& in) {
+    std::vector<char> seen(in.n_edge_objs, 0);
+    const uint64_t NE = in.n_lines ? in.lpath_off[in.cell_off[in.line_off[in.n_lines]]] : 0;
+    for (uint64_t i = 0; i < NE; ++i) seen[in.line_edges[i]] = 1;
+    for (uint64_t e = 0; e < in.n_edge_objs; ++e) if (!seen[e]) return bad("an edge object that belongs to no line");
+    return OK;
+}
+// behind lines() and edge_lens(): no line of 2^31 K-mers or more (a bound: every path of every cell counted in full)
+template <class In> Err line_lengths(const In& in) {
+    for (uint64_t l = 0; l < in.n_lines; ++l) {
+        uint64_t sum = 0;
+        for (uint64_t i = in.lpath_off[in.cell_off[in.line_off[l]]]; i < in.lpath_off[in.cell_off[in.line_off[l + 1]]]; ++i) sum += (uint64_t)in.edge_len[in.line_edges[i]] - (uint64_t)in.K + 1;
+        if (sum >= (1ull << 31)) return Err{W2RAP_E_LIMIT, "a line of 2^31 K-mers or more"};
+    }
+    return OK;
+}
+// npairs: one entry per line when given; `needed`: it must be given
+template <class In> Err npairs_given(const In& in, bool needed) {
+    if (!in.npairs) return needed && in.n_lines ? bad("LINKS without LINES needs npairs") : (in.n_npairs ? bad("null npairs") : OK);
+    return in.n_npairs != in.n_lines ? bad("npairs must have one entry per line") : OK;
 }
 
 // ---- read paths, reads and qualities

@@ -425,6 +425,118 @@ def read_paths(path):
     return offset, po, edges
 
 
+# --------------------------------------------------------------------------- lines, int vectors
+# BinaryWriter::writeFile of a vec<...> (feudal/BinaryStream.h:104-112, :477-494): "BINWRITE", then per vector a u64 size followed by its
+# elements -- nested vectors again, ints as 4 little-endian bytes.
+@dataclass
+class Lines:
+    """vec<vec<vec<vec<int>>>> flattened: line -> cell -> path -> edge (.fin.lines; the layout of w2rap_step7_in)"""
+    line_off: np.ndarray      # u64[n_lines+1] into the cells
+    cell_off: np.ndarray      # u64[n_cells+1] into the paths
+    lpath_off: np.ndarray     # u64[n_lpaths+1] into edges
+    edges: np.ndarray         # i32
+
+    @property
+    def n_lines(self):
+        return len(self.line_off) - 1
+
+    def nested(self):
+        """-> list (lines) of lists (cells) of lists (paths) of ints"""
+        lo, co, po = (np.asarray(a, np.int64) for a in (self.line_off, self.cell_off, self.lpath_off))
+        ed = np.asarray(self.edges).tolist()
+        return [[[ed[po[p]:po[p + 1]] for p in range(co[c], co[c + 1])] for c in range(lo[l], lo[l + 1])] for l in range(len(lo) - 1)]
+
+    @staticmethod
+    def from_nested(lines):
+        lo, co, po, ed = [0], [0], [0], []
+        for line in lines:
+            for cell in line:
+                for path in cell:
+                    ed.extend(int(e) for e in path)
+                    po.append(len(ed))
+                co.append(len(po) - 1)
+            lo.append(len(co) - 1)
+        return Lines(np.array(lo, np.uint64), np.array(co, np.uint64), np.array(po, np.uint64), np.array(ed, np.int32))
+
+
+def lines_to_bytes(lines: Lines) -> bytes:
+    lo, co, po = (np.asarray(a, np.int64) for a in (lines.line_off, lines.cell_off, lines.lpath_off))
+    ed = np.asarray(lines.edges, "<i4")
+    out = bytearray(b"BINWRITE")
+    out += struct.pack("<Q", len(lo) - 1)
+    for l in range(len(lo) - 1):
+        out += struct.pack("<Q", lo[l + 1] - lo[l])
+        for c in range(lo[l], lo[l + 1]):
+            out += struct.pack("<Q", co[c + 1] - co[c])
+            for p in range(co[c], co[c + 1]):
+                out += struct.pack("<Q", po[p + 1] - po[p])
+                out += ed[po[p]:po[p + 1]].tobytes()
+    return bytes(out)
+
+
+def write_lines(path, lines: Lines):
+    with open(path, "wb") as f:
+        f.write(lines_to_bytes(lines))
+
+
+def read_lines(path) -> Lines:
+    with open(path, "rb") as f:
+        raw = f.read()
+    if raw[:8] != b"BINWRITE":
+        raise ValueError(f"{path}: missing BINWRITE magic")
+    buf = memoryview(raw)
+    p = 8
+
+    def size():
+        nonlocal p
+        if p + 8 > len(raw):
+            raise ValueError(f"{path}: truncated")
+        (n,) = struct.unpack_from("<Q", buf, p)
+        p += 8
+        if n > len(raw) - p:                  # (an element takes four bytes at least: a size no file of this length can hold)
+            raise ValueError(f"{path}: a vector of {n} elements in a file of {len(raw)} bytes")
+        return n
+    lo, co, po, chunks, total = [0], [0], [0], [], 0
+    for _ in range(size()):
+        for _ in range(size()):
+            for _ in range(size()):
+                n = size()
+                if p + 4 * n > len(raw):
+                    raise ValueError(f"{path}: truncated")
+                chunks.append(np.frombuffer(buf, dtype="<i4", count=n, offset=p))
+                p += 4 * n
+                total += n
+                po.append(total)
+            co.append(len(po) - 1)
+        lo.append(len(co) - 1)
+    if p != len(raw):
+        raise ValueError(f"{path}: {len(raw) - p} trailing bytes")
+    edges = np.concatenate(chunks).astype(np.int32) if chunks else np.zeros(0, np.int32)
+    return Lines(np.array(lo, np.uint64), np.array(co, np.uint64), np.array(po, np.uint64), edges)
+
+
+def int_vec_to_bytes(v) -> bytes:
+    v = np.asarray(v, "<i4")
+    return b"BINWRITE" + struct.pack("<Q", len(v)) + v.tobytes()
+
+
+def write_int_vec(path, v):
+    """a vec<int> as BinaryWriter::writeFile leaves it (.fin.lines.npairs)"""
+    with open(path, "wb") as f:
+        f.write(int_vec_to_bytes(v))
+
+
+def read_int_vec(path) -> np.ndarray:
+    with open(path, "rb") as f:
+        raw = f.read()
+    if raw[:8] != b"BINWRITE" or len(raw) < 16:
+        raise ValueError(f"{path}: missing BINWRITE magic or size")
+    (n,) = struct.unpack_from("<Q", raw, 8)
+    if len(raw) != 16 + 4 * n:
+        raise ValueError(f"{path}: {n} ints announced, {len(raw) - 16} bytes behind the size")
+    return np.frombuffer(raw, dtype="<i4", count=n, offset=16).astype(np.int32)
+
+
 # --------------------------------------------------------------------------- freqs
 def freqs_text(hist) -> str:
     """hist: 101 counts -> small_K.freqs text (BuildReadQGraph.cc:1108-1112)"""

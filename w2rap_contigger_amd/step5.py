@@ -10,7 +10,7 @@ exactly one good (edge, offset) is placed there.  The graph is not edited.
 every read path is moved onto the new graph and re-extended over the branches with its bases and qualities.  `finish` is the two calls
 one after the other: given new_stuff, what the reference writes as .large_K.final.hbv/.paths.
 
-The rest of Step 5 (the local assemblies, the clustering half of Unsat) and Steps 6-7 stay the reference's.  The HIP library is the only
+The rest of Step 5 (the local assemblies, the clustering half of Unsat) and Step 6 stay the reference's (Step 7: step7.py).  The HIP library is the only
 implementation (no CPU fallback)."""
 from __future__ import annotations
 

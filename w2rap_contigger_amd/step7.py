@@ -1,0 +1,202 @@
+"""ctypes binding of the Step-7 entry point of libw2rap_step2.so (include/w2rap_step7.h), and a small command line.
+
+`line_stats` is GetTol, GetLineLengths and GetLineNpairs (src/paths/long/large/Lines.cc:329-355, Lines.h:74-117): the line of every
+edge, the length of every line in K-mers and the number of read pairs that touch it -- what the reference writes as .fin.lines.npairs.
+
+`find_gaps` is MakeGaps (src/paths/long/large/MakeGaps.cc:25-427) up to its list of accepted gaps: the edge groups, the nears of every
+read pair, the links that the bounded search does not find close, the per-link filters and the set rules.  The graph edit behind that
+list, GAP_CLEANUP, FinalFiles and FindLines stay the reference's; the lines come in as data (formats.read_lines).
+
+``python -m w2rap_contigger_amd.step7 DIR PREFIX`` reads DIR/PREFIX.contig.hbv, .contig.paths, .fin.lines and .fin.lines.npairs and
+writes the accepted gaps as text.  The HIP library is the only implementation (no CPU fallback)."""
+from __future__ import annotations
+
+import ctypes as C
+import sys
+from dataclasses import dataclass
+
+import numpy as np
+
+from . import formats as F
+from .step2 import Step2Error, _np_from, _ptr, lib as _lib2
+
+PARTS = {"lines": 1, "links": 2}            # W2RAP_STEP7_*
+PAIR_LINES = 16                             # W2RAP_STEP7_PAIR_LINES
+NEAR_LIST = 16                              # W2RAP_STEP7_NEAR_LIST
+REASONS = ("accepted", "count", "line", "coverage", "alt", "left_end", "right_end")      # W2RAP_STEP7_R_*
+
+
+class Step7In(C.Structure):
+    _fields_ = [("K", C.c_int32), ("n_edge_objs", C.c_uint64), ("edge_len", C.c_void_p), ("n_vertices", C.c_uint64), ("from_off", C.c_void_p), ("from_v", C.c_void_p),
+                ("from_e", C.c_void_p), ("to_off", C.c_void_p), ("to_e", C.c_void_p), ("inv", C.c_void_p),
+                ("n_paths", C.c_uint64), ("path_off", C.c_void_p), ("path_edges", C.c_void_p),
+                ("n_lines", C.c_uint64), ("line_off", C.c_void_p), ("cell_off", C.c_void_p), ("lpath_off", C.c_void_p), ("line_edges", C.c_void_p),
+                ("n_npairs", C.c_uint64), ("npairs", C.c_void_p)]
+
+
+class Step7Params(C.Structure):
+    _fields_ = [("device", C.c_int32), ("flags", C.c_uint32), ("min_line", C.c_int32), ("min_link_count", C.c_int32)]
+
+
+# name -> (dtype, the counter or size that gives its length)
+ARRAYS = {"tol": (np.int32, "E"), "llens": (np.int32, "NL"), "npairs": (np.int32, "NL"),
+          "tom": (np.int32, "E"), "sink_like": (np.uint8, "E"), "source_like": (np.uint8, "E"), "dist_to_end": (np.int32, "E"),
+          "near_max1": (np.int32, "E"), "near_max2": (np.int32, "E"),
+          "link_from": (np.int32, "n_links"), "link_to": (np.int32, "n_links"), "link_count": (np.int32, "n_links"), "link_reason": (np.uint8, "n_links"),
+          "gap_from": (np.int32, "n_gaps"), "gap_to": (np.int32, "n_gaps"), "gap_inv": (np.int32, "n_gaps")}
+LINES_COUNTERS = ("n_pairs", "n_pairs_listed", "n_pairs_spilled", "n_pairs_no_path", "n_line_hits")
+LINKS_COUNTERS = ("n_group_sink", "n_group_source", "n_group_loop1", "n_group_loop2", "n_pass_placed", "n_pass_y_long", "n_pass_none", "n_nears", "n_near_kinds",
+                  "n_pred_start", "n_close", "n_links", "n_reason", "n_not_one_to_one", "n_advanced", "n_unique", "n_sym_deleted", "n_sym_added", "n_overlinked", "n_gaps")
+PHASES = ("ms_lines", "ms_nears", "ms_search", "ms_filter")
+_CTYPE = {"n_close": C.c_uint64 * 4, "n_reason": C.c_uint64 * 7, "n_sym_added": C.c_int64}
+
+
+class Step7Out(C.Structure):
+    _fields_ = ([(k, C.c_void_p) for k in ARRAYS] + [(k, _CTYPE.get(k, C.c_uint64)) for k in LINES_COUNTERS + LINKS_COUNTERS] + [(k, C.c_float) for k in PHASES])
+
+
+_ready = False
+
+
+def lib():
+    global _ready
+    L = _lib2()
+    if not _ready:
+        L.w2rap_step7_links.argtypes = [C.POINTER(Step7In), C.POINTER(Step7Params), C.POINTER(Step7Out), C.c_char_p, C.c_size_t]
+        L.w2rap_step7_free.argtypes = [C.POINTER(Step7Out)]
+        L.w2rap_step7_free.restype = None
+        L.w2rap_step7_profile.argtypes = [C.c_char_p, C.c_size_t]
+        L.w2rap_step7_profile.restype = C.c_size_t
+        _ready = True
+    return L
+
+
+@dataclass
+class Step7Result:
+    """the arrays of include/w2rap_step7.h by name (None: the part was not asked for), the counters and the device times"""
+    arrays: dict
+    counters: dict
+    ms: dict
+
+    def __getattr__(self, k):
+        try:
+            return self.__dict__["arrays"][k]
+        except KeyError:
+            raise AttributeError(k)
+
+    def gaps(self):
+        return list(zip(self.arrays["gap_from"].tolist(), self.arrays["gap_to"].tolist()))
+
+
+def run(hbv: F.HBV, inv, paths, lines: F.Lines, parts=("lines", "links"), npairs=None, min_line=5000, min_link_count=3, device=0, flags=None) -> Step7Result:
+    """w2rap_step7_links.  paths = (offset, path_off u64[n+1], edges i32[]) as formats.read_paths gives them (the offsets are not read);
+    inv = the graph's involution; lines = formats.Lines; npairs = the .fin.lines.npairs values for LINKS without LINES (None: LINKS reads
+    what LINES of the same call counts).  flags overrides parts (the tests of the argument checks)."""
+    L = lib()
+    if flags is None:
+        flags = 0
+        for p in parts:
+            if p not in PARTS:
+                raise ValueError(f"unknown part {p!r}: one of {sorted(PARTS)}")
+            flags |= PARTS[p]
+        if not flags:
+            raise ValueError("no part asked for")
+    keep = [np.ascontiguousarray(hbv.edge_len, np.uint32), np.ascontiguousarray(hbv.from_off, np.uint64), np.ascontiguousarray(hbv.from_v, np.int32),
+            np.ascontiguousarray(hbv.from_e, np.int32), np.ascontiguousarray(hbv.to_off, np.uint64), np.ascontiguousarray(hbv.to_e, np.int32),
+            np.ascontiguousarray(inv, np.int32), np.ascontiguousarray(paths[1], np.uint64), np.ascontiguousarray(paths[2], np.int32),
+            np.ascontiguousarray(lines.line_off, np.uint64), np.ascontiguousarray(lines.cell_off, np.uint64), np.ascontiguousarray(lines.lpath_off, np.uint64),
+            np.ascontiguousarray(lines.edges, np.int32), None if npairs is None else np.ascontiguousarray(npairs, np.int32)]
+    if len(keep[6]) != len(keep[0]):
+        raise ValueError("inv must have one entry per edge object")
+    if len(keep[7]) < 1 or len(keep[9]) < 1 or len(keep[10]) != int(keep[9][-1]) + 1 or len(keep[11]) != int(keep[10][-1]) + 1:
+        raise ValueError("path_off, line_off, cell_off and lpath_off must each have one entry more than what they divide")
+    E, NL = len(keep[0]), len(keep[9]) - 1
+    p = lambda a: _ptr(a) if a is not None and len(a) else None
+    i = Step7In(hbv.K, E, p(keep[0]), hbv.n_vertices, p(keep[1]), p(keep[2]), p(keep[3]), p(keep[4]), p(keep[5]), p(keep[6]), len(keep[7]) - 1, p(keep[7]), p(keep[8]),
+                NL, p(keep[9]), p(keep[10]), p(keep[11]), p(keep[12]), 0 if npairs is None else len(keep[13]), p(keep[13]))
+    prm = Step7Params(device, flags, min_line, min_link_count)
+    o = Step7Out()
+    err = C.create_string_buffer(1024)
+    rc = L.w2rap_step7_links(C.byref(i), C.byref(prm), C.byref(o), err, 1024)
+    if rc:
+        raise Step2Error(rc, err.value.decode(errors="replace"))
+    try:
+        size = {"E": E, "NL": NL, "n_links": int(o.n_links), "n_gaps": int(o.n_gaps)}
+        arrays = {k: (_np_from(getattr(o, k), dt, size[n]) if getattr(o, k) else None) for k, (dt, n) in ARRAYS.items()}
+        counters = {}
+        for k in LINES_COUNTERS + LINKS_COUNTERS:
+            v = getattr(o, k)
+            counters[k] = [int(x) for x in v] if k in ("n_close", "n_reason") else int(v)
+        return Step7Result(arrays, counters, {k: float(getattr(o, k)) for k in PHASES})
+    finally:
+        L.w2rap_step7_free(C.byref(o))
+
+
+def line_stats(hbv: F.HBV, inv, paths, lines: F.Lines, device=0) -> Step7Result:
+    """Part LINES: tol, llens and npairs (GetTol, GetLineLengths, GetLineNpairs)"""
+    return run(hbv, inv, paths, lines, parts=("lines",), device=device)
+
+
+def find_gaps(hbv: F.HBV, inv, paths, lines: F.Lines, npairs=None, min_line=5000, min_link_count=3, device=0) -> Step7Result:
+    """MakeGaps up to the accepted gaps.  npairs None: counted in the same call (part LINES); given: read as the reference's MakeGaps
+    reads .fin.lines.npairs, and part LINES does not run"""
+    return run(hbv, inv, paths, lines, parts=("lines", "links") if npairs is None else ("links",), npairs=npairs, min_line=min_line, min_link_count=min_link_count, device=device)
+
+
+def profile():
+    """-> {kernel name: (total ms, launches)} of the last call in this process"""
+    L = lib()
+    n = L.w2rap_step7_profile(None, 0)
+    buf = C.create_string_buffer(int(n) + 16)
+    L.w2rap_step7_profile(buf, len(buf))
+    out = {}
+    for line in buf.value.decode().splitlines():
+        name, ms, k = line.rsplit(" ", 2)
+        out[name] = (float(ms), int(k))
+    return out
+
+
+def involution(hbv: F.HBV) -> np.ndarray:
+    """HyperBasevector::Involution (src/paths/HyperBasevector.cc:648-660): the i-th edge object in sequence order pairs with the i-th in
+    the order of the reverse complements.  In a graph that holds the reverse complement of every edge object once, any total order
+    gives the same pairing: inv[e] is the object whose sequence is e's reverse complement"""
+    codes, off = hbv.edge_codes()
+    seq = [codes[int(off[e]):int(off[e + 1])] for e in range(hbv.n_edges)]
+    x1 = sorted(range(len(seq)), key=lambda e: seq[e].tobytes())
+    x2 = sorted(range(len(seq)), key=lambda e: (3 - seq[e][::-1]).astype(np.uint8).tobytes())
+    inv = np.zeros(len(seq), np.int32)
+    inv[x1] = x2
+    return inv
+
+
+def gaps_text(res: Step7Result) -> str:
+    """one line per accepted gap: "from to inverse", then the line the reference prints about the forced symmetry"""
+    a = res.arrays
+    body = "".join(f"{f} {t} {i}\n" for f, t, i in zip(a["gap_from"].tolist(), a["gap_to"].tolist(), a["gap_inv"].tolist()))
+    return body + f"# deleting {res.counters['n_sym_deleted']} gaps and adding {res.counters['n_sym_added']} gaps to force symmetry\n"
+
+
+def main(argv=None):
+    import argparse
+    import os
+    ap = argparse.ArgumentParser(prog="python -m w2rap_contigger_amd.step7", description="MakeGaps' accepted gaps from PREFIX.contig.hbv/.paths and PREFIX.fin.lines/.npairs")
+    ap.add_argument("dir"); ap.add_argument("prefix")
+    ap.add_argument("--min_line", type=int, default=5000); ap.add_argument("--min_link_count", type=int, default=3)
+    ap.add_argument("--device", type=int, default=0)
+    ap.add_argument("-o", "--out", default=None, help="the text file to write (default DIR/PREFIX.gaps.txt)")
+    a = ap.parse_args(argv)
+    stem = os.path.join(a.dir, a.prefix)
+    hbv = F.read_hbv(stem + ".contig.hbv")
+    paths = F.read_paths(stem + ".contig.paths")
+    lines = F.read_lines(stem + ".fin.lines")
+    npairs = F.read_int_vec(stem + ".fin.lines.npairs")
+    res = find_gaps(hbv, involution(hbv), paths, lines, npairs=npairs, min_line=a.min_line, min_link_count=a.min_link_count, device=a.device)
+    out = a.out or stem + ".gaps.txt"
+    with open(out, "w") as f:
+        f.write(gaps_text(res))
+    print(f"{res.counters['n_gaps']} gaps of {res.counters['n_links']} links ({res.counters['n_nears']} nears) -> {out}")
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
