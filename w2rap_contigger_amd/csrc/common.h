@@ -276,6 +276,63 @@ constexpr unsigned REC_MAXK = 64;
 constexpr unsigned REC_HB = 32;
 #endif
 constexpr unsigned REC_BYTES = 4 * REC_DWORDS;
+
+// The record of the run `meta` of the read at byte `ro` of the packed bases (the one definition of the format: K2 and the slab route's
+// cutter both call it).  meta: bits 15:0 first k-mer position p, 21:16 nk-1, 22 hasL, 23 hasR.  Cuts the 2*(nk+61) stream bits
+// [left flank][k-mers' bases][right flank] out of the read with five unaligned 8-byte loads (byte by byte at the end of the allocation).
+__host__ __device__ inline void rec_build(const uint8_t* __restrict__ bases, uint64_t bases_bytes, uint64_t ro, uint32_t meta, uint32_t (&out)[REC_DWORDS]) {
+    const unsigned p = meta & 0xFFFFu, nk = ((meta >> 16) & 63u) + 1u;
+    const bool hasL = (meta >> 22) & 1u, hasR = (meta >> 23) & 1u;
+    const unsigned q = p ? p - 1 : 0;                          // first base taken from the read
+    const uint64_t byte0 = ro + ((2 * q) >> 3);
+    const unsigned sh = (2 * q) & 7;
+    uint64_t W[5];
+#pragma unroll
+    for (unsigned j = 0; j < 5; ++j) {
+        const uint64_t a = byte0 + 8 * j;
+        uint64_t w = 0;
+        if (a + 8 <= bases_bytes) w = reinterpret_cast<const U64u*>(bases + a)->v;
+        else for (unsigned t = 0; t < 8; ++t) if (a + t < bases_bytes) w |= (uint64_t)bases[a + t] << (8 * t);
+        W[j] = w;
+    }
+    uint64_t O[4];
+#pragma unroll
+    for (unsigned j = 0; j < 4; ++j) O[j] = sh ? (W[j] >> sh) | (W[j + 1] << (64 - sh)) : W[j];
+    if (!p) {                                                  // no base before base 0: a zero left flank
+        O[3] = (O[3] << 2) | (O[2] >> 62); O[2] = (O[2] << 2) | (O[1] >> 62); O[1] = (O[1] << 2) | (O[0] >> 62); O[0] <<= 2;
+    }
+    unsigned nbits = 2 * (nk + 61);
+    if (!hasR) nbits -= 2;                                     // the right flank is not part of the k-mer run
+#pragma unroll
+    for (unsigned j = 0; j < 4; ++j) {
+        if (nbits <= 64 * j) O[j] = 0;
+        else if (nbits < 64 * (j + 1)) O[j] &= (1ull << (nbits - 64 * j)) - 1;
+    }
+    const uint32_t hdr = (nk - 1) | (hasL ? 64u : 0u) | (hasR ? 128u : 0u);
+    if constexpr (REC_HB == 8) {                               // 256 bits: the header byte, the stream behind it
+        O[3] = (O[3] << 8) | (O[2] >> 56); O[2] = (O[2] << 8) | (O[1] >> 56); O[1] = (O[1] << 8) | (O[0] >> 56);
+        O[0] = (O[0] << 8) | (uint64_t)hdr;
+#pragma unroll
+        for (unsigned j = 0; j < 4; ++j) { out[2 * j] = (uint32_t)O[j]; out[2 * j + 1] = (uint32_t)(O[j] >> 32); }
+    } else {
+        out[0] = hdr;
+#pragma unroll
+        for (unsigned j = 0; j < 4; ++j) { out[(1 + 2 * j) % REC_DWORDS] = (uint32_t)O[j]; out[(2 + 2 * j) % REC_DWORDS] = (uint32_t)(O[j] >> 32); }
+    }
+}
+
+// ---- bucket slabs (the partition's slab route, NOTES.md section 19): bucket b owns records [b * C, (b + 1) * C) of the record array; the
+// records of rank >= C lie in an overflow segment behind the nb slabs, bucket by bucket (ovbase: the exclusive scan of max(0, count - C)).
+// -> the record's place, in records
+__host__ __device__ inline uint64_t slab_place(uint32_t b, uint32_t rank, uint32_t C, uint64_t nb, uint64_t ovbase_b) {
+    return rank < C ? (uint64_t)b * C + rank : nb * C + ovbase_b + (rank - C);
+}
+// A bucket's segment for the counting kernels as one word: first record (37 bits) | records << 37 (27 bits; the kernels refuse 2^26 and more)
+constexpr unsigned SEG_START_BITS = 37;
+constexpr uint32_t SEG_PACKED = 1u << 31;      // in the counting kernels' bucket-count argument (<= 2^24): the segment table holds such words
+__host__ __device__ inline uint64_t seg_pack(uint64_t start, uint64_t count) {
+    return start | ((count < (1ull << 26) ? count : (1ull << 26)) << SEG_START_BITS);
+}
 constexpr unsigned MMER = 15;                 // minimizer length
 constexpr unsigned WIN = K - MMER + 1;        // m-mers per k-mer window (46)
 

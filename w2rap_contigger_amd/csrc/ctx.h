@@ -50,6 +50,8 @@ struct Ctx {
     uint64_t* d_bbase = nullptr;        // [NB+1] first record of each bucket
     uint32_t* d_recs = nullptr;         // records, REC_DWORDS each
     uint64_t nrec = 0;
+    uint32_t slab_cap = 0;              // != 0: d_recs is NB slabs of slab_cap records + an overflow segment, d_bbase the scan of the buckets' excess
+                                        // (count_partition_slabs; the next count reads packed segments)
     uint64_t solid_cap = 0;
     uint64_t* d_shi = nullptr;          // solid k-mers (device order)
     uint64_t* d_slo = nullptr;
@@ -76,6 +78,7 @@ struct Ctx {
     unsigned cs_ns = 0;                 // slices launched so far
     unsigned cs_planned = 0;            // slices of the pending count (0: none pending)
     uint32_t cs_nbl = 0, cs_nseg = 0; const uint32_t* cs_recs = nullptr;
+    bool cs_packed = false;             // cs_off holds seg_pack() words (slab route), not a scan
     bool cs_short_first = false;        // slice 0 covers half as many buckets as the others
     hipEvent_t cs_ev[16] = {};
     unsigned long long* cs_cnt = nullptr;   // device counters of the pending count

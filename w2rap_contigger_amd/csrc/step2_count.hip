@@ -3,6 +3,7 @@
 //   K1  k_superkmers      canonical-minimizer super-k-mers: bucket histogram + one descriptor per record
 //   K2  k_scatter_records descriptor -> 32-B record in its bucket  (K1+K2 replace the leaf loop :1062-1080 and
 //                                                                   std::sort's partitioning :1081)
+//       (one GPU, one pass, reads of up to 315 good bases: K1 stores the records itself, into a slab per bucket -- count_partition_slabs)
 //   K3  k_count_buckets   per-bucket LDS hash count/merge          (collapse_entries :1002-1013, combine_Entries :943-949,
 //                         + min_freq filter + histogram             filter :1094-1104)
 //   K4  k_table_insert    lookup table over solid k-mers           (new BRQ_Dict + insertEntryNoLocking :1092-1099)
@@ -402,14 +403,20 @@ __global__ void __launch_bounds__(256, MINW) k_superkmers(uint64_t n, uint32_t c
 // staged descriptors into final ones 64 at a time -- the histogram atomic returns the rank -- and stores them coalesced: the 64 reads'
 // slots are one contiguous piece of s_desc.  Runs are cut at bucket changes and when a record is full (REC_MAXK = 63 k-mers);
 // the kernel above also cuts at every multiple of 64 (its half-passes).
-template <unsigned SMAX, bool ALIGN64>
-__global__ void __launch_bounds__(256, 4) k_superkmers_lane(uint64_t n, const uint8_t* __restrict__ bases, const uint64_t* __restrict__ boff,
+// SLABS (NOTES.md section 19): every bucket owns records [b * C, (b + 1) * C) of `recs`, so the rank the histogram atomic returns IS the
+// record's place: the tail builds the 32-B record itself (rec_build, K2's code; the wave's reads are 2.4 KB it loaded a moment ago) and
+// stores it as K2 does -- through LDS, two lanes per record, 16 B each -- and no descriptor is written.  Ranks >= C go to the overflow list
+// like a read's records beyond its S slots; K2's list branch places both.  The LDS it needs is the part of the staging area whose
+// descriptors the lanes hold in registers by then.
+template <unsigned SMAX, bool ALIGN64, bool SLABS = false, unsigned MINW = 4>
+__global__ void __launch_bounds__(256, MINW) k_superkmers_lane(uint64_t n, const uint8_t* __restrict__ bases, const uint64_t* __restrict__ boff,
                                                             const uint16_t* __restrict__ good, uint32_t nb, uint32_t pb_lo, uint32_t pb_hi,
                                                             uint32_t* __restrict__ bcount, uint32_t nbl_part, uint32_t inv_nbl,
                                                             unsigned long long* __restrict__ part_kmers, uint2* __restrict__ s_desc, uint32_t S,
                                                             uint32_t* __restrict__ o_read, uint32_t* __restrict__ o_bkt, uint32_t* __restrict__ o_meta,
-                                                            uint32_t* __restrict__ o_rank, uint64_t ov_cap, unsigned long long* __restrict__ ov_cursor) {
-    __shared__ uint2 stage_[4][64 * SMAX];
+                                                            uint32_t* __restrict__ o_rank, uint64_t ov_cap, unsigned long long* __restrict__ ov_cursor,
+                                                            uint32_t* __restrict__ recs, uint32_t slab_cap, uint64_t bases_bytes) {
+    __shared__ __attribute__((aligned(16))) uint2 stage_[4][64 * SMAX];
     __shared__ uint32_t spart_[4][64];
     const unsigned lane = threadIdx.x & 63, wv_ = threadIdx.x >> 6;
     const uint64_t r0 = ((uint64_t)blockIdx.x * 4 + wv_) * 64;
@@ -537,6 +544,49 @@ __global__ void __launch_bounds__(256, 4) k_superkmers_lane(uint64_t n, const ui
                 }
             }
         }
+        if constexpr (SLABS && REC_DWORDS == 8) {
+            // the 512 staged descriptors of this group are in registers: their 4 KB hold the 64 records of a round (2 KB) and their places
+            static_assert(SMAX >= 8, "a group of eight slots per lane is the tail's record buffer");
+            uint4* s_rec = reinterpret_cast<uint4*>(stage + 64 * u0);                       // [128]
+            uint64_t* s_dst = reinterpret_cast<uint64_t*>(stage + 64 * u0 + 256);           // [64]
+#pragma unroll 1
+            for (unsigned k = 0; k < 8 && u0 + k < S; ++k) {                                 // (one copy of the builder: d[] and rk[] rotate through element 0)
+                const unsigned i = lane + 64 * (u0 + k);
+                const uint2 dk = d[0]; const uint32_t rkk = rk[0];
+#pragma unroll
+                for (unsigned t = 0; t < 7; ++t) { d[t] = d[t + 1]; rk[t] = rk[t + 1]; }
+                uint64_t dst = ~0ull;
+                uint32_t out[REC_DWORDS] = {};
+                const uint32_t rd = (uint32_t)(r0 + i / S);
+                const bool listed = dk.y != NONE32 && rkk >= slab_cap;
+                if (dk.y != NONE32 && !listed) {
+                    rec_build(bases, bases_bytes, boff[rd], dk.y, out);
+                    dst = slab_place(dk.x, rkk, slab_cap, 0, 0) * REC_DWORDS;
+                }
+                // beyond the slab: the list, its cursor taken ONCE for the wave's lanes (every wave's atomics on that one word queue up behind each other)
+                const unsigned long long lm = __ballot(listed);
+                if (lm) {
+                    unsigned long long o0 = 0;
+                    if (lane == (unsigned)__ffsll((long long)lm) - 1u) o0 = atomicAdd(ov_cursor, (unsigned long long)__popcll(lm));
+                    o0 = ((unsigned long long)(unsigned)__shfl((int)(o0 >> 32), __ffsll((long long)lm) - 1) << 32) | (unsigned)__shfl((int)o0, __ffsll((long long)lm) - 1);
+                    const unsigned long long o = o0 + __popcll(lm & ((1ull << lane) - 1ull));
+                    if (listed && o < ov_cap) { o_read[o] = rd; o_bkt[o] = dk.x; o_meta[o] = dk.y; o_rank[o] = rkk; }
+                }
+                wave_lds_fence();                                                            // (the round before has left the buffer)
+                s_rec[2 * lane] = make_uint4(out[0], out[1], out[2], out[3]);
+                s_rec[2 * lane + 1] = make_uint4(out[4], out[5], out[6], out[7]);
+                s_dst[lane] = dst;
+                wave_lds_fence();
+#pragma unroll
+                for (unsigned j = 0; j < 2; ++j) {
+                    const unsigned idx = j * 64 + lane;
+                    const uint64_t t = s_dst[idx >> 1];
+                    if (t != ~0ull) reinterpret_cast<uint4*>(recs + t)[idx & 1u] = s_rec[idx];
+                }
+            }
+            wave_lds_fence();
+            continue;
+        }
 #pragma unroll
         for (unsigned k = 0; k < 8; ++k) {
             const unsigned i = lane + 64 * (u0 + k);
@@ -576,7 +626,7 @@ __global__ void __launch_bounds__(256) k_scatter_records(uint64_t nslots, uint32
                                                           const uint8_t* __restrict__ bases,
                                                           const uint64_t* __restrict__ boff, uint64_t bases_bytes,
                                                           const uint64_t* __restrict__ bbase,
-                                                          uint32_t* __restrict__ recs) {
+                                                          uint32_t* __restrict__ recs, uint32_t slab_cap, uint64_t slab_nb) {
     // A wavefront's 64 records leave through LDS: built one per lane, stored REC_DWORDS lanes per record, so that every store
     // instruction carries eight whole 32-B records (seven of 36 B in a W2RAP_REC36 build) as contiguous bursts instead of 64 scattered dwords.
     __shared__ __attribute__((aligned(16))) uint32_t s_rec[4][64 * REC_DWORDS];
@@ -598,47 +648,10 @@ __global__ void __launch_bounds__(256) k_scatter_records(uint64_t nslots, uint32
     uint64_t dst = ~0ull;
     uint32_t out[REC_DWORDS] = {};
     if (valid) {
-        const uint64_t base = bbase[b];
-        const unsigned p = meta & 0xFFFFu, nk = ((meta >> 16) & 63u) + 1u;
-        const bool hasL = (meta >> 22) & 1u, hasR = (meta >> 23) & 1u;
-        const uint64_t ro = boff[r];
-        const unsigned q = p ? p - 1 : 0;                          // first base taken from the read
-        const uint64_t byte0 = ro + ((2 * q) >> 3);
-        const unsigned sh = (2 * q) & 7;
-        uint64_t W[5];
-#pragma unroll
-        for (unsigned j = 0; j < 5; ++j) {
-            const uint64_t a = byte0 + 8 * j;
-            uint64_t w = 0;
-            if (a + 8 <= bases_bytes) w = reinterpret_cast<const U64u*>(bases + a)->v;
-            else for (unsigned t = 0; t < 8; ++t) if (a + t < bases_bytes) w |= (uint64_t)bases[a + t] << (8 * t);
-            W[j] = w;
-        }
-        uint64_t O[4];
-#pragma unroll
-        for (unsigned j = 0; j < 4; ++j) O[j] = sh ? (W[j] >> sh) | (W[j + 1] << (64 - sh)) : W[j];
-        if (!p) {                                                  // no base before base 0: a zero left flank
-            O[3] = (O[3] << 2) | (O[2] >> 62); O[2] = (O[2] << 2) | (O[1] >> 62); O[1] = (O[1] << 2) | (O[0] >> 62); O[0] <<= 2;
-        }
-        unsigned nbits = 2 * (nk + 61);
-        if (!hasR) nbits -= 2;                                     // the right flank is not part of the k-mer run
-#pragma unroll
-        for (unsigned j = 0; j < 4; ++j) {
-            if (nbits <= 64 * j) O[j] = 0;
-            else if (nbits < 64 * (j + 1)) O[j] &= (1ull << (nbits - 64 * j)) - 1;
-        }
-        const uint32_t hdr = (nk - 1) | (hasL ? 64u : 0u) | (hasR ? 128u : 0u);
-        if constexpr (REC_HB == 8) {                               // 256 bits: the header byte, the stream behind it
-            O[3] = (O[3] << 8) | (O[2] >> 56); O[2] = (O[2] << 8) | (O[1] >> 56); O[1] = (O[1] << 8) | (O[0] >> 56);
-            O[0] = (O[0] << 8) | (uint64_t)hdr;
-#pragma unroll
-            for (unsigned j = 0; j < 4; ++j) { out[2 * j] = (uint32_t)O[j]; out[2 * j + 1] = (uint32_t)(O[j] >> 32); }
-        } else {
-            out[0] = hdr;
-#pragma unroll
-            for (unsigned j = 0; j < 4; ++j) { out[(1 + 2 * j) % REC_DWORDS] = (uint32_t)O[j]; out[(2 + 2 * j) % REC_DWORDS] = (uint32_t)(O[j] >> 32); }
-        }
-        dst = (base + slot) * REC_DWORDS;
+        // (slab route, nslots == 0: the listed records only -- into the bucket's slab, or beyond it into the overflow segment, bbase its scan)
+        const uint64_t place = slab_cap ? slab_place(b, slot, slab_cap, slab_nb, slot < slab_cap ? 0 : bbase[b]) : bbase[b] + slot;
+        rec_build(bases, bases_bytes, boff[r], meta, out);
+        dst = place * REC_DWORDS;
     }
     if constexpr (REC_DWORDS == 8) {
         reinterpret_cast<uint4*>(s_rec[wv])[2 * lane] = make_uint4(out[0], out[1], out[2], out[3]);
@@ -788,9 +801,13 @@ __global__ void __launch_bounds__(THREADS, MINW) k_count_buckets(uint32_t nb, ui
     auto seg_load = [&](uint32_t bb, uint64_t& r0, uint32_t& cnt) {
         r0 = 0; cnt = 0;
         if (tid < nseg && bb < b_hi) {
-            const uint64_t a = roff[(uint64_t)tid * nb + bb], e = roff[(uint64_t)tid * nb + bb + 1];
-            r0 = a; cnt = (uint32_t)(e - a);
-            if (e - a >= (1ull << 26)) { cnt = 0; counters[3] = 2; }     // keeps 24-bit counts and 32-bit dword indices exact
+            // (SEG_PACKED in nb: roff[seg * nb + bb] is seg_pack(first record, records) -- the slab route's segments are no scan)
+            const uint64_t at = (uint64_t)tid * (nb & ~SEG_PACKED) + bb;
+            uint64_t a = roff[at], len;
+            if (nb & SEG_PACKED) { len = a >> SEG_START_BITS; a &= (1ull << SEG_START_BITS) - 1; }
+            else len = roff[at + 1] - a;
+            r0 = a; cnt = (uint32_t)len;
+            if (len >= (1ull << 26)) { cnt = 0; counters[3] = 2; }     // keeps 24-bit counts and 32-bit dword indices exact
         }
     };
     auto seg_store = [&](unsigned q, uint64_t r0, uint32_t cnt) {       // wave 0 only
@@ -1376,8 +1393,11 @@ __device__ __forceinline__ void count_fp_body(W2_FP_PARAMS) {
     auto seg_load = [&](uint32_t bb, uint64_t& r0, uint32_t& cnt) {
         r0 = 0; cnt = 0;
         if (tid < nseg && bb < b_hi) {
-            const uint64_t a = roff[(uint64_t)tid * nb + bb], e = roff[(uint64_t)tid * nb + bb + 1];
-            r0 = a; cnt = e - a < (1ull << 20) ? (uint32_t)(e - a) : (1u << 20);       // (anything beyond the tile is deferred)
+            const uint64_t at = (uint64_t)tid * (nb & ~SEG_PACKED) + bb;                // (SEG_PACKED: see k_count_buckets)
+            uint64_t a = roff[at], len;
+            if (nb & SEG_PACKED) { len = a >> SEG_START_BITS; a &= (1ull << SEG_START_BITS) - 1; }
+            else len = roff[at + 1] - a;
+            r0 = a; cnt = len < (1ull << 20) ? (uint32_t)len : (1u << 20);              // (anything beyond the tile is deferred)
         }
     };
     auto seg_store = [&](unsigned q, uint64_t r0, uint32_t cnt) {       // wave 0 only
@@ -2055,6 +2075,12 @@ static bool k1_wave(uint32_t spp, uint32_t npass) {
     const char* k1v = getenv("W2RAP_K1");
     return (k1v && !strcmp(k1v, "wave")) || spp * npass > 16;
 }
+// descriptor slots per pass of 128 k-mer positions (W2RAP_SPP, default 8) and passes of the longest read: the one place they are derived
+static void k1_slots(const Ctx& c, uint32_t* spp, uint32_t* npass) {
+    const char* sv = getenv("W2RAP_SPP");
+    *spp = sv ? (uint32_t)atoi(sv) : 8;
+    *npass = c.max_len > K + 127 ? (c.max_len - (K - 1) + 127) / 128 : 1;
+}
 
 __global__ void __launch_bounds__(256) k_k1_passes(uint64_t n, const uint16_t* __restrict__ good, uint32_t* __restrict__ np) {
     const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -2083,10 +2109,30 @@ static int k1_pass_offsets(Ctx& c, uint64_t nr, const uint16_t* good, uint64_t* 
 static int launch_k1(Ctx& c, uint64_t nr, const uint64_t* boff, const uint16_t* good, uint32_t pb_lo, uint32_t pb_hi, uint32_t* bcount,
                      uint32_t nbl_part, uint32_t inv_nbl, unsigned long long* d_part, uint2* s_desc, uint32_t spp, uint32_t npass,
                      const uint64_t* pass_off /* k1_wave: k1_pass_offsets' */,
-                     uint32_t* o_read, uint32_t* o_bkt, uint32_t* o_meta, uint32_t* o_rank, uint64_t ov_cap, unsigned long long* d_ov_cur) {
+                     uint32_t* o_read, uint32_t* o_bkt, uint32_t* o_meta, uint32_t* o_rank, uint64_t ov_cap, unsigned long long* d_ov_cur,
+                     uint32_t* slab_recs = nullptr, uint32_t slab_cap = 0, uint64_t bases_bytes = 0 /* the slab route: the lane kernel stores the records */) {
     if (getenv("W2RAP_TRACE"))                           // the route (tests assert it: a moved threshold must not go unnoticed)
-        fprintf(stderr, "[w2rap] K1 route: %s, npass %u, spp %u, %llu reads, longest %u\n", k1_wave(spp, npass) ? "wave" : "lane",
-                npass, spp, (unsigned long long)nr, c.max_len);
+        fprintf(stderr, "[w2rap] K1 route: %s, npass %u, spp %u, %llu reads, longest %u, records %s %u\n", k1_wave(spp, npass) ? "wave" : "lane",
+                npass, spp, (unsigned long long)nr, c.max_len, slab_cap ? "to slabs of" : "by scatter pass", slab_cap);
+    if (slab_cap) {
+        if (k1_wave(spp, npass) || REC_DWORDS != 8) { c.err = "partition: the slab route is the lane kernel's"; return W2RAP_E_STATE; }
+#define W2_K1S(SMAX, MINW) LAUNCH(c, "k_superkmers_lane", (k_superkmers_lane<SMAX, false, true, MINW>), dim3((unsigned)((nr + 255) / 256)), dim3(256), 0, nr, c.d_bases, \
+                                  boff, good, c.NB, pb_lo, pb_hi, bcount, nbl_part, inv_nbl, d_part, (uint2*)nullptr, spp * npass, o_read, o_bkt, o_meta, o_rank, ov_cap,   \
+                                  d_ov_cur, slab_recs, slab_cap, bases_bytes)
+        // (eight slots per read -- PE150 -- need half the staging area, so more than four blocks fit a CU, and the tail is a chain of round
+        // trips that only other waves hide: K1 14.5 / 13.6 / 11.9 ms at 4 / 5 / 6 waves per SIMD -- the last with 15 VGPRs spilled --, 16.5 at
+        // 7 and 8, whose instantiations are not kept (NOTES.md section 19).  The six-wave figure rests on WHERE the allocator puts those
+        // spills: two small edits of the tail moved them and lost the whole gain.  After any edit of the kernel, measure 4 / 5 / 6 again
+        // (W2RAP_TEST_K1_SLAB_WAVES = 4, 5: a test hook, announced like the others))
+        int waves = 6;
+        if (const char* wv = getenv("W2RAP_TEST_K1_SLAB_WAVES")) { if (test_hook("W2RAP_TEST_K1_SLAB_WAVES")) waves = atoi(wv); }
+        if (spp * npass > 8 || waves == 4) W2_K1S(16, 4);
+        else if (waves == 5) W2_K1S(8, 5);
+        else W2_K1S(8, 6);
+#undef W2_K1S
+        W2_HIP(hipGetLastError());
+        return 0;
+    }
     if (!k1_wave(spp, npass)) {
         // (four waves per SIMD: with five -- the staging area of 8 slots per read would leave room -- the scatter pass beside it loses more
         // than this kernel gains, partition 20.6 -> 23.8 ms; W2RAP_K1_ALIGN64: the cuts of the wavefront-per-read kernel, for the test that
@@ -2094,7 +2140,7 @@ static int launch_k1(Ctx& c, uint64_t nr, const uint64_t* boff, const uint16_t* 
         const bool a64 = getenv("W2RAP_K1_ALIGN64") != nullptr;
         const dim3 grid((unsigned)((nr + 255) / 256));
 #define W2_K1L(A64) LAUNCH(c, "k_superkmers_lane", (k_superkmers_lane<16, A64>), grid, dim3(256), 0, nr, c.d_bases, boff, good, c.NB, pb_lo, pb_hi, bcount, \
-                           nbl_part, inv_nbl, d_part, s_desc, spp * npass, o_read, o_bkt, o_meta, o_rank, ov_cap, d_ov_cur)
+                           nbl_part, inv_nbl, d_part, s_desc, spp * npass, o_read, o_bkt, o_meta, o_rank, ov_cap, d_ov_cur, (uint32_t*)nullptr, 0u, 0ull)
         if (a64) W2_K1L(true); else W2_K1L(false);
 #undef W2_K1L
         W2_HIP(hipGetLastError());
@@ -2129,7 +2175,7 @@ int count_partition(Ctx& c, uint32_t nb, uint32_t n_parts, uint32_t pb_lo, uint3
     hipStream_t st = c.stream;
     const uint64_t n = c.n;
     if (n >= (1ull << 32)) { c.err = "more than 2^32 reads on one GPU (32-bit read ids in the record descriptors)"; return W2RAP_E_LIMIT; }
-    c.NB = nb;
+    c.NB = nb; c.slab_cap = 0;
     if (c.d_bcount) c.release(c.d_bcount);
     if (c.d_bbase) c.release(c.d_bbase);
     if (c.d_recs) c.release(c.d_recs);
@@ -2145,9 +2191,8 @@ int count_partition(Ctx& c, uint32_t nb, uint32_t n_parts, uint32_t pb_lo, uint3
     // descriptor slots: spp per (read, pass of 128 k-mer positions).  A pass of a PE150 read cuts into ~4 records,
     // 8 slots hold all but ~1 % of them; the surplus goes to the overflow list.  If even that list is too small the
     // pass is repeated with twice the slots (128 cannot overflow).
-    const char* sv = getenv("W2RAP_SPP");
-    uint32_t spp = sv ? (uint32_t)atoi(sv) : 8;
-    const uint32_t npass = c.max_len > K + 127 ? (c.max_len - (K - 1) + 127) / 128 : 1;
+    uint32_t spp, npass;
+    k1_slots(c, &spp, &npass);
     uint2* s_desc = nullptr; uint32_t *o_read = nullptr, *o_bkt = nullptr, *o_meta = nullptr, *o_rank = nullptr;
     uint64_t ov_cap = n / 8 + 1024;
     W2_ALLOC(o_read, uint32_t, ov_cap); W2_ALLOC(o_bkt, uint32_t, ov_cap); W2_ALLOC(o_meta, uint32_t, ov_cap); W2_ALLOC(o_rank, uint32_t, ov_cap);
@@ -2188,10 +2233,10 @@ int count_partition(Ctx& c, uint32_t nb, uint32_t n_parts, uint32_t pb_lo, uint3
         const uint64_t nthreads = nslots + nov;
         if (wave)
             LAUNCH(c, "k_scatter_records", k_scatter_records<true>, dim3((unsigned)((nthreads + 255) / 256)), dim3(256), 0, nslots, spp, pass_off, n, s_desc,
-                   nov, o_read, o_bkt, o_meta, o_rank, c.d_bases, c.d_boff, bases_bytes, c.d_bbase, c.d_recs);
+                   nov, o_read, o_bkt, o_meta, o_rank, c.d_bases, c.d_boff, bases_bytes, c.d_bbase, c.d_recs, 0u, 0ull);
         else
         LAUNCH(c, "k_scatter_records", k_scatter_records<false>, dim3((unsigned)((nthreads + 255) / 256)), dim3(256), 0, nslots, npass * spp, nullptr, 0, s_desc,
-               nov, o_read, o_bkt, o_meta, o_rank, c.d_bases, c.d_boff, bases_bytes, c.d_bbase, c.d_recs);
+               nov, o_read, o_bkt, o_meta, o_rank, c.d_bases, c.d_boff, bases_bytes, c.d_bbase, c.d_recs, 0u, 0ull);
         W2_HIP(hipGetLastError());
     }
     W2_HIP(hipStreamSynchronize(st));
@@ -2212,7 +2257,7 @@ int count_partition_batched(Ctx& c, uint32_t nb, unsigned n_batches, unsigned* n
     if (n >= (1ull << 32)) { c.err = "more than 2^32 reads on one GPU (32-bit read ids in the record descriptors)"; return W2RAP_E_LIMIT; }
     if (n_batches < 1) n_batches = 1; if (n_batches > 16) n_batches = 16;
     if (n < (1u << 20) || !st2) n_batches = 1;
-    c.NB = nb;
+    c.NB = nb; c.slab_cap = 0;
     if (c.d_bcount) c.release(c.d_bcount);
     if (c.d_bbase) { c.release(c.d_bbase); c.d_bbase = nullptr; }
     if (c.d_recs) c.release(c.d_recs);
@@ -2223,9 +2268,8 @@ int count_partition_batched(Ctx& c, uint32_t nb, unsigned n_batches, unsigned* n
     uint32_t *o_read[2] = {nullptr, nullptr}, *o_bkt[2] = {nullptr, nullptr}, *o_meta[2] = {nullptr, nullptr}, *o_rank[2] = {nullptr, nullptr};
     unsigned long long* d_ov_cur = nullptr;
     W2_ALLOC(d_ov_cur, unsigned long long, 2);
-    const char* sv = getenv("W2RAP_SPP");
-    uint32_t spp = sv ? (uint32_t)atoi(sv) : 8;
-    const uint32_t npass = c.max_len > K + 127 ? (c.max_len - (K - 1) + 127) / 128 : 1;
+    uint32_t spp, npass;
+    k1_slots(c, &spp, &npass);
     // equal batches (W2RAP_LAST_BATCH < 1: a shorter last one, whose scatter pass is the one nothing hides -- measured in round 4: no difference)
     const double last_frac = getenv("W2RAP_LAST_BATCH") ? std::min(1.0, std::max(0.1, atof(getenv("W2RAP_LAST_BATCH")))) : 1.0;
     const uint64_t per_batch = n_batches > 1 ? (((uint64_t)((double)n / ((double)n_batches - 1.0 + last_frac)) + 2) & ~1ull) : ((n + 1) & ~1ull);
@@ -2295,10 +2339,10 @@ int count_partition_batched(Ctx& c, uint32_t nb, unsigned n_batches, unsigned* n
             const uint64_t nthreads = nslots + nov;
             if (wave)
                 LAUNCH_ON(c, sk, "k_scatter_records", k_scatter_records<true>, dim3((unsigned)((nthreads + 255) / 256)), dim3(256), 0, nslots, spp, pass_off[b], nr, s_desc[b],
-                          nov, o_read[b], o_bkt[b], o_meta[b], o_rank[b], c.d_bases, c.d_boff + r0, bases_bytes, d_bbase[b], c.d_recs + seg_base * REC_DWORDS);
+                          nov, o_read[b], o_bkt[b], o_meta[b], o_rank[b], c.d_bases, c.d_boff + r0, bases_bytes, d_bbase[b], c.d_recs + seg_base * REC_DWORDS, 0u, 0ull);
             else
             LAUNCH_ON(c, sk, "k_scatter_records", k_scatter_records<false>, dim3((unsigned)((nthreads + 255) / 256)), dim3(256), 0, nslots, npass * spp, nullptr, 0, s_desc[b],
-                      nov, o_read[b], o_bkt[b], o_meta[b], o_rank[b], c.d_bases, c.d_boff + r0, bases_bytes, d_bbase[b], c.d_recs + seg_base * REC_DWORDS);
+                      nov, o_read[b], o_bkt[b], o_meta[b], o_rank[b], c.d_bases, c.d_boff + r0, bases_bytes, d_bbase[b], c.d_recs + seg_base * REC_DWORDS, 0u, 0ull);
             W2_HIP(hipGetLastError());
         }
         W2_HIP(hipEventCreateWithFlags(&ev_k2[k], hipEventDisableTiming));
@@ -2316,6 +2360,155 @@ int count_partition_batched(Ctx& c, uint32_t nb, unsigned n_batches, unsigned* n
     c.release(d_ov_cur);
     *n_seg = nseg;
     return 0;
+}
+
+// ---- K1 alone, records into bucket slabs (single GPU, one hash-range pass, lane route; NOTES.md section 19): bucket b owns records
+// [b * C, (b + 1) * C) of c.d_recs -- not zeroed, the counts bound every read --, the cutter stores a record where its rank atomic says, and
+// what it cannot store from its tail (a read's records beyond its staged slots, ranks >= C) goes through the overflow list: K2's list
+// branch puts the former into their slabs and the latter into an overflow segment behind the slabs (c.d_bbase: the scan of the buckets'
+// excess).  One launch over all reads, one host wait.  c.d_bcount: [nb]; the count reads two (start, count) segments per bucket.
+__global__ void __launch_bounds__(256) k_slab_excess(uint32_t nb, const uint32_t* __restrict__ bcount, uint32_t C, uint32_t* __restrict__ excess) {
+    const uint32_t b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b < nb) excess[b] = bcount[b] > C ? bcount[b] - C : 0u;
+}
+__global__ void __launch_bounds__(256) k_slab_segments(uint32_t nb, const uint32_t* __restrict__ bcount, uint32_t C, const uint64_t* __restrict__ ovbase,
+                                                        uint64_t* __restrict__ seg /* [2][nb] */) {
+    const uint32_t b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= nb) return;
+    const uint32_t n = bcount[b];
+    seg[b] = seg_pack((uint64_t)b * C, n < C ? n : C);
+    seg[(uint64_t)nb + b] = seg_pack((uint64_t)nb * C + ovbase[b], n > C ? n - C : 0u);
+}
+
+// records per slab: the resident tile of the shipped k_count_fp shape -- the buckets that overflow are the ones it defers anyway
+static constexpr uint32_t SLAB_CAP = 512;
+
+// whether this count takes the slab route, and its C (0: the scatter pass)
+static uint32_t slab_route(const Ctx& c, uint32_t nb, unsigned npass_hash) {
+    const char* sv = getenv("W2RAP_K1_SLABS");
+    if (sv && atoi(sv) == 0) return 0;
+    if (REC_DWORDS != 8 || npass_hash != 1 || !c.n || getenv("W2RAP_K1_ALIGN64")) return 0;
+    uint32_t spp, npass;
+    k1_slots(c, &spp, &npass);
+    if (!spp || k1_wave(spp, npass)) return 0;
+    uint32_t C = SLAB_CAP;
+    if (const char* t = getenv("W2RAP_TEST_SLAB_CAP")) { if (test_hook("W2RAP_TEST_SLAB_CAP")) C = (uint32_t)std::max(1, atoi(t)); }
+    // the slabs take no more than a quarter of the free HBM (the rule of auto_passes), and a segment word holds every record's number
+    size_t free_b = 0, total_b = 0;
+    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess || !free_b) return 0;
+    const double need = (double)nb * C * REC_BYTES + (double)c.M / 15.0 * REC_BYTES * 0.25;
+    if (need > (double)free_b / 4.0 || (double)nb * C + (double)c.M >= (double)(1ull << SEG_START_BITS)) return 0;
+    return C;
+}
+
+// The slab route pays for every record beyond its slab: the overflow list has ONE cursor word, and its atomics queue up behind each other
+// (~2 ns a listed record: 8.7 M of them -- 50 M reads of a genome with repeat families -- make K1 29 ms instead of 11.5, against 17.5 ms for
+// the scatter pass; the routes break even near reads / 18 such records).  So inputs of 2^20 reads and more are asked first: the old lane
+// kernel cuts the first 1/32 of the reads (0.4 ms at 50 M), and the records its buckets hold beyond C / 32, times 32, estimate the records
+// beyond the slabs.  The estimate runs high by about reads / 25 -- ordinary buckets near C, whose sampled counts scatter above C / 32 --, so
+// the limit is reads / 10 (SLAB_EXCESS_DIV): above it the scatter pass.  -> *est
+static constexpr uint32_t SLAB_EXCESS_DIV = 10;
+static constexpr uint32_t SLAB_SAMPLE = 32;
+static int slab_excess_estimate(Ctx& c, uint32_t nb, uint32_t C, uint64_t* est) {
+    hipStream_t st = c.stream;
+    uint32_t spp, npass;
+    k1_slots(c, &spp, &npass);
+    const uint64_t ns = c.n / SLAB_SAMPLE, lcap = ns / 8 + 1024;
+    c.NB = nb;
+    uint32_t *cnt = nullptr, *exc = nullptr, *o_read = nullptr, *o_bkt = nullptr, *o_meta = nullptr, *o_rank = nullptr;
+    uint64_t* scan = nullptr; uint2* s_desc = nullptr; unsigned long long* d_ov_cur = nullptr;
+    auto run = [&]() -> int {
+        W2_ALLOC(cnt, uint32_t, nb); W2_ALLOC(exc, uint32_t, nb); W2_ALLOC(scan, uint64_t, (uint64_t)nb + 1); W2_ALLOC(s_desc, uint2, ns * spp * npass);
+        W2_ALLOC(d_ov_cur, unsigned long long, 2);
+        W2_ALLOC(o_read, uint32_t, lcap); W2_ALLOC(o_bkt, uint32_t, lcap); W2_ALLOC(o_meta, uint32_t, lcap); W2_ALLOC(o_rank, uint32_t, lcap);
+        W2_HIP(hipMemsetAsync(cnt, 0, (size_t)nb * 4, st));
+        W2_HIP(hipMemsetAsync(d_ov_cur, 0, 16, st));
+        W2_TRY(launch_k1(c, ns, c.d_boff, c.d_good, 0, nb, cnt, 0u, 0u, nullptr, s_desc, spp, npass, nullptr, o_read, o_bkt, o_meta, o_rank, lcap, d_ov_cur));
+        LAUNCH(c, "k_slab_excess", k_slab_excess, dim3((nb + 255) / 256), dim3(256), 0, nb, cnt, std::max(1u, C / SLAB_SAMPLE), exc);
+        W2_HIP(hipGetLastError());
+        W2_TRY(exclusive_scan_u32_to_u64(c, exc, scan, nb));
+        uint64_t h = 0;
+        W2_HIP(hipMemcpyAsync(&h, scan + nb, 8, hipMemcpyDeviceToHost, st));
+        W2_HIP(hipStreamSynchronize(st));
+        *est = h * SLAB_SAMPLE;
+        return 0;
+    };
+    const int rc = run();
+    for (void* q : {(void*)cnt, (void*)exc, (void*)scan, (void*)s_desc, (void*)d_ov_cur, (void*)o_read, (void*)o_bkt, (void*)o_meta, (void*)o_rank}) if (q) c.release(q);
+    return rc;
+}
+
+// *refused: the overflow list of an input of 2^20 reads and more was too small after all (the estimate's sample was not like the rest): nothing
+// is kept, the caller takes the scatter pass -- a second cut of all reads costs more than that.  Smaller inputs are cut again into a list of
+// the exact size.
+int count_partition_slabs(Ctx& c, uint32_t nb, uint32_t C, bool* refused) {
+    *refused = false;
+    if (!c.quality_done) { c.err = "partition before quality_windows"; return W2RAP_E_STATE; }
+    hipStream_t st = c.stream;
+    const uint64_t n = c.n;
+    if (n >= (1ull << 32)) { c.err = "more than 2^32 reads on one GPU (32-bit read ids in the record descriptors)"; return W2RAP_E_LIMIT; }
+    c.NB = nb;
+    if (c.d_bcount) c.release(c.d_bcount);
+    if (c.d_bbase) c.release(c.d_bbase);
+    if (c.d_recs) c.release(c.d_recs);
+    c.d_bcount = nullptr; c.d_bbase = nullptr; c.d_recs = nullptr;
+    uint32_t* d_excess = nullptr;
+    unsigned long long* d_ov_cur = nullptr;
+    uint32_t *o_read = nullptr, *o_bkt = nullptr, *o_meta = nullptr, *o_rank = nullptr;
+    auto drop_lists = [&]() { for (uint32_t** q : {&o_read, &o_bkt, &o_meta, &o_rank}) if (*q) { c.release(*q); *q = nullptr; } };
+    auto run = [&]() -> int {
+        W2_ALLOC(c.d_bcount, uint32_t, nb);
+        W2_ALLOC(c.d_bbase, uint64_t, (uint64_t)nb + 1);
+        W2_ALLOC(d_excess, uint32_t, nb);
+        W2_ALLOC(d_ov_cur, unsigned long long, 2);
+        uint32_t spp, npass;
+        k1_slots(c, &spp, &npass);
+        uint64_t bases_bytes = 0;
+        W2_HIP(hipMemcpy(&bases_bytes, c.d_boff + n, 8, hipMemcpyDeviceToHost));
+        // every record of the overflow segment is a listed one: a list that held them all bounds the segment
+        uint64_t ov_cap = n / 8 + 1024, nov = 0, n_excess = 0;
+        const dim3 bgrid((nb + 255) / 256);
+        for (;;) {
+            W2_ALLOC(o_read, uint32_t, ov_cap); W2_ALLOC(o_bkt, uint32_t, ov_cap); W2_ALLOC(o_meta, uint32_t, ov_cap); W2_ALLOC(o_rank, uint32_t, ov_cap);
+            W2_ALLOC(c.d_recs, uint32_t, ((uint64_t)nb * C + ov_cap) * REC_DWORDS);
+            W2_HIP(hipMemsetAsync(c.d_bcount, 0, (size_t)nb * 4, st));
+            W2_HIP(hipMemsetAsync(d_ov_cur, 0, 16, st));
+            W2_TRY(launch_k1(c, n, c.d_boff, c.d_good, 0, nb, c.d_bcount, 0u, 0u, nullptr, nullptr, spp, npass, nullptr, o_read, o_bkt, o_meta, o_rank, ov_cap, d_ov_cur,
+                             c.d_recs, C, bases_bytes));
+            LAUNCH(c, "k_slab_excess", k_slab_excess, bgrid, dim3(256), 0, nb, c.d_bcount, C, d_excess);
+            W2_HIP(hipGetLastError());
+            W2_TRY(exclusive_scan_u32_to_u64(c, d_excess, c.d_bbase, nb));
+            unsigned long long h_ov = 0;
+            W2_HIP(hipMemcpyAsync(&n_excess, c.d_bbase + nb, 8, hipMemcpyDeviceToHost, st));
+            W2_HIP(hipMemcpyAsync(&h_ov, d_ov_cur, 8, hipMemcpyDeviceToHost, st));
+            W2_HIP(hipStreamSynchronize(st));
+            nov = h_ov;
+            if (nov <= ov_cap) break;
+            // the list was too small: its exact need is known now (the cut does not depend on the list)
+            drop_lists();
+            c.release(c.d_recs); c.d_recs = nullptr;
+            if (n >= (1ull << 20)) { *refused = true; return 0; }
+            ov_cap = nov + nov / 8 + 1024;
+        }
+        if (n_excess > nov) { c.err = "partition: more records beyond the slabs than the overflow list holds"; return W2RAP_E_STATE; }
+        if (nov) {
+            LAUNCH(c, "k_scatter_records", k_scatter_records<false>, dim3((unsigned)((nov + 255) / 256)), dim3(256), 0, 0ull, npass * spp, nullptr, 0, nullptr,
+                   nov, o_read, o_bkt, o_meta, o_rank, c.d_bases, c.d_boff, bases_bytes, c.d_bbase, c.d_recs, C, (uint64_t)nb);
+            W2_HIP(hipGetLastError());
+        }
+        W2_HIP(hipStreamSynchronize(st));
+        if (getenv("W2RAP_TRACE"))
+            fprintf(stderr, "[w2rap] partition slabs: %u buckets x %u records, %llu listed records, %llu beyond their slab\n", nb, C, (unsigned long long)nov,
+                    (unsigned long long)n_excess);
+        c.slab_cap = C;
+        c.nrec = (uint64_t)nb * C + n_excess;                // (the extent of c.d_recs in use)
+        return 0;
+    };
+    const int rc = run();
+    drop_lists();
+    if (d_excess) c.release(d_excess);
+    if (d_ov_cur) c.release(d_ov_cur);
+    return rc;
 }
 
 // ---- K3: count `nbl` buckets whose records arrive in `nseg` segments (one per source rank), each
@@ -2350,6 +2543,12 @@ int count_buckets_launch(Ctx& c, uint32_t min_freq, uint32_t nbl, uint32_t nseg,
     const uint64_t nflat = (uint64_t)nbl * nseg;
     uint64_t* d_off = nullptr;
     W2_ALLOC(d_off, uint64_t, nflat + 1);
+    c.cs_packed = c.slab_cap != 0;
+    if (c.cs_packed) {                                   // bucket slabs + overflow segment: (start | count) words, count_partition_slabs
+        if (nseg != 2 || d_counts != c.d_bcount || !c.d_bbase) { c.err = "count_records: the slab layout has two segments"; return W2RAP_E_STATE; }
+        LAUNCH(c, "k_slab_segments", k_slab_segments, dim3((nbl + 255) / 256), dim3(256), 0, nbl, d_counts, c.slab_cap, c.d_bbase, d_off);
+        W2_HIP(hipGetLastError());
+    } else
     W2_TRY(exclusive_scan_u32_to_u64(c, d_counts, d_off, nflat));
     // A later pass of a multi-pass count (c.pass > 0) appends to the solid arrays, the chunk list, the counters and the histogram of
     // the passes before it; everything else is this pass's own.
@@ -2399,6 +2598,7 @@ int count_buckets_launch_slice(Ctx& c, unsigned k) {
     if (!c.cs_planned || k != c.cs_ns || k >= c.cs_planned) { c.err = "count_records_launch: slices are launched once each, in order"; return W2RAP_E_STATE; }
     const unsigned NS = c.cs_planned;
     const uint32_t nbl = c.cs_nbl, nseg = c.cs_nseg;
+    const uint32_t nb_arg = nbl | (c.cs_packed ? SEG_PACKED : 0u);     // the kernels' segment-table stride, with the table's form
     unsigned long long* d_cnt = c.cs_cnt;
     // (the bucket queue in a 128-byte line of its own: the counters behind d_cnt + 4 take one same-address atomic per bucket too -- its output range --,
     //  and two hot words in one line share one L2 channel's atomic unit)
@@ -2419,7 +2619,7 @@ int count_buckets_launch_slice(Ctx& c, unsigned k) {
         W2_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
         unsigned grid = (unsigned)std::min<uint64_t>(b_hi - b_lo, (uint64_t)c.sm_count * blocks_per_cu);
         if (k || c.pass) W2_HIP(hipMemsetAsync(d_queue, 0, 4, st));
-        LAUNCH(c, "k_count_buckets", kern, dim3(grid ? grid : 1), dim3(threads), lds, nbl, b_lo, b_hi, nseg, c.cs_off, c.cs_recs, c.min_freq, d_queue,
+        LAUNCH(c, "k_count_buckets", kern, dim3(grid ? grid : 1), dim3(threads), lds, nb_arg, b_lo, b_hi, nseg, c.cs_off, c.cs_recs, c.min_freq, d_queue,
                c.d_shi, c.d_slo, c.d_scc, c.solid_cap, d_cnt + 4, d_cnt + 8, c.d_chunk_start, c.d_chunk_cnt, c.cs_chunk_cap, (const uint32_t*)nullptr, 0u);
         W2_HIP(hipGetLastError());
         return slice_done();
@@ -2437,7 +2637,7 @@ int count_buckets_launch_slice(Ctx& c, unsigned k) {
         uint32_t fill_limit = fp_limit, solid_limit = fp_sc;
         if (const char* t = getenv("W2RAP_TEST_FP_LIMIT")) { if (test_hook("W2RAP_TEST_FP_LIMIT")) fill_limit = std::min<uint32_t>(fill_limit, (uint32_t)std::max(1, atoi(t))); }
         if (const char* t = getenv("W2RAP_TEST_FP_SC")) { if (test_hook("W2RAP_TEST_FP_SC")) solid_limit = std::min<uint32_t>(solid_limit, (uint32_t)std::max(1, atoi(t))); }
-        LAUNCH(c, "k_count_fp", kern, dim3(grid ? grid : 1), dim3(threads), lds, nbl, b_lo, b_hi, nseg, c.cs_off, c.cs_recs, c.min_freq, d_queue,
+        LAUNCH(c, "k_count_fp", kern, dim3(grid ? grid : 1), dim3(threads), lds, nb_arg, b_lo, b_hi, nseg, c.cs_off, c.cs_recs, c.min_freq, d_queue,
                c.d_shi, c.d_slo, c.d_scc, c.solid_cap, d_cnt + 4, d_cnt + 8, c.d_chunk_start, c.d_chunk_cnt, c.cs_chunk_cap, c.cs_defer, nbl, fill_limit, solid_limit,
                c.fused_prune ? c.d_sctx : (uint8_t*)nullptr, c.fused_prune ? c.d_unres : (uint8_t*)nullptr, c.fused_prune ? (uint32_t*)c.d_nbr : (uint32_t*)nullptr);
         W2_HIP(hipGetLastError());
@@ -2447,7 +2647,7 @@ int count_buckets_launch_slice(Ctx& c, unsigned k) {
             // (its buckets are the heavy ones: several tiles, hash classes -- 50-80 us each)
             const unsigned lgrid = (unsigned)std::min<uint64_t>(nbl, (uint64_t)c.sm_count);
             constexpr unsigned list_lds = K3Cfg<COUNT_CAP, COUNT_THREADS>::LDS;
-            LAUNCH(c, "k_count_buckets", list_kern, dim3(lgrid ? lgrid : 1), dim3(COUNT_THREADS), list_lds, nbl, 0u, nbl, nseg, c.cs_off,
+            LAUNCH(c, "k_count_buckets", list_kern, dim3(lgrid ? lgrid : 1), dim3(COUNT_THREADS), list_lds, nb_arg, 0u, nbl, nseg, c.cs_off,
                    c.cs_recs, c.min_freq, c.cs_defer + 1, c.d_shi, c.d_slo, c.d_scc, c.solid_cap, d_cnt + 4, d_cnt + 8, c.d_chunk_start, c.d_chunk_cnt, c.cs_chunk_cap,
                    (const uint32_t*)c.cs_defer, nbl);
             W2_HIP(hipGetLastError());
@@ -2841,10 +3041,26 @@ int phase_count(Ctx& c, uint32_t min_qual, uint32_t min_freq) {
         unsigned nseg = 1;
         c.pass = p;
         double a = now();
-        W2_TRY(count_partition_batched(c, NB, bv ? (unsigned)atoi(bv) : 4, &nseg, lo, hi));
+        // (one GPU, one pass, the lane kernel, room for the slabs: the cutter stores the records itself; W2RAP_K1_SLABS=0: the scatter pass)
+        uint32_t slabs = slab_route(c, NB, P);
+        uint64_t ask_from = 1ull << 20;                  // (W2RAP_TEST_SLAB_SAMPLE_MIN: a test hook, so that a small input is asked too)
+        if (const char* t = getenv("W2RAP_TEST_SLAB_SAMPLE_MIN")) { if (test_hook("W2RAP_TEST_SLAB_SAMPLE_MIN")) ask_from = (uint64_t)std::max(64ll, atoll(t)); }
+        if (slabs && c.n >= ask_from) {                  // (an input whose buckets pass their slabs by much is faster on the scatter pass)
+            uint64_t est = 0;
+            W2_TRY(slab_excess_estimate(c, NB, slabs, &est));
+            if (trace) fprintf(stderr, "[w2rap] partition: ~%llu records beyond slabs of %u (limit %llu)\n", (unsigned long long)est, slabs, (unsigned long long)(c.n / SLAB_EXCESS_DIV));
+            if (est > c.n / SLAB_EXCESS_DIV) slabs = 0;
+        }
+        if (slabs) {
+            bool refused = false;
+            W2_TRY(count_partition_slabs(c, NB, slabs, &refused));
+            if (refused) slabs = 0; else nseg = 2;
+        }
+        if (!slabs) W2_TRY(count_partition_batched(c, NB, bv ? (unsigned)atoi(bv) : 4, &nseg, lo, hi));
         double b = now();
         W2_TRY(count_buckets(c, min_freq, hi - lo, nseg, c.d_recs, c.d_bcount, c.M, P == 1));
         c.release(c.d_recs); c.d_recs = nullptr;         // the records are no longer needed
+        c.slab_cap = 0;
         t_part += b - a; t_cnt += now() - b;
     }
     c.pass = 0; c.npass = 1;
