@@ -25,6 +25,9 @@ runs), step3_fragdist_K200 (FragDist's bounds), step3_joined_K<K2>_extend (--ext
 step3_counts_<U>_<N2>_K100 (launch sizes).  ref_step3 runs every loop of the reference on one thread, so the cases of tests/step3_cases.py
 are reproduced byte for byte; the step3_<fixture>_* records were made when the reference's own worklists still took every processor, which
 numbers the large-K edges differently from run to run: they stay as recorded (the tests replay whatever order a record has).
+For Step 7 (`make_golden.py refruns tests/test_step7_model.py`): step7_s6_<fixture> and step7_s7_<case> (the reference's main) and
+step7_fn_<case> (oracle/_ref/ref_step7 lines and gaps on every case of tests/step7_cases.py, at 1 thread and at 4: t.lines.txt, t.gaps.txt,
+t.verbose.txt).
 All of these are data (inputs and expected outputs); no reference source is stored.
 """
 import os
@@ -137,7 +140,7 @@ def gfa_goldens():
 
 # the tests whose reference runs are replayed from refruns/<case>/ (conftest.reference_outputs)
 REFRUN_TESTS = ("tests/test_step3_consumer.py", "tests/test_step3_oracle.py", "tests/test_gfa_oracle.py", "tests/test_step1_oracle.py",
-                "tests/test_step5_reference.py", "tests/test_step4_model.py", "tests/test_gfa_cases.py", "tests/test_step5_add_model.py")
+                "tests/test_step5_reference.py", "tests/test_step4_model.py", "tests/test_gfa_cases.py", "tests/test_step5_add_model.py", "tests/test_step7_model.py")
 
 
 def refruns(tests=()):

@@ -14,6 +14,9 @@ Recorded runs.
                        150 bases no read covers, 2,482 pairs of error-free 150-base reads from 700-base fragments, taken through the
                        reference's own Steps 2-6 (its contig files are tests/golden/step7_planted.*); the others are hand-made cases
                        of this file, built with real sequences.
+  step7_fn_<case>      the reference's own GetTol, GetLineLengths, GetLineNpairs and MakeGaps (without its cleanup, verbose) called on
+                       EVERY hand-made and generated case as it stands (oracle/ref_step7_driver.cc): t.lines.txt, t.gaps.txt and
+                       t.verbose.txt -- see lines_run, gaps_run, check_lines_record and check_gaps_record.
 Every run is recorded at 1 thread and at 4; the two had to agree, the 1-thread files are kept."""
 import os
 import re
@@ -292,7 +295,107 @@ def _hand_cases():
     line = [[[a1]], [[b1], [b2]], [[m]]]
     out["overlinked"] = g.case(lines=[line, mirror_line(line)], npairs=[10, 10, 10, 10, 20, 20], expect=dict(n_reason=[4, 0, 0, 0, 0, 0, 0], n_not_one_to_one=0, n_advanced=2, n_unique=4, n_sym_added=0,
                                                                                        n_sym_deleted=0, n_overlinked=4, gaps=[]))
+    _median_cases(out)
+    _in_edge_cases(out)
+    _list_cases(out)
     return out
+
+
+MEDIANS = {3: ((50, 50, 70), 50), 4: ((40, 60, 60, 81), 60), 5: ((90, 30, 30, 75, 30), 30), 6: ((10, 20, 30, 41, 50, 60), 35), 7: ((5, 5, 5, 5, 9, 9, 9), 5)}
+
+
+def _median_cases(out):
+    """A line a (0) -> a cell of n parallel paths -> c, n = 3 .. 7 with ties among the lengths (Lines.h:84-96: one path its length, two
+    their mean, more the median of the sorted lengths, for an even n the mean of the two middle ones, in int), and a cell of one path of
+    two edges beside two of one.  B is as long as the line: 3 pairs from c to B and 2 whose first read walks a, the first path and c: every
+    pair names all four lines (npairs 5 each, equal coverage), (c, B) has 5 nears and is accepted, (a, B) and (p, B) have 2.
+    (Edges of 5 K-mers hold no two (K-1)-mers: these graphs are built without sequences in either mode.)"""
+    def finish(name, g, a, first, c, line, med):
+        b = g.contig(2 * LONG + med)
+        g.link(c, b, 3); g.pair([a] + first + [c], [b ^ 1], 2)
+        R = {(c, b): "accepted", (b + 1, c + 1): "accepted"}
+        for e in [a] + first:
+            R[(e, b)] = "count"; R[(b + 1, e + 1)] = "count"
+        out[name] = g.case(lines=[line, mirror_line(line)], expect=dict(llens=[2 * LONG + med] * 4, npairs=[5] * 4, tol=[2, 3] * (b // 2) + [0, 1], reasons=R, gaps=[(c, b), (b + 1, c + 1)],
+                                                                        gap_inv=[1, 0], near_max1_at={c: 5, a: 2, b + 1: 5}, near_max2_at={b: 5, c + 1: 5, a + 1: 2}))
+    for n, (lens, med) in MEDIANS.items():
+        g = Contigs(40 + n, real=False); v = [g.v() for _ in range(4)]
+        a = g.e(v[0], v[1], LONG); ps = [g.e(v[1], v[2], k) for k in lens]; c = g.e(v[2], v[3], LONG)
+        finish(f"median_{n}", g, a, [ps[0]], c, [[[a]], [[p] for p in ps], [[c]]], med)
+    # x (100) and y (110) in a row beside z (200) and z2 (300): 210 is the median
+    g = Contigs(50, real=False); v = [g.v() for _ in range(5)]
+    a = g.e(v[0], v[1], LONG); x = g.e(v[1], v[2], 100); y = g.e(v[2], v[3], 110); z = g.e(v[1], v[3], 200); z2 = g.e(v[1], v[3], 300); c = g.e(v[3], v[4], LONG)
+    finish("median_two_edge_path", g, a, [x, y], c, [[[a]], [[z2], [x, y], [z]], [[c]]], 210)
+
+
+def _in_edge_cases(out):
+    """The search through in-edges (MakeGaps.cc:244-252: a node's children are the out-edges of its right vertex AND the in-edges of its
+    left vertex).  e1 (0): s -> t, 6000 K-mers; 3 pairs from e1 to e2, every edge a line of its own, npairs 10 everywhere.  A vertex whose
+    single in-edge would become a predecessor root (0 K-mers, which would take the limit away) has a second one, `o`."""
+    def scene(seed):
+        g = Contigs(seed); s, t = g.v(), g.v()
+        return g, s, t, g.e(s, t, LONG)
+    two = lambda e1, e2: dict(n_near_kinds=2, n_pred_start=0, n_close=[0, 0, 0, 0], n_links=2, reasons={(e1, e2): "accepted", (e2 + 1, e1 + 1): "accepted"}, n_sym_added=0,
+                              gaps=[(e1, e2), (e2 + 1, e1 + 1)], gap_inv=[1, 0])
+    # e2 and o enter s: e2 is met at step 1 as an in-edge of e1's left vertex, which has no predecessor root.  The mirror near (e2', e1'):
+    # e1' is the one edge into the left vertex of e2', the predecessor root itself (step 0)
+    g, s, t, e1 = scene(60); e2 = g.e(g.v(), s, LONG); g.e(g.v(), s, LONG); g.link(e1, e2, 3)
+    out["in_step_1"] = g.case(npairs=10, expect=dict(n_near_kinds=2, n_pred_start=1, n_close=[1, 1, 0, 0], n_links=0, gaps=[]))
+    # n (100): t -> x, e2: y -> t.  From e1 out to n, then in: the in-edges of n's left vertex t are e1 and e2 (step 2).  The mirror near:
+    # the left vertex t' of e2' has the one in-edge n', the predecessor root, whose out-edges are e2' and e1' (step 1)
+    g, s, t, e1 = scene(61); n = g.e(t, g.v(), 100); e2 = g.e(g.v(), t, LONG); g.link(e1, e2, 3)
+    out["out_in_step_2"] = g.case(npairs=10, expect=dict(n_near_kinds=2, n_pred_start=1, n_close=[0, 1, 1, 0], n_links=0, gaps=[]))
+    for kn in (1500, 1501):
+        # in, in: n (kn): x -> s, o -> s, e2: y -> x, z: x -> w.  n is expanded at 1500 K-mers (e2 at step 2) and not at 1501.  The mirror
+        # near walks the same edges: n' is one of the two in-edges of the left vertex x' of e2', e1' the in-edge of the left vertex of n'
+        g, s, t, e1 = scene(62); x = g.v(); n = g.e(x, s, kn); g.e(g.v(), s, LONG); e2 = g.e(g.v(), x, LONG); g.e(x, g.v(), LONG); g.link(e1, e2, 3)
+        out[f"in_in_{kn}"] = g.case(npairs=10, expect=dict(n_near_kinds=2, n_pred_start=0, n_close=[0, 0, 2, 0], n_links=0, gaps=[]) if kn == 1500 else two(e1, e2))
+        # in, in, in: a (700): x -> s, o -> s, b (kn - 700): y -> x, e2: q -> y, z: y -> w.  b, at depth 1, is expanded with 1500 K-mers
+        # behind it and not with 1501; e2 enters the LEFT vertex of b
+        g, s, t, e1 = scene(63); x, y = g.v(), g.v(); a = g.e(x, s, 700); g.e(g.v(), s, LONG); b = g.e(y, x, kn - 700); e2 = g.e(g.v(), y, LONG); g.e(y, g.v(), LONG); g.link(e1, e2, 3)
+        out[f"in_in_in_{kn}"] = g.case(npairs=10, expect=dict(n_near_kinds=2, n_pred_start=0, n_close=[0, 0, 0, 2], n_links=0, gaps=[]) if kn == 1500 else two(e1, e2))
+    # out, out, in: a (100): t -> u, c and c2 (100) out of u, e2: q -> u.  e2 is no child of a (it ENTERS a's right vertex); it enters the
+    # left vertex of c (step 3).  The mirror near: in (c'), out (a'), out (e1'): step 3 by the other clause
+    g, s, t, e1 = scene(64); u = g.v(); a = g.e(t, u, 100); c = g.e(u, g.v(), 100); c2 = g.e(u, g.v(), 100); e2 = g.e(g.v(), u, LONG); g.link(e1, e2, 3)
+    out["out_out_in_step_3"] = g.case(npairs=10, expect=dict(n_near_kinds=2, n_pred_start=0, n_close=[0, 0, 0, 2], n_links=0, gaps=[]))
+    # a first level of 140: 70 out-edges of t and 70 in-edges of s (x_i -> s), 100 K-mers each, all in one line (over the 500 K-mers
+    # below which reads are ignored).  Behind the in-edges (children 70 .. 139 of the root): e2 -> x_64 and e3 -> x_1 (step 2), e4 -> m
+    # (100) -> x_69 (step 3); behind the out-edge 66: e5 (step 2); the in-edge 67 itself (step 1).  The mirror nears: the left vertex of
+    # e2', e3' and of the mirror of the in-edge 67 has one in-edge, the predecessor root -- for the last it IS e1' (step 0), for e2' and
+    # e3' e1' is a child of it (step 1) --; m' is the predecessor root of e4' (step 2); e5' has none (out, out: step 2)
+    g, s, t, e1 = scene(65)
+    zs = [g.v() for _ in range(70)]; outs = [g.e(t, z, 100) for z in zs]
+    xs = [g.v() for _ in range(70)]; ins = [g.e(x, s, 100) for x in xs]
+    e2 = g.e(g.v(), xs[64], LONG); e3 = g.e(g.v(), xs[1], LONG); y = g.v(); m = g.e(y, xs[69], 100); e4 = g.e(g.v(), y, LONG); e5 = g.e(zs[66], g.v(), LONG)
+    for e in (e2, e3, e4, e5, ins[67]):
+        g.link(e1, e, 3)
+    short = outs + ins + [m]
+    out["hub_in_70"] = g.case(lines=[[[short]], [[[e + 1 for e in short]]]], npairs=10, min_line=50,
+                              expect=dict(n_near_kinds=10, n_pred_start=4, n_close=[1, 3, 5, 1], n_links=0, gaps=[], n_nears=30))
+
+
+def _list_cases(out):
+    """y of exactly NEAR_LIST = 16 kept edges and of 17 (the list of k7_nears, and the walk beyond it), each near 3 times; 1, 3, 4 and 5
+    distinct nears (a block of k7_close takes 4)."""
+    for n in (16, 17):
+        # A (0, 600 K-mers, as long as the others: equal coverage) and a chain of n edges of 600: 3 pairs from A whose second read walks
+        # the whole chain.  Pass 1: x = [A], y = the chain; pass 2: x = the mirror chain, y = [A'].  2 n links of count 3, all accepted --
+        # A on the left of n of them, A' on the right of the others: none is one-to-one
+        g = Contigs(66 + n); a = g.contig(600); ch = g.chain([600] * n)
+        g.pair([a], [e ^ 1 for e in reversed(ch)], 3)
+        out[f"y_{n}"] = g.case(npairs=10, min_line=500, expect=dict(n_pass_placed=6, n_pass_y_long=3 * (n > 16), n_pass_none=0, n_nears=6 * n, n_near_kinds=2 * n, n_close=[0, 0, 0, 0], n_links=2 * n,
+                                                                     n_reason=[2 * n, 0, 0, 0, 0, 0, 0], n_not_one_to_one=2 * n, gaps=[], near_max1_at={a: 3, ch[0] + 1: 3}, near_max2_at={a + 1: 3, ch[n - 1]: 3}))
+    # two-sided: 3 pairs from a contig to another, the near and its mirror image.  one-sided: A -> three edges of 100 K-mers -> B, 3 pairs
+    # whose first read walks all five and whose second lies on B'.  Pass 1: the short lines are ignored, x = [A, B], y = [B]: (A, B), and B
+    # is in y; pass 2: x = [B'] is in y = [B', A']: no mirror near.  B is 4 steps from A: a link, accepted, its mirror added for symmetry
+    for kinds, (double, single) in {1: (0, 1), 3: (1, 1), 4: (2, 0), 5: (2, 1)}.items():
+        g = Contigs(80 + kinds); gaps = []
+        for _ in range(double):
+            a, b = g.contig(), g.contig(); g.link(a, b, 3); gaps += [(a, b), (b + 1, a + 1)]
+        for _ in range(single):
+            ch = g.chain([LONG, 100, 100, 100, LONG]); g.pair(ch, [ch[4] ^ 1], 3); gaps += [(ch[0], ch[4]), (ch[4] + 1, ch[0] + 1)]
+        out[f"kinds_{kinds}"] = g.case(npairs=10, expect=dict(n_near_kinds=kinds, n_pred_start=0, n_close=[0, 0, 0, 0], n_links=kinds, n_reason=[kinds, 0, 0, 0, 0, 0, 0], n_not_one_to_one=0,
+                                                              n_pass_none=3 * single, n_sym_added=single, n_sym_deleted=0, gaps=sorted(gaps)))
 
 
 def check_expect(case, got):
@@ -479,6 +582,158 @@ def step7_run(name, case, workdir):
     m = re.findall(r"deleting (-?\d+) gaps and adding (-?\d+) gaps", out)
     assert len(m) == 1
     return open(w("t_assembly_raw.gfa")).read(), (int(m[0][0]), int(m[0][1]))
+
+
+# ---------------------------------------------------------------------------------------------------------------- recorded calls
+# step7_fn_<case>: the reference's public functions called on a case as it stands (oracle/ref_step7_driver.cc -> oracle/_ref/ref_step7):
+# no sequences, the case's own involution as text.  `lines`: GetTol, GetLineLengths, GetLineNpairs -> t.lines.txt.  `gaps`: MakeGaps
+# without its cleanup -> t.gaps.txt (every gap edge it appended, `e1 e2 mirror_index`, read from the edited graph) and its stdout,
+# t.verbose.txt.  Of stdout the dated prefix of a line and the time after `done making gaps` are dropped: no clock enters a fixture.
+REF_STEP7 = os.path.join(ROOT, "oracle", "_ref", "ref_step7")
+FN_INPUTS = ["t.contig.hbv", "t.contig.paths", "t.fin.lines", "t.inv"]
+FN_OUTPUTS = ["t.lines.txt", "t.gaps.txt", "t.verbose.txt"]
+FN_QUIET = ("many_links",)                    # recorded with verbose = 0: 5,998 accepted links are 790 KB of text
+BOUNDARY_PAIRS = (("count_2", "count_3"), ("line_4999", "line_5000"), ("alt_equal", "alt_count_plus_1"), ("hang_800", "hang_801"), ("steps_3", "steps_4"), ("inter_1500", "inter_1501"),
+                  ("inter2_1500", "inter2_1501"), ("bubbles_3", "bubbles_4"), ("in_in_1500", "in_in_1501"), ("in_in_in_1500", "in_in_in_1501"))
+_DATED = re.compile(r"^\S+ \S+ +\d+ \d\d:\d\d:\d\d \d{4}: ")
+
+
+def _undated(text):
+    return "".join(re.sub(r"(done making gaps), time used = .*", r"\1", _DATED.sub("", line)) + "\n" for line in text.splitlines())
+
+
+def _ints(line):
+    return [int(x) for x in line.split()]
+
+
+def _fn_twice(workdir, case, verbose):
+    """ref_step7 lines and ref_step7 gaps at 1 thread and at 4 on copies of workdir; the outputs must agree; the 1-thread files are put
+    into workdir.  Where the case gives no npairs, MakeGaps reads what GetLineNpairs of the same run counted"""
+    res = []
+    for t in (1, 4):
+        d = os.path.join(workdir, f"threads{t}")
+        shutil.copytree(workdir, d, ignore=shutil.ignore_patterns("threads*"))
+        env = dict(os.environ, OMP_NUM_THREADS=str(t))
+        subprocess.run([REF_STEP7, "lines", d, str(t)], check=True, capture_output=True, env=env)
+        if case["npairs"] is None:
+            F.write_int_vec(os.path.join(d, "t.fin.lines.npairs"), _ints(open(os.path.join(d, "t.lines.txt")).read().split("\n")[2]))
+        out = subprocess.run([REF_STEP7, "gaps", d, str(t), str(case["min_line"]), str(case["min_link_count"]), str(int(verbose))], check=True, capture_output=True, text=True, env=env).stdout
+        with open(os.path.join(d, "t.verbose.txt"), "w") as fh:
+            fh.write(_undated(out))
+        res.append((d, [open(os.path.join(d, f), "rb").read() for f in FN_OUTPUTS]))
+    assert res[0][1] == res[1][1], "the reference's outputs differ between 1 thread and 4"
+    for f in FN_OUTPUTS:
+        shutil.copy(os.path.join(res[0][0], f), os.path.join(workdir, f))
+    for d, _ in res:
+        shutil.rmtree(d)
+
+
+def _fn_run(name, case, workdir):
+    """stages the case in workdir (regenerated here; held to the record by SHA-256) and puts the recorded outputs beside it"""
+    w = lambda f: os.path.join(workdir, f)
+    F.write_hbv(w("t.contig.hbv"), case["hbv"]); F.write_paths(w("t.contig.paths"), *case["paths"]); F.write_lines(w("t.fin.lines"), case["lines"])
+    with open(w("t.inv"), "w") as fh:
+        fh.write("".join(f"{int(x)}\n" for x in case["inv"]))
+    inputs = list(FN_INPUTS)
+    if case["npairs"] is not None:
+        F.write_int_vec(w("t.fin.lines.npairs"), case["npairs"])
+        inputs.append("t.fin.lines.npairs")
+    reference_outputs(f"step7_fn_{name}", workdir, inputs, FN_OUTPUTS, lambda: _fn_twice(workdir, case, name not in FN_QUIET))
+    if case["npairs"] is None:                # as Step 6 would have written it: the recorded GetLineNpairs of this case
+        F.write_int_vec(w("t.fin.lines.npairs"), _ints(open(w("t.lines.txt")).read().split("\n")[2]))
+
+
+def lines_run(name, case, workdir):
+    """-> dict(tol, llens, npairs) of the recorded GetTol, GetLineLengths and GetLineNpairs on the case"""
+    _fn_run(name, case, workdir)
+    rows = open(os.path.join(workdir, "t.lines.txt")).read().split("\n")
+    assert len(rows) == 4 and rows[3] == ""
+    return dict(tol=_ints(rows[0]), llens=_ints(rows[1]), npairs=_ints(rows[2]))
+
+
+def _run_list(text):
+    """`22^3,4,7^2` -> [(22, 3), (4, 1), (7, 2)]"""
+    return [(int(x.split("^")[0]), int(x.split("^")[1]) if "^" in x else 1) for x in text.split(",") if x]
+
+
+def parse_verbose(text):
+    """MakeGaps' stdout -> dict(accepted: one dict per numbered entry -- e1, e2, count, lines ((tol, len) of either end), lefts and rights
+    (the runs of nears1[e1] and nears2[e2]), left_group, right_group --, deleting: the links the one-to-one rule removed, symmetry:
+    (deleted, added)).  Every line must be one the reference's text can have written."""
+    acc, deleting, sym = [], [], []
+    for line in text.splitlines():
+        m = re.fullmatch(r"(\d+)\. \[(\d+)\] (\d+) --> (\d+)", line)
+        if m:
+            assert int(m[1]) == len(acc) + 1
+            acc.append(dict(count=int(m[2]), e1=int(m[3]), e2=int(m[4])))
+            continue
+        m = re.fullmatch(r"lines: (\d+)\[len=(\d+)\], (\d+)\[len=(\d+)\]", line)
+        if m:
+            acc[-1]["lines"] = ((int(m[1]), int(m[2])), (int(m[3]), int(m[4])))
+            continue
+        m = re.fullmatch(r"(lefts|rights): ([\d^,]*)", line)
+        if m:
+            acc[-1][m[1]] = _run_list(m[2])
+            continue
+        m = re.fullmatch(r"(left|right) edge group: ([\d,]*)", line)
+        if m:
+            acc[-1][m[1] + "_group"] = [int(x) for x in m[2].split(",") if x]
+            continue
+        m = re.fullmatch(r"deleting (\d+) --> (\d+)", line)
+        if m:
+            deleting.append((int(m[1]), int(m[2])))
+            continue
+        m = re.fullmatch(r"deleting (-?\d+) gaps and adding (-?\d+) gaps to force symmetry", line)
+        if m:
+            sym.append((int(m[1]), int(m[2])))
+            continue
+        assert line in ("", "done making gaps"), line
+    assert len(sym) == 1 and all(len(a) == 8 for a in acc)
+    return dict(accepted=acc, deleting=deleting, symmetry=sym[0])
+
+
+def gaps_run(name, case, workdir):
+    """-> dict(gap_from, gap_to, gap_inv: the gap edges MakeGaps appended, in its order; symmetry; accepted and deleting, None for a case
+    recorded without verbose) of the recorded MakeGaps on the case"""
+    _fn_run(name, case, workdir)
+    rows = [_ints(r) for r in open(os.path.join(workdir, "t.gaps.txt")).read().splitlines()]
+    assert all(len(r) == 3 for r in rows)
+    v = parse_verbose(open(os.path.join(workdir, "t.verbose.txt")).read())
+    quiet = name in FN_QUIET
+    assert not (quiet and (v["accepted"] or v["deleting"]))
+    return dict(gap_from=[r[0] for r in rows], gap_to=[r[1] for r in rows], gap_inv=[r[2] for r in rows], symmetry=v["symmetry"], accepted=None if quiet else v["accepted"],
+                deleting=None if quiet else v["deleting"])
+
+
+def check_lines_record(rec, got):
+    """tol, llens and -- where part LINES ran -- npairs of a result (see check_expect) are the recorded ones"""
+    for k in ("tol", "llens") + (("npairs",) if got.get("npairs") is not None else ()):
+        assert [int(x) for x in got[k]] == rec[k], k
+
+
+def check_gaps_record(rec, got):
+    """a result of part LINKS held to the recorded MakeGaps: the gaps with their own ids, in order; the accepted links as a multiset
+    (ParallelSortSync leaves equal links in no stated order); per accepted link the longest runs of its nears, its edge groups and its
+    lines; the count of the one-to-one rule; the symmetry counts"""
+    from collections import Counter
+    from w2rap_contigger_amd.step7 import REASONS
+    for k in ("gap_from", "gap_to", "gap_inv"):
+        assert [int(x) for x in got[k]] == rec[k], (k, list(got[k]), rec[k])
+    assert (got["counters"]["n_sym_deleted"], got["counters"]["n_sym_added"]) == rec["symmetry"]
+    if rec["accepted"] is None:
+        return
+    mine = Counter((int(f), int(t), int(n)) for f, t, n, r in zip(got["link_from"], got["link_to"], got["link_count"], got["link_reason"]) if REASONS[int(r)] == "accepted")
+    assert mine == Counter((a["e1"], a["e2"], a["count"]) for a in rec["accepted"])
+    tom, tol, llens = [int(x) for x in got["tom"]], [int(x) for x in got["tol"]], [int(x) for x in got["llens"]]
+    groups = {}
+    for e, t in enumerate(tom):
+        groups.setdefault(t, []).append(e)
+    for a in rec["accepted"]:
+        e1, e2 = a["e1"], a["e2"]
+        assert max(n for _, n in a["lefts"]) == int(got["near_max1"][e1]) and max(n for _, n in a["rights"]) == int(got["near_max2"][e2]), (e1, e2)
+        assert a["left_group"] == groups.get(e1, []) and a["right_group"] == groups.get(e2, []), (e1, e2)
+        assert a["lines"] == ((tol[e1], llens[tol[e1]]), (tol[e2], llens[tol[e2]])), (e1, e2)
+    assert got["counters"]["n_not_one_to_one"] == len(rec["deleting"])
 
 
 _COMP = str.maketrans("ACGT", "TGCA")

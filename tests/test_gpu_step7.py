@@ -1,7 +1,10 @@
-"""w2rap_step7_links on the GPU held to the recorded runs of the reference's main, to the literal outcomes of the hand-made cases and to
-the CPU model (tests/step7_model.py), array for array, counters included -- at the shapes where a kernel can go wrong: 1, 63, 64, 65 and
+"""w2rap_step7_links on the GPU held to the recorded runs of the reference's main, to the recorded calls of the reference's own GetTol,
+GetLineLengths, GetLineNpairs and MakeGaps on every case (replayed from tests/golden/refruns/step7_fn_*), to the literal outcomes of the
+hand-made cases and to the CPU model (tests/step7_model.py), array for array, counters included -- at the shapes where a kernel can go wrong: 1, 63, 64, 65 and
 257 pairs; runs of 1, 63, 64, 65, 256, 257 and 1025 equal nears; paths of 0, 1, 9, 17 and 40 edges (both sides of the per-thread lists);
-an edge and its inverse in one line and in two; a hub of 300 edges in the search; more distinct links than a scan tile holds."""
+an edge and its inverse in one line and in two; a hub of 300 edges in the search; more distinct links than a scan tile holds; medians of
+3 to 7 parallel paths; the search through in-edges (steps 1 to 3, the 1500 K-mer limit, a first level of 140 with the out/in boundary
+behind lane 63); y of 16 and 17 kept edges; 1, 3, 4 and 5 candidates of the search."""
 import numpy as np
 import pytest
 
@@ -43,18 +46,29 @@ def parts_of(case):
     return ("lines", "links") if case["npairs"] is None else ("links",)
 
 
+def held_to_the_records(name, case, res, tmp_path):
+    """the recorded calls of the reference's own GetTol, GetLineLengths, GetLineNpairs and MakeGaps on this case (refruns/step7_fn_<name>/,
+    replayed): tol, llens, npairs where part LINES ran; the gaps with their ids and mirror indices, in order; the accepted links, their
+    nears' longest runs, edge groups and lines; the one-to-one and the symmetry counts"""
+    got = C.as_dict(res)
+    C.check_lines_record(C.lines_run(name, case, str(tmp_path)), got)
+    C.check_gaps_record(C.gaps_run(name, case, str(tmp_path)), got)
+
+
 @pytest.mark.parametrize("name", sorted(HAND))
-def test_hand_made_cases(name):
+def test_hand_made_cases(name, tmp_path):
     case = HAND[name]
     res = library(case, parts_of(case))
     C.check_expect(case, C.as_dict(res))
+    held_to_the_records(name, case, res, tmp_path)
     same(res, model(name, case, parts_of(case)))
 
 
 @pytest.mark.parametrize("name", sorted(GENERATED))
-def test_generated_cases(name):
+def test_generated_cases(name, tmp_path):
     case = GENERATED[name]
     res = library(case, parts_of(case))
+    held_to_the_records(name, case, res, tmp_path)
     same(res, model(name, case, parts_of(case)))
     assert all(v >= 0 for v in res.ms.values())
 
@@ -65,6 +79,15 @@ def test_lines_alone(name):
     res = step7.line_stats(case["hbv"], case["inv"], case["paths"], case["lines"])
     same(res, model(name, case, ("lines",)))
     assert res.ms["ms_nears"] == 0 and res.ms["ms_search"] == 0 and res.ms["ms_filter"] == 0
+
+
+@pytest.mark.parametrize("name", sorted({**HAND, **GENERATED}))
+def test_lines_are_the_recorded_ones(name, tmp_path):
+    """part LINES alone on every case, whether it gives npairs or not: the recorded tol, llens and npairs, value for value"""
+    case = {**HAND, **GENERATED}[name]
+    res = step7.line_stats(case["hbv"], case["inv"], case["paths"], case["lines"])
+    assert res.npairs is not None
+    C.check_lines_record(C.lines_run(name, case, str(tmp_path)), C.as_dict(res))
 
 
 def test_links_read_the_given_npairs_not_their_own():

@@ -1,5 +1,6 @@
 """The CPU model of Step 7's read-sized passes (tests/step7_model.py) held to the recorded runs of the reference's own main
-(tests/golden/refruns/step7_*) and to the literal outcomes of the hand-made cases (tests/step7_cases.py); the file formats of the
+(tests/golden/refruns/step7_s6_*, step7_s7_*), to the recorded calls of its own GetTol, GetLineLengths, GetLineNpairs and MakeGaps on every
+hand-made and generated case (refruns/step7_fn_*) and to the literal outcomes of the hand-made cases (tests/step7_cases.py); the file formats of the
 lines and of npairs held to the reference's files; and the things that do not exist without the feature."""
 import ctypes
 
@@ -98,6 +99,55 @@ def test_the_records_hold_an_accepted_gap_and_a_filtered_link(tmp_path):
         seen |= {"gap"} if ref_gaps else set()
         seen |= {"filtered"} if any(r != M.R_ACCEPTED for r in got["link_reason"]) else set()
     assert seen == {"gap", "filtered"}
+
+
+# ---- the model against the recorded calls of the reference's own functions (refruns/step7_fn_<case>/): every case of step7_cases.py
+GENERATED = C.generated_cases()
+ALL = {**HAND, **GENERATED}
+
+
+@pytest.mark.parametrize("name", sorted(ALL))
+def test_model_gives_the_reference_tol_llens_npairs(name, tmp_path):
+    """GetTol, GetLineLengths and GetLineNpairs, value for value (part LINES for every case, whether it gives npairs or not)"""
+    case = ALL[name]
+    rec = C.lines_run(name, case, str(tmp_path))
+    got = model(case, parts=("lines",))
+    assert got["npairs"] is not None
+    C.check_lines_record(rec, got)
+    if "npairs" in case["expect"]:            # (the literal is the recorded value too)
+        assert case["expect"]["npairs"] == rec["npairs"]
+
+
+@pytest.mark.parametrize("name", sorted(ALL))
+def test_model_makes_the_reference_gaps(name, tmp_path):
+    """MakeGaps: its gap edges with their own ids, in its order, and what its verbose text states about every accepted link"""
+    case = ALL[name]
+    rec = C.gaps_run(name, case, str(tmp_path))
+    got = model(case, shortcut_last=name == "hub_300")
+    C.check_lines_record(C.lines_run(name, case, str(tmp_path)), got)
+    C.check_gaps_record(rec, got)
+    assert F.read_int_vec(tmp_path / "t.fin.lines.npairs").tolist() == (case["npairs"].tolist() if case["npairs"] is not None else got["npairs"])
+
+
+@pytest.mark.parametrize("a,b", C.BOUNDARY_PAIRS)
+def test_the_records_show_the_verdict_of_a_boundary_pair(a, b, tmp_path):
+    """on the records alone: the two sides of a limit differ in the gaps the reference made -- one side has none, the other two.  (A case
+    that drifted into `rejected for another reason` on both sides fails here)"""
+    gaps = []
+    for name in (a, b):
+        d = tmp_path / name
+        d.mkdir()
+        C.gaps_run(name, HAND[name], str(d))
+        gaps.append(open(d / "t.gaps.txt").read())
+    assert gaps[0] != gaps[1] and sorted(len(g.splitlines()) for g in gaps) == [0, 2], gaps
+
+
+def test_the_records_reach_what_the_new_cases_are_for():
+    """the medians are the literal ones; the in-edge searches are close or not as derived; y of 16 and 17; 1, 3, 4 and 5 candidates"""
+    for n, (lens, med) in C.MEDIANS.items():
+        assert M.line_lengths(M.Graph(HAND[f"median_{n}"]["hbv"]), HAND[f"median_{n}"]["nested"])[-1] == 2 * C.LONG + med and len(lens) == n
+    assert [model(HAND[f"kinds_{k}"])["counters"]["n_near_kinds"] for k in (1, 3, 4, 5)] == [1, 3, 4, 5]
+    assert [model(HAND[f"y_{n}"])["counters"]["n_pass_y_long"] for n in (16, 17)] == [0, 3]
 
 
 # ---- the model against the literal outcomes
