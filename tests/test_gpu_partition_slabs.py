@@ -97,6 +97,18 @@ def _case_rank16():
     return _pack(reads, rng=rng)
 
 
+HEAVY_COPIES = 20000
+
+
+def _case_heavy_behind_the_sample():
+    """9600 reads over a genome of 192 000 bases (7.5x: the first 1/32 of the reads puts ~7 records into a bucket, few beyond C / 32 = 16),
+    and behind them one read 20 000 times.  Not shuffled: the guard's sample sees the background only."""
+    rng = np.random.default_rng(507)
+    _, reads = _background(rng, glen=192000, n=9600)
+    reads += [rng.integers(0, 4, 150, dtype=np.uint8)] * HEAVY_COPIES
+    return _pack(reads)
+
+
 def _case_slots():
     """reads that cut into more than eight records: of 6000 random reads those with the most minimizer runs, six times each"""
     rng = np.random.default_rng(504)
@@ -160,7 +172,7 @@ def _case_long():
 
 LAUNCH_N = (2, 62, 64, 66, 254, 256, 258)
 _CASES = {"uniform": _case_uniform, "heavy": _case_heavy, "rank16": _case_rank16, "slots": _case_slots, "read_edges": _case_read_edges,
-          "long": _case_long, **{f"n{n}": (lambda n=n: _case_n(n)) for n in LAUNCH_N}}
+          "long": _case_long, "heavy_behind_the_sample": _case_heavy_behind_the_sample, **{f"n{n}": (lambda n=n: _case_n(n)) for n in LAUNCH_N}}
 _cache = {}
 
 
@@ -296,6 +308,31 @@ def test_guard_sends_heavy_buckets_to_the_scatter_pass(mods, monkeypatch, capfd,
     assert m and int(m.group(2)) == n // 10 and int(m.group(1)) > 3 * int(m.group(2)), err
     sample = re.findall(r"K1 route: lane, npass \d+, spp \d+, (\d+) reads", err)
     assert [int(x) for x in sample] == [n // 32, n], err
+
+
+def test_sample_says_yes_but_the_list_overflows(mods, monkeypatch, capfd):
+    """an asked input (the hook: from 64 reads on) whose sample holds none of the heavy buckets: the estimate stays under the limit, the
+    cut to slabs needs a list of more than reads / 8 + 1024 entries, and such an input is not cut into slabs a second time -- nothing is
+    kept, the scatter pass takes all reads.  Three K1 lines: the sample's, the refused cut's, the scatter pass's."""
+    monkeypatch.setenv("W2RAP_TRACE", "1")
+    monkeypatch.setenv("W2RAP_TEST_SLAB_SAMPLE_MIN", "64")
+    c = _case(mods, "heavy_behind_the_sample")
+    n = len(c["off"]) - 1
+    assert HEAVY_COPIES - 512 > n // 8 + 1024                       # (a bucket holds a record of every copy: those beyond its slab alone pass the list)
+    F, step2, O = mods
+    pk, bo, ln = c["packed"]
+    routes = _check_stages(mods, c, capfd)
+    assert routes == [("lane", "scatter", 0), ("lane", "slabs", 512), ("lane", "scatter", 0)], routes
+    capfd.readouterr()
+    with step2.Step2Context(0) as ctx:
+        ctx.set_reads_host(pk, bo, ln, quals=c["quals"], qual_off=c["off"])
+        ctx.count_kmers(7, 4)
+    err = capfd.readouterr().err
+    m = re.search(r"partition: ~(\d+) records beyond slabs of 512 \(limit (\d+)\)", err)
+    assert m and int(m.group(2)) == n // 10 and int(m.group(1)) <= int(m.group(2)), err
+    cut = re.findall(r"K1 route: lane, npass \d+, spp \d+, (\d+) reads", err)
+    assert [int(x) for x in cut] == [n // 32, n, n], err
+    assert "partition slabs:" not in err, err                       # (the line of a slab layout that was kept)
 
 
 def test_fallback_two_passes(mods, monkeypatch, capfd):

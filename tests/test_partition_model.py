@@ -1,4 +1,4 @@
-"""CPU models of two pieces of index arithmetic in k_superkmers_lane (w2rap_contigger_amd/csrc/step2_count.hip): the sliding-window minimum
+"""CPU models of two pieces of index arithmetic in k_superkmers_lane (w2rap_contigger_amd/csrc/step2_partition.hip): the sliding-window minimum
 over WIN = 46 m-mer keys by blocks of 16 (van Herk / Gil-Werman: suffix minima of the three blocks before the current one, running prefix
 of the current one) and the cut of a read's k-mers into records (bucket change, or REC_MAXK k-mers).  The GPU parity tests compare the
 kernel with the oracle; these pin the scheme itself, step for step as the kernel walks it."""

@@ -347,6 +347,13 @@ __host__ __device__ inline uint32_t bucket_mix(uint32_t key) {
     return h ^ (h >> 13);
 }
 __device__ inline uint32_t bucket_of(uint32_t key, uint32_t nb) { return __umulhi(bucket_mix(key), nb); }
+// orders the LDS accesses of ONE wavefront (LDS executes a wave's operations in order; this only stops the compiler
+// from reordering them) -- unlike __syncthreads() it does not wait for outstanding global memory operations
+__device__ inline void wave_lds_fence() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
 // reverse complement of the 15 bases in the low 30 bits of x (LSB first), LSB first again
 __host__ __device__ inline uint32_t rc15(uint32_t x) {
     x = ~x;

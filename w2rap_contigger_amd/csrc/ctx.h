@@ -386,7 +386,13 @@ void host_parallel_for(size_t n, const std::function<void(size_t)>& f);
 int phase_count(Ctx& c, uint32_t min_qual, uint32_t min_freq);          // step2_count.hip
 int count_quality(Ctx& c, uint32_t min_qual);
 uint32_t default_buckets(uint64_t total_kmers, uint32_t multiple_of);
+// the partition (step2_partition.hip): c.d_recs, c.d_bcount, c.nrec from the reads and their quality windows
 int count_partition(Ctx& c, uint32_t nb, uint32_t n_parts, uint32_t pb_lo, uint32_t pb_hi);   // n_parts 0: single GPU; buckets [pb_lo, pb_hi) of nb
+int count_partition_batched(Ctx& c, uint32_t nb, unsigned n_batches, unsigned* n_seg, uint32_t pb_lo, uint32_t pb_hi);   // one segment of records per batch of reads
+uint32_t slab_route(const Ctx& c, uint32_t nb, unsigned npass_hash);    // records per bucket slab if this count may take the slab route, else 0
+int slab_excess_estimate(Ctx& c, uint32_t nb, uint32_t C, uint64_t* est, uint64_t* limit);   // records beyond the slabs, from a sample; above *limit: the scatter pass
+int count_partition_slabs(Ctx& c, uint32_t nb, uint32_t C, uint64_t refuse_from, bool* refused);
+int slab_segments(Ctx& c, uint32_t nb, const uint32_t* d_counts, uint64_t* d_seg);          // the slab layout's [2][nb] seg_pack() words for the counting kernels
 int count_buckets(Ctx& c, uint32_t min_freq, uint32_t nbl, uint32_t nseg, const uint32_t* d_recs, const uint32_t* d_counts, uint64_t total_kmers,
                   bool build_table = false);
 int count_buckets_launch(Ctx& c, uint32_t min_freq, uint32_t nbl, uint32_t nseg, const uint32_t* d_recs, const uint32_t* d_counts, uint64_t total_kmers,

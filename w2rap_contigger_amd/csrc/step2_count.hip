@@ -1,9 +1,6 @@
-// step2_count.hip -- phases a1..a6 of Step 2 on gfx950:
+// step2_count.hip -- phases a1..a6 of Step 2 on gfx950, all but the partition:
 //   K0  k_good_len        quality window per read                 (BuildReadQGraph.cc:962-987)
-//   K1  k_superkmers      canonical-minimizer super-k-mers: bucket histogram + one descriptor per record
-//   K2  k_scatter_records descriptor -> 32-B record in its bucket  (K1+K2 replace the leaf loop :1062-1080 and
-//                                                                   std::sort's partitioning :1081)
-//       (one GPU, one pass, reads of up to 315 good bases: K1 stores the records itself, into a slab per bucket -- count_partition_slabs)
+//   K1, K2                the partition into super-k-mer records grouped by bucket: step2_partition.hip
 //   K3  k_count_buckets   per-bucket LDS hash count/merge          (collapse_entries :1002-1013, combine_Entries :943-949,
 //                         + min_freq filter + histogram             filter :1094-1104)
 //   K4  k_table_insert    lookup table over solid k-mers           (new BRQ_Dict + insertEntryNoLocking :1092-1099)
@@ -164,519 +161,6 @@ int decode_pq(Ctx& c, const uint8_t* d_pq, const uint64_t* d_pqoff, uint8_t* d_q
     LAUNCH(c, "k_decode_pq", k_decode_pq, dim3((unsigned)((c.n + 255) / 256)), dim3(256), 0, c.n, d_pq, d_pqoff, d_quals, d_qoff);
     W2_HIP(hipGetLastError());
     return 0;
-}
-
-// =============================================================================== K1+K2
-// orders the LDS accesses of ONE wavefront (LDS executes a wave's operations in order; this only stops the compiler
-// from reordering them) -- unlike __syncthreads() it does not wait for outstanding global memory operations
-__device__ inline void wave_lds_fence() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-// (mmer_key, bucket_of: common.h -- the sharded graph phase and the pathing index use the same minimizers)
-
-// One wavefront per read; a pass covers 128 k-mer positions (two per lane), i.e. a whole PE150 read.
-// The canonical-minimizer of every k-mer is a sliding-window minimum over 46 m-mer keys; the window
-// minimum is computed by doubling (2,4,8,16,32, then 32+16) entirely in registers with ds_bpermute
-// lane shifts, so a pass is six cross-lane round trips deep and needs no barrier.  The m-mer key is
-// mix32(canonical 15-mer): mix32 is a bijection, so distinct m-mers never tie and the choice depends
-// only on the SET of canonical m-mers in the window (strand-symmetric, as it must be for a k-mer
-// and its reverse complement to land in the same bucket).
-__device__ inline uint32_t lane_shift(uint32_t lo, uint32_t hi, unsigned lane, unsigned d) {
-    // value at position (lane + d) of the concatenation lo[0..63] ++ hi[0..63]
-    const int idx = (int)(((lane + d) & 63u) << 2);
-    const uint32_t a = (uint32_t)__builtin_amdgcn_ds_bpermute(idx, (int)lo);
-    const uint32_t b = (uint32_t)__builtin_amdgcn_ds_bpermute(idx, (int)hi);
-    return lane + d < 64 ? a : b;
-}
-
-// Output of K1: the number of records per bucket (fire-and-forget atomics) and one 8-B descriptor per record
-// (bucket; start | nk-1 << 16 | hasL << 22 | hasR << 23).  Descriptors live at FIXED positions -- `spp` slots per
-// (read, pass of 128 k-mer positions), unused slots keep the 0xFFFFFFFF the array was filled with -- so the wave
-// neither reserves anything nor waits for memory; the rare pass with more than `spp` records appends the surplus
-// to a small overflow list.  K2 turns every descriptor into a 32-B record with one thread per slot, so the slot
-// reservations of a whole wavefront are in flight together instead of one read's at a time.
-template <unsigned MINW>
-__global__ void __launch_bounds__(256, MINW) k_superkmers(uint64_t n, uint32_t chunk, const uint8_t* __restrict__ bases,
-                                                    const uint64_t* __restrict__ boff, const uint16_t* __restrict__ good,
-                                                    uint32_t nb, uint32_t pb_lo, uint32_t pb_hi /* this pass keeps buckets [pb_lo, pb_hi) */,
-                                                    uint32_t* __restrict__ bcount /* [pb_hi - pb_lo] */,
-                                                    uint32_t nbl_part, uint32_t inv_nbl, unsigned long long* __restrict__ part_kmers,
-                                                    uint2* __restrict__ s_desc, uint32_t spp, uint32_t npass,
-                                                    const uint64_t* __restrict__ pass_off /* [n + 1]: read r's passes start at pass_off[r] */,
-                                                    uint32_t* __restrict__ o_read, uint32_t* __restrict__ o_bkt, uint32_t* __restrict__ o_meta,
-                                                    uint32_t* __restrict__ o_rank,
-                                                    uint64_t ov_cap, unsigned long long* __restrict__ ov_cursor /*[0] entries*/) {
-    // four independent wavefronts per block (a CU holds more 256-thread blocks than 64-thread ones); no block barriers
-    __shared__ uint2 dbuf_[4][128];       // the descriptors of one pass, in record order
-    __shared__ uint32_t spart_[4][64];    // multi-GPU: k-mers this wave sends to each owner rank (owner = bucket / nbl_part)
-    const unsigned lane = threadIdx.x & 63, wv_ = threadIdx.x >> 6;
-    if (part_kmers) { spart_[wv_][lane] = 0; wave_lds_fence(); }
-    uint2* dbuf = dbuf_[wv_];
-    // The window of a read that a pass needs (<= 206 bases = 52 bytes) lives in REGISTERS: lanes 0..15 hold the sixteen aligned dwords from
-    // the dword that contains the window's first byte (an aligned word that holds a valid byte never leaves the allocation), and a lane
-    // fetches the two dwords of its 15-mer from them with ds_bpermute.  (Rounds 1-3 staged the bytes in LDS: three fences, a clearing
-    // store, a byte store -- 60 of the pass's 300 VALU instructions.)
-    auto win_load = [&](uint64_t first_byte, unsigned nbytes) -> uint32_t {          // nbytes: valid bytes from first_byte on
-        const uintptr_t a = reinterpret_cast<uintptr_t>(bases) + first_byte;         // (aligned by ADDRESS: the array itself may start anywhere)
-        const unsigned sb = (unsigned)(a & 3);
-        return 4 * lane < sb + nbytes ? reinterpret_cast<const uint32_t*>(a & ~uintptr_t(3))[lane & 15u] : 0u;
-    };
-    // A wave takes `chunk` CONSECUTIVE reads and the grid has one wave per chunk: blocks are dispatched in order, so the reads
-    // -- and with them the ranks the histogram atomic hands out inside a bucket -- advance roughly in read order, the order in
-    // which the scatter pass writes the records (neighbouring slots of a bucket are then written close in time and meet in L2).
-    const uint64_t stride = 1;
-    uint64_t r = ((uint64_t)blockIdx.x * 4 + wv_) * chunk;
-    const uint64_t r_end = r + chunk < n ? r + chunk : n;
-    // Software pipeline over this wave's reads: the quality window and byte offset of the read after next and the
-    // first 60 packed bytes of the next read are loaded while the current read is cut, so no read waits for HBM.
-    unsigned gl_c = 0, gl_n = 0; uint64_t off_c = 0, off_n = 0; uint32_t win_c = 0;
-    if (r < r_end) { gl_c = good[r]; off_c = boff[r]; }
-    if (r + stride < r_end) { gl_n = good[r + stride]; off_n = boff[r + stride]; }
-    if (r < r_end && lane < 16 && gl_c > K) win_c = win_load(off_c, (gl_c + 3) >> 2);
-    for (; r < r_end; r += stride) {
-        const unsigned gl = gl_c;
-        const uint64_t off_cur = off_c;
-        const uint32_t win0 = win_c;
-        // look ahead
-        unsigned gl_nn = 0; uint64_t off_nn = 0;
-        if (r + 2 * stride < r_end) { gl_nn = good[r + 2 * stride]; off_nn = boff[r + 2 * stride]; }
-        win_c = 0;
-        if (r + stride < r_end && lane < 16 && gl_n > K) win_c = win_load(off_n, (gl_n + 3) >> 2);
-        gl_c = gl_n; off_c = off_n; gl_n = gl_nn; off_n = off_nn;
-        if (gl <= K) continue;                                   // strict, BuildReadQGraph.cc:1064: no records, no passes, no slots
-        const unsigned nk_total = gl - (K - 1);
-        const unsigned nbytes_read = (gl + 3) >> 2;
-        for (unsigned c0 = 0; c0 < nk_total; c0 += 128) {
-            // ---- stage the window of the read this pass needs: bases [c0-1, c0+189) ----
-            const unsigned first_base = c0 ? c0 - 1 : 0;
-            const unsigned b0a = (first_base >> 2) & ~3u;        // window start byte, dword aligned in the read
-            // this pass's window: the prefetched dwords (first pass) or sixteen dwords from byte b0a of the read on
-            uint32_t wdw = win0;
-            if (c0) wdw = lane < 16 ? win_load(off_cur + b0a, nbytes_read - b0a) : 0u;
-            const unsigned sbit = 8u * (unsigned)((reinterpret_cast<uintptr_t>(bases) + off_cur) & 3);   // the window's first byte inside its first dword (b0a is a multiple of 4)
-            const unsigned sbase = 4 * b0a;                      // read base of the window's first byte
-            // ---- canonical m-mer keys at m-mer positions c0+lane, c0+64+lane, c0+128+lane ----
-            uint32_t k0, k1, k2;
-            {
-                uint32_t kk[3];
-#pragma unroll
-                for (int h = 0; h < 3; ++h) {
-                    const unsigned j = c0 + h * 64 + lane;
-                    uint32_t key = 0xFFFFFFFFu;
-                    // (every lane takes part in the two cross-lane fetches; lanes without an m-mer read dword 0)
-                    const bool has = j + MMER <= gl && (h < 2 || lane < WIN - 1);
-                    const unsigned o = has ? sbit + 2 * (j - sbase) : 0u, wi = o >> 5, sh = o & 31;
-                    const uint32_t w0 = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(wi << 2), (int)wdw);
-                    const uint32_t w1 = (uint32_t)__builtin_amdgcn_ds_bpermute((int)((wi + 1) << 2), (int)wdw);
-                    if (has) {
-                        const uint32_t f = __funnelshift_r(w0, w1, sh) & 0x3FFFFFFFu;                 // 15 bases, LSB first
-                        // reverse complement in 32-bit ops: complement, reverse the 16 two-bit groups, drop the padding group
-                        uint32_t rc = __brev(~f & 0x3FFFFFFFu);
-                        rc = (((rc & 0x55555555u) << 1) | ((rc >> 1) & 0x55555555u)) >> 2;
-                        key = mmer_key(f < rc ? f : rc);
-                    }
-                    kk[h] = key;
-                }
-                k0 = kk[0]; k1 = kk[1]; k2 = kk[2];
-            }
-            // ---- sliding-window minimum over WIN=46 keys, by 16-lane rows: the window [p, p+45] is the suffix of p's
-            //      row from p, the prefix of (p+45)'s row up to p+45, and the one or two whole rows in between.
-            //      Suffix/prefix minima inside rows are DPP scans (VALU only), row minima travel through SGPRs
-            //      (v_readlane), and only the prefix at p+45 is a cross-lane fetch: 2 ds_bpermute per half-pass.
-            constexpr uint32_t INF = 0xFFFFFFFFu;
-            auto row_pref = [](uint32_t x) {
-                x = min(x, (uint32_t)__builtin_amdgcn_update_dpp((int)0xFFFFFFFFu, (int)x, 0x111, 0xF, 0xF, false));
-                x = min(x, (uint32_t)__builtin_amdgcn_update_dpp((int)0xFFFFFFFFu, (int)x, 0x112, 0xF, 0xF, false));
-                x = min(x, (uint32_t)__builtin_amdgcn_update_dpp((int)0xFFFFFFFFu, (int)x, 0x114, 0xF, 0xF, false));
-                x = min(x, (uint32_t)__builtin_amdgcn_update_dpp((int)0xFFFFFFFFu, (int)x, 0x118, 0xF, 0xF, false));
-                return x;
-            };
-            auto row_suff = [](uint32_t x) {
-                x = min(x, (uint32_t)__builtin_amdgcn_update_dpp((int)0xFFFFFFFFu, (int)x, 0x101, 0xF, 0xF, false));
-                x = min(x, (uint32_t)__builtin_amdgcn_update_dpp((int)0xFFFFFFFFu, (int)x, 0x102, 0xF, 0xF, false));
-                x = min(x, (uint32_t)__builtin_amdgcn_update_dpp((int)0xFFFFFFFFu, (int)x, 0x104, 0xF, 0xF, false));
-                x = min(x, (uint32_t)__builtin_amdgcn_update_dpp((int)0xFFFFFFFFu, (int)x, 0x108, 0xF, 0xF, false));
-                return x;
-            };
-            const uint32_t P0 = row_pref(k0), P1 = row_pref(k1), P2 = row_pref(k2), S0 = row_suff(k0), S1 = row_suff(k1);
-            uint32_t F[12];                                          // row minima, rows 0..11 of the 192 keys (wave-uniform)
-#pragma unroll
-            for (int R = 0; R < 4; ++R) {
-                F[R] = (uint32_t)__builtin_amdgcn_readlane((int)P0, 16 * R + 15);
-                F[4 + R] = (uint32_t)__builtin_amdgcn_readlane((int)P1, 16 * R + 15);
-                F[8 + R] = (uint32_t)__builtin_amdgcn_readlane((int)P2, 16 * R + 15);
-            }
-            const unsigned rowi = lane >> 4;
-            const bool two = (lane & 15u) >= 3;                      // (p+45) lies three rows after p's row: two whole rows between
-            uint32_t mkh[2];
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                const uint32_t g1a = F[4 * h + 1], g1b = F[4 * h + 2], g1c = F[4 * h + 3], g1d = F[4 * h + 4];
-                const uint32_t g2a = min(g1a, F[4 * h + 2]), g2b = min(g1b, F[4 * h + 3]), g2c = min(g1c, F[4 * h + 4]), g2d = min(g1d, F[4 * h + 5]);
-                const uint32_t one_row = rowi == 0 ? g1a : rowi == 1 ? g1b : rowi == 2 ? g1c : g1d;
-                const uint32_t two_rows = rowi == 0 ? g2a : rowi == 1 ? g2b : rowi == 2 ? g2c : g2d;
-                const uint32_t pend = h ? lane_shift(P1, P2, lane, WIN - 1) : lane_shift(P0, P1, lane, WIN - 1);
-                mkh[h] = min(min(h ? S1 : S0, pend), two ? two_rows : one_row);
-            }
-            const uint32_t mk0 = mkh[0], mk1 = mkh[1];
-            // ---- two half-passes of 64 k-mer positions.  All global traffic of both halves (slot
-            //      reservation, bucket base) is issued before any of it is consumed, so a read pays
-            //      one atomic round trip, not two. ----
-            unsigned nkh[2] = {0, 0}; uint32_t bkh[2] = {0, 0}; bool sth[2] = {false, false};
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                const unsigned cc0 = c0 + 64 * h;
-                const unsigned p = cc0 + lane;
-                const bool valid = p < nk_total;
-                const uint32_t bkt = valid ? bucket_of(h ? mk1 : mk0, nb) : 0xFFFFFFFFu;
-                const uint32_t prev = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)bkt, 0x138, 0xF, 0xF, false);   // wave_shr:1 (lane 0 unused)
-                bool start = valid && (lane == 0 || prev != bkt);
-                unsigned long long smask = __ballot(start);
-                unsigned nvalid = cc0 < nk_total ? nk_total - cc0 : 0; if (nvalid > 64) nvalid = 64;
-                // a record holds at most 63 k-mers (32 B): a half-pass that is ONE run of 64 is cut before its last k-mer
-                if (REC_MAXK < 64 && smask == 1ull && nvalid == 64) { start |= lane == 63; smask |= 1ull << 63; }
-                unsigned long long rest = lane < 63 ? (smask >> (lane + 1)) : 0ull;
-                unsigned nxt = rest ? lane + 1 + __builtin_ctzll(rest) : nvalid;
-                // multi-pass counting (MapReduceEngine.h:288-291): records of buckets outside this pass's range are dropped here and
-                // cut again in their own pass; bucket numbers are relative to the range
-                const bool mine = bkt - pb_lo < pb_hi - pb_lo;
-                sth[h] = start && mine; bkh[h] = bkt - pb_lo; nkh[h] = start ? nxt - lane : 0;
-            }
-            unsigned cnt = 0;
-            const uint64_t slot0 = (pass_off[r] + c0 / 128) * spp;
-            // the histogram atomic RETURNS the record's rank inside its bucket: it travels in the descriptor (16 bits; the rare
-            // bucket that gets more than 65535 records from these reads sends the surplus through the overflow list), so the
-            // scatter pass needs no atomic of its own.  Both halves' atomics are in flight before either result is used.
-            uint32_t rk[2] = {0, 0};
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                if (sth[h]) {
-                    rk[h] = atomicAdd(&bcount[bkh[h]], 1u);
-                    if (part_kmers) {                                        // bucket / nbl_part by reciprocal (+1 correction)
-                        uint32_t pt = nbl_part > 1 ? __umulhi(bkh[h], inv_nbl) : bkh[h];
-                        if ((pt + 1) * nbl_part <= bkh[h]) ++pt;
-                        atomicAdd(&spart_[wv_][pt & 63], nkh[h]);
-                    }
-                }
-            }
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                const unsigned long long m = __ballot(sth[h]);
-                if (sth[h]) {
-                    const unsigned p = c0 + 64 * h + lane, nk = nkh[h];
-                    const uint32_t meta = p | ((nk - 1) << 16) | (p > 0 ? 1u << 22 : 0u) | ((p + nk - 1) < (nk_total - 1) ? 1u << 23 : 0u);
-                    const unsigned j = cnt + (unsigned)__builtin_popcountll(m & ((1ull << lane) - 1));
-                    if (j < spp && rk[h] < 65536u) dbuf[j] = make_uint2(bkh[h] | (rk[h] << 24), meta | ((rk[h] >> 8) << 24));
-                    else {
-                        if (j < spp) dbuf[j] = make_uint2(0u, NONE32);
-                        const unsigned long long o = atomicAdd(ov_cursor, 1ull);
-                        if (o < ov_cap) { o_read[o] = (uint32_t)r; o_bkt[o] = bkh[h]; o_meta[o] = meta; o_rank[o] = rk[h]; }
-                    }
-                }
-                cnt += (unsigned)__builtin_popcountll(m);
-            }
-            // the pass's slots as whole, coalesced 8-B stores (unused ones marked empty)
-            wave_lds_fence();
-            for (unsigned i = lane; i < spp; i += 64) s_desc[slot0 + i] = i < cnt ? dbuf[i] : make_uint2(0u, NONE32);
-            wave_lds_fence();
-        }
-    }
-    if (part_kmers) {
-        wave_lds_fence();
-        const uint32_t v = spart_[wv_][lane];
-        // 64 copies of the 64 totals: millions of waves adding to ONE address would serialise at ~11 ns each
-        if (v) atomicAdd(&part_kmers[(blockIdx.x & 63u) * 64u + lane], (unsigned long long)v);
-    }
-}
-
-
-// ------------------------------------------------------------------------------- K1, one LANE per read (round 4)
-// The wavefront-per-read kernel above spends ~300 VALU instructions of a whole wavefront on the 136 m-mers of a PE150 read (cross-lane
-// scans for the window minimum, wave-wide control flow per record) -- measured in round 4: with its atomics AND its descriptor stores
-// removed it still takes 19.2 of its 22.9 ms (profiles/r04_k1_diag.txt), it is bound by its own instruction stream.  Here a lane walks
-// ITS read base by base: the forward and the reverse-complement 15-mer roll (five operations), the sliding-window minimum over 46 keys is
-// the block decomposition of van Herk / Gil-Werman with blocks of 16 keys held in registers -- a window is the suffix of its first block,
-// one or two whole blocks and the running prefix of the current one: one v_min3 per position --, and a run of equal buckets ends with ~10 instructions of the few
-// lanes it concerns.  Descriptors (bucket, meta) are staged in LDS at the lane's S slots; when the 64 reads are done the wave turns the
-// staged descriptors into final ones 64 at a time -- the histogram atomic returns the rank -- and stores them coalesced: the 64 reads'
-// slots are one contiguous piece of s_desc.  Runs are cut at bucket changes and when a record is full (REC_MAXK = 63 k-mers);
-// the kernel above also cuts at every multiple of 64 (its half-passes).
-// SLABS (NOTES.md section 19): every bucket owns records [b * C, (b + 1) * C) of `recs`, so the rank the histogram atomic returns IS the
-// record's place: the tail builds the 32-B record itself (rec_build, K2's code; the wave's reads are 2.4 KB it loaded a moment ago) and
-// stores it as K2 does -- through LDS, two lanes per record, 16 B each -- and no descriptor is written.  Ranks >= C go to the overflow list
-// like a read's records beyond its S slots; K2's list branch places both.  The LDS it needs is the part of the staging area whose
-// descriptors the lanes hold in registers by then.
-template <unsigned SMAX, bool ALIGN64, bool SLABS = false, unsigned MINW = 4>
-__global__ void __launch_bounds__(256, MINW) k_superkmers_lane(uint64_t n, const uint8_t* __restrict__ bases, const uint64_t* __restrict__ boff,
-                                                            const uint16_t* __restrict__ good, uint32_t nb, uint32_t pb_lo, uint32_t pb_hi,
-                                                            uint32_t* __restrict__ bcount, uint32_t nbl_part, uint32_t inv_nbl,
-                                                            unsigned long long* __restrict__ part_kmers, uint2* __restrict__ s_desc, uint32_t S,
-                                                            uint32_t* __restrict__ o_read, uint32_t* __restrict__ o_bkt, uint32_t* __restrict__ o_meta,
-                                                            uint32_t* __restrict__ o_rank, uint64_t ov_cap, unsigned long long* __restrict__ ov_cursor,
-                                                            uint32_t* __restrict__ recs, uint32_t slab_cap, uint64_t bases_bytes) {
-    __shared__ __attribute__((aligned(16))) uint2 stage_[4][64 * SMAX];
-    __shared__ uint32_t spart_[4][64];
-    const unsigned lane = threadIdx.x & 63, wv_ = threadIdx.x >> 6;
-    const uint64_t r0 = ((uint64_t)blockIdx.x * 4 + wv_) * 64;
-    if (r0 >= n) return;                                     // (the whole wavefront; the kernel has no block barrier)
-    uint2* stage = stage_[wv_];
-    if (part_kmers) spart_[wv_][lane] = 0;
-    for (unsigned u = 0; u < S; ++u) stage[lane + 64 * u] = make_uint2(0u, NONE32);
-    wave_lds_fence();
-    constexpr uint32_t INF = 0xFFFFFFFFu;
-    const uint64_t r = r0 + lane;
-    unsigned gl = r < n ? good[r] : 0;
-    if (gl <= K) gl = 0;                                     // strict, BuildReadQGraph.cc:1064
-    const unsigned nk = gl ? gl - (K - 1) : 0;
-    unsigned maxgl = gl;
-#pragma unroll
-    for (int d = 32; d; d >>= 1) maxgl = max(maxgl, (unsigned)__shfl_xor((int)maxgl, d));
-    maxgl = (unsigned)__builtin_amdgcn_readfirstlane((int)maxgl);
-    if (maxgl) {
-        // the read as ALIGNED dwords (an aligned word that holds a valid byte never leaves the allocation), sixteen bases per refill, one
-        // refill ahead; words past the read's last one are not loaded (the last one again: bases past the good length are never used)
-        const uint64_t off = gl ? boff[r] : 0;
-        const unsigned mis = (unsigned)((reinterpret_cast<uintptr_t>(bases) + off) & 3);
-        const unsigned sb8 = 8u * mis;
-        const uint32_t* q = reinterpret_cast<const uint32_t*>(bases + ((int64_t)off - (int64_t)mis));
-        const unsigned ulast = gl ? (mis + ((gl + 3) >> 2) - 1) >> 2 : 0;
-        uint32_t dA, dB, W; unsigned un = 3;
-        { const uint32_t d0 = q[0]; dA = q[min(1u, ulast)]; dB = q[min(2u, ulast)]; W = __funnelshift_r(d0, dA, sb8); }
-        uint32_t f = 0, rc = 0;
-        auto roll = [&]() {                                  // takes the next base into the two 15-mers
-            const uint32_t b = W & 3u; W >>= 2;
-            f = (f >> 2) | (b << 28);
-            rc = ((rc << 2) & 0x3FFFFFFFu) | (b ^ 3u);
-        };
-#pragma unroll
-        for (unsigned s = 0; s < MMER - 1; ++s) roll();
-        // Sliding-window minimum over WIN = 46 keys, blocks of 16 m-mers: at m-mer 16c + i the window of k-mer 16c + i - 45 is the suffix of
-        // block c-3 from i+3, the blocks c-2 and c-1 and the prefix of block c (i <= 12), or the suffix of block c-2 from i-13, block c-1
-        // and the prefix of block c (i >= 13): one v_min3 per position.  X3, X2, X1: suffix minima of the three blocks before the current one.
-        uint32_t X3[16], X2[16], X1[16], C[16];
-#pragma unroll
-        for (int t = 0; t < 16; ++t) { X3[t] = INF; X2[t] = INF; X1[t] = INF; C[t] = INF; }
-        uint32_t cur = 0;
-        unsigned p0 = 0, jrec = 0;
-        // one block of 16 m-mers from m-mer jb on (base jb + 14 + i is taken at step i: the refill of sixteen bases falls on step 2 of every
-        // block).  FIRST: its first step that has a k-mer position -- blocks 0 and 1 have none, block 2 has k-mer 0 at step 13.  Steps past
-        // the longest read of the wave do nothing (no key, no k-mer), so the block needs no guard -- a guard makes every array a phi of
-        // the branch and costs a register move per element and step.
-        auto block = [&](auto first, unsigned jb) {
-            constexpr int FIRST = decltype(first)::value;
-            // stage 1, branch-free: the sixteen keys of the block and the buckets of its k-mer positions -- sixteen independent chains
-            // (three multiplications each) in one basic block, so that a wavefront alone keeps its SIMD issuing
-            uint32_t pref = INF;
-            const uint32_t w21 = min(X2[0], X1[0]);
-            uint32_t bk[16];
-#pragma unroll
-            for (int i = 0; i < 16; ++i) {
-                const unsigned s = jb + (MMER - 1) + i;      // base taken in this step; m-mer s-14 is complete, k-mer s-59 gets its window
-                if (i == 2) { W = __funnelshift_r(dA, dB, sb8); dA = dB; dB = q[min(un, ulast)]; ++un; }
-                roll();
-                const uint32_t key = s < gl ? mmer_key(f < rc ? f : rc) : INF;
-                C[i] = key; pref = min(pref, key);
-                bk[i] = 0;
-                if (i >= FIRST) {
-                    const uint32_t mk = i <= 12 ? min(min(X3[i <= 12 ? i + 3 : 0], w21), pref) : min(min(X2[i >= 13 ? i - 13 : 0], X1[0]), pref);
-                    bk[i] = bucket_of(mk, nb);
-                }
-            }
-            // stage 2: where runs end (the few lanes it concerns; nearly every step has some)
-#pragma unroll
-            for (int i = FIRST; i < 16; ++i) {
-                const unsigned p = jb + i - (WIN - 1);       // (= s - 59)
-                const bool isk = p < nk;
-                const uint32_t bkt = bk[i];
-                // a run ends where the bucket changes and when the record is full (ALIGN64: at every multiple of 64 instead, the cuts
-                // of the wavefront-per-read kernel -- 17 % more records; the parity test of the two kernels asks for it)
-                const bool brk = isk && (!p || bkt != cur || (ALIGN64 ? !(p & 63u) || (REC_MAXK < 64 && p - p0 == REC_MAXK) : p - p0 == REC_MAXK));
-                if ((brk && p) || (p == nk && nk)) {                                  // the run [p0, p) ends here
-                    const uint32_t rb = cur - pb_lo;
-                    if (rb < pb_hi - pb_lo) {                // multi-pass counting: other ranges' records are cut again in their own pass
-                        const uint32_t meta = p0 | ((p - p0 - 1) << 16) | (p0 ? 1u << 22 : 0u) | (isk ? 1u << 23 : 0u);
-                        if (jrec < S) stage[lane * S + jrec] = make_uint2(rb, meta);
-                        else {                               // more records than slots: the overflow list, with its rank
-                            const uint32_t rk = atomicAdd(&bcount[rb], 1u);
-                            if (part_kmers) {
-                                uint32_t pt = nbl_part > 1 ? __umulhi(rb, inv_nbl) : rb;
-                                if ((pt + 1) * nbl_part <= rb) ++pt;
-                                atomicAdd(&spart_[wv_][pt & 63], p - p0);
-                            }
-                            const unsigned long long o = atomicAdd(ov_cursor, 1ull);
-                            if (o < ov_cap) { o_read[o] = (uint32_t)r; o_bkt[o] = rb; o_meta[o] = meta; o_rank[o] = rk; }
-                        }
-                        ++jrec;
-                    }
-                }
-                if (brk) { p0 = p; cur = bkt; }
-            }
-#pragma unroll
-            for (int t = 14; t >= 0; --t) C[t] = min(C[t], C[t + 1]);                     // suffix minima of the block just filled
-#pragma unroll
-            for (int t = 0; t < 16; ++t) { X3[t] = X2[t]; X2[t] = X1[t]; X1[t] = C[t]; }
-        };
-        block(std::integral_constant<int, 16>{}, 0);
-        block(std::integral_constant<int, 16>{}, 16);
-        block(std::integral_constant<int, 13>{}, 32);
-        for (unsigned jb = 48; jb + (MMER - 1) <= maxgl; jb += 16) block(std::integral_constant<int, 0>{}, jb);
-    }
-    wave_lds_fence();
-    // ---- staged descriptors -> final ones, 64 at a time in slot order (conflict-free LDS reads, coalesced stores): the histogram atomic
-    //      RETURNS the record's rank inside its bucket (16 bits in the descriptor; beyond that the overflow list); eight atomics are in
-    //      flight per lane before the first result is used
-    const uint64_t nflat = (uint64_t)((n - r0 < 64 ? n - r0 : 64)) * S;
-    for (unsigned u0 = 0; u0 < S; u0 += 8) {
-        uint2 d[8]; uint32_t rk[8];
-#pragma unroll
-        for (unsigned k = 0; k < 8; ++k) {
-            const unsigned i = lane + 64 * (u0 + k);
-            d[k] = u0 + k < S ? stage[i] : make_uint2(0u, NONE32);
-            rk[k] = 0;
-            if (d[k].y != NONE32) {
-                rk[k] = atomicAdd(&bcount[d[k].x], 1u);
-                if (part_kmers) {                            // bucket / nbl_part by reciprocal (+1 correction)
-                    uint32_t pt = nbl_part > 1 ? __umulhi(d[k].x, inv_nbl) : d[k].x;
-                    if ((pt + 1) * nbl_part <= d[k].x) ++pt;
-                    atomicAdd(&spart_[wv_][pt & 63], ((d[k].y >> 16) & 63u) + 1u);
-                }
-            }
-        }
-        if constexpr (SLABS && REC_DWORDS == 8) {
-            // the 512 staged descriptors of this group are in registers: their 4 KB hold the 64 records of a round (2 KB) and their places
-            static_assert(SMAX >= 8, "a group of eight slots per lane is the tail's record buffer");
-            uint4* s_rec = reinterpret_cast<uint4*>(stage + 64 * u0);                       // [128]
-            uint64_t* s_dst = reinterpret_cast<uint64_t*>(stage + 64 * u0 + 256);           // [64]
-#pragma unroll 1
-            for (unsigned k = 0; k < 8 && u0 + k < S; ++k) {                                 // (one copy of the builder: d[] and rk[] rotate through element 0)
-                const unsigned i = lane + 64 * (u0 + k);
-                const uint2 dk = d[0]; const uint32_t rkk = rk[0];
-#pragma unroll
-                for (unsigned t = 0; t < 7; ++t) { d[t] = d[t + 1]; rk[t] = rk[t + 1]; }
-                uint64_t dst = ~0ull;
-                uint32_t out[REC_DWORDS] = {};
-                const uint32_t rd = (uint32_t)(r0 + i / S);
-                const bool listed = dk.y != NONE32 && rkk >= slab_cap;
-                if (dk.y != NONE32 && !listed) {
-                    rec_build(bases, bases_bytes, boff[rd], dk.y, out);
-                    dst = slab_place(dk.x, rkk, slab_cap, 0, 0) * REC_DWORDS;
-                }
-                // beyond the slab: the list, its cursor taken ONCE for the wave's lanes (every wave's atomics on that one word queue up behind each other)
-                const unsigned long long lm = __ballot(listed);
-                if (lm) {
-                    unsigned long long o0 = 0;
-                    if (lane == (unsigned)__ffsll((long long)lm) - 1u) o0 = atomicAdd(ov_cursor, (unsigned long long)__popcll(lm));
-                    o0 = ((unsigned long long)(unsigned)__shfl((int)(o0 >> 32), __ffsll((long long)lm) - 1) << 32) | (unsigned)__shfl((int)o0, __ffsll((long long)lm) - 1);
-                    const unsigned long long o = o0 + __popcll(lm & ((1ull << lane) - 1ull));
-                    if (listed && o < ov_cap) { o_read[o] = rd; o_bkt[o] = dk.x; o_meta[o] = dk.y; o_rank[o] = rkk; }
-                }
-                wave_lds_fence();                                                            // (the round before has left the buffer)
-                s_rec[2 * lane] = make_uint4(out[0], out[1], out[2], out[3]);
-                s_rec[2 * lane + 1] = make_uint4(out[4], out[5], out[6], out[7]);
-                s_dst[lane] = dst;
-                wave_lds_fence();
-#pragma unroll
-                for (unsigned j = 0; j < 2; ++j) {
-                    const unsigned idx = j * 64 + lane;
-                    const uint64_t t = s_dst[idx >> 1];
-                    if (t != ~0ull) reinterpret_cast<uint4*>(recs + t)[idx & 1u] = s_rec[idx];
-                }
-            }
-            wave_lds_fence();
-            continue;
-        }
-#pragma unroll
-        for (unsigned k = 0; k < 8; ++k) {
-            const unsigned i = lane + 64 * (u0 + k);
-            if (u0 + k < S && i < nflat) {
-                uint2 out = make_uint2(0u, NONE32);
-                if (d[k].y != NONE32) {
-                    if (rk[k] < 65536u) out = make_uint2(d[k].x | (rk[k] << 24), d[k].y | ((rk[k] >> 8) << 24));
-                    else {
-                        const unsigned long long o = atomicAdd(ov_cursor, 1ull);
-                        if (o < ov_cap) { o_read[o] = (uint32_t)(r0 + i / S); o_bkt[o] = d[k].x; o_meta[o] = d[k].y; o_rank[o] = rk[k]; }
-                    }
-                }
-                s_desc[r0 * S + i] = out;
-            }
-        }
-    }
-    if (part_kmers) {
-        wave_lds_fence();
-        const uint32_t v = spart_[wv_][lane];
-        if (v) atomicAdd(&part_kmers[(blockIdx.x & 63u) * 64u + lane], (unsigned long long)v);
-    }
-}
-
-// =============================================================================== K2
-// One thread per descriptor slot (then per overflow entry): the record's place is its bucket's base + the rank K1's
-// histogram atomic returned; cut the 2*(nk+61) stream bits [left flank][k-mers' bases][right flank] out of the read
-// (unaligned 8-byte loads), store the 32-B record.  No atomics.
-// (PASS_OFF: the wavefront kernel's layout, spp slots per pass a read has -- slots_per_read is spp, pass_off[nreads + 1] the reads' first passes)
-// (its binary search costs ~log2(nreads) dependent loads per slot; it runs only where the longest read passes 315 bases or W2RAP_K1=wave,
-// never on the PE150 lane route, and its cost on long-read inputs has not been measured)
-template <bool PASS_OFF>
-__global__ void __launch_bounds__(256) k_scatter_records(uint64_t nslots, uint32_t slots_per_read, const uint64_t* __restrict__ pass_off, uint64_t nreads,
-                                                          const uint2* __restrict__ s_desc,
-                                                          uint64_t nov, const uint32_t* __restrict__ o_read,
-                                                          const uint32_t* __restrict__ o_bkt, const uint32_t* __restrict__ o_meta,
-                                                          const uint32_t* __restrict__ o_rank,
-                                                          const uint8_t* __restrict__ bases,
-                                                          const uint64_t* __restrict__ boff, uint64_t bases_bytes,
-                                                          const uint64_t* __restrict__ bbase,
-                                                          uint32_t* __restrict__ recs, uint32_t slab_cap, uint64_t slab_nb) {
-    // A wavefront's 64 records leave through LDS: built one per lane, stored REC_DWORDS lanes per record, so that every store
-    // instruction carries eight whole 32-B records (seven of 36 B in a W2RAP_REC36 build) as contiguous bursts instead of 64 scattered dwords.
-    __shared__ __attribute__((aligned(16))) uint32_t s_rec[4][64 * REC_DWORDS];
-    __shared__ uint64_t s_dst[4][64];
-    const unsigned lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    uint32_t r = 0, b = 0, meta = NONE32, slot = 0;
-    if (i < nslots) {
-        const uint2 d = s_desc[i];
-        if (d.y != NONE32) { meta = d.y & 0xFFFFFFu; b = d.x & 0xFFFFFFu; slot = (d.x >> 24) | ((d.y >> 24) << 8); }
-        if (PASS_OFF) {                                          // the read whose passes hold pass i / spp: pass_off[lo] <= pass < pass_off[hi]
-            const uint64_t ps = i / slots_per_read;
-            uint64_t lo = 0, hi = nreads;
-            while (hi - lo > 1) { const uint64_t mid = (lo + hi) >> 1; if (pass_off[mid] <= ps) lo = mid; else hi = mid; }
-            r = (uint32_t)lo;
-        } else r = (uint32_t)(i / slots_per_read);
-    } else if (i - nslots < nov) { r = o_read[i - nslots]; b = o_bkt[i - nslots]; meta = o_meta[i - nslots]; slot = o_rank[i - nslots]; }
-    const bool valid = meta != NONE32;
-    uint64_t dst = ~0ull;
-    uint32_t out[REC_DWORDS] = {};
-    if (valid) {
-        // (slab route, nslots == 0: the listed records only -- into the bucket's slab, or beyond it into the overflow segment, bbase its scan)
-        const uint64_t place = slab_cap ? slab_place(b, slot, slab_cap, slab_nb, slot < slab_cap ? 0 : bbase[b]) : bbase[b] + slot;
-        rec_build(bases, bases_bytes, boff[r], meta, out);
-        dst = place * REC_DWORDS;
-    }
-    if constexpr (REC_DWORDS == 8) {
-        reinterpret_cast<uint4*>(s_rec[wv])[2 * lane] = make_uint4(out[0], out[1], out[2], out[3]);
-        reinterpret_cast<uint4*>(s_rec[wv])[2 * lane + 1] = make_uint4(out[4], out[5], out[6], out[7]);
-    } else {
-#pragma unroll
-        for (unsigned j = 0; j < REC_DWORDS; ++j) s_rec[wv][lane * REC_DWORDS + j] = out[j];
-    }
-    s_dst[wv][lane] = dst;
-    wave_lds_fence();
-    if constexpr (REC_DWORDS == 8) {                               // 32-B records, 32-B aligned: two lanes per record, 16 B each
-#pragma unroll
-        for (unsigned j = 0; j < 2; ++j) {
-            const unsigned idx = j * 64 + lane, rec = idx >> 1;
-            const uint64_t d = s_dst[wv][rec];
-            if (d != ~0ull) reinterpret_cast<uint4*>(recs + d)[idx & 1u] = reinterpret_cast<const uint4*>(s_rec[wv])[idx];
-        }
-    } else {
-#pragma unroll
-        for (unsigned j = 0; j < REC_DWORDS; ++j) {
-            const unsigned idx = j * 64 + lane, rec = idx / REC_DWORDS, qd = idx - rec * REC_DWORDS;
-            const uint64_t d = s_dst[wv][rec];
-            if (d != ~0ull) recs[d + qd] = s_rec[wv][idx];
-        }
-    }
 }
 
 // =============================================================================== K3
@@ -2061,456 +1545,6 @@ uint32_t default_buckets(uint64_t total_kmers, uint32_t multiple_of) {
     return (uint32_t)nb64;
 }
 
-static uint32_t k1_chunk_reads() {                      // consecutive reads per wavefront of K1
-    const char* v = getenv("W2RAP_K1_CHUNK");
-    const int x = v ? atoi(v) : 16;
-    return x > 0 ? (uint32_t)x : 16;
-}
-
-
-// K1 on reads [0, nr) of (boff, good): the lane-per-read kernel when a read's slots fit its LDS staging (spp * npass <= 16: reads up to
-// ~315 good bases at the default 8 slots per pass), the wavefront-per-read kernel otherwise or with W2RAP_K1=wave
-// (W2RAP_K1_MINW: 6 or 7 waves per SIMD instead of 8 for the latter -- 80 / 72 VGPRs, no spills -- an A/B knob)
-static bool k1_wave(uint32_t spp, uint32_t npass) {
-    const char* k1v = getenv("W2RAP_K1");
-    return (k1v && !strcmp(k1v, "wave")) || spp * npass > 16;
-}
-// descriptor slots per pass of 128 k-mer positions (W2RAP_SPP, default 8) and passes of the longest read: the one place they are derived
-static void k1_slots(const Ctx& c, uint32_t* spp, uint32_t* npass) {
-    const char* sv = getenv("W2RAP_SPP");
-    *spp = sv ? (uint32_t)atoi(sv) : 8;
-    *npass = c.max_len > K + 127 ? (c.max_len - (K - 1) + 127) / 128 : 1;
-}
-
-__global__ void __launch_bounds__(256) k_k1_passes(uint64_t n, const uint16_t* __restrict__ good, uint32_t* __restrict__ np) {
-    const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (r >= n) return;
-    const uint32_t g = good[r];
-    np[r] = g > K ? (g - (K - 1) + 127) / 128 : 0;
-}
-
-// The wavefront kernel's descriptor slots: spp per pass of 128 k-mer positions that read r HAS, from slot pass_off[r] * spp on -- sized by
-// the reads' own lengths, not n times the longest read's passes (one read of 65,535 bases among 600 k PE150 reads: 20 GB of slots).
-// pass_off: [nr + 1] (the caller's); *total: the passes of all nr reads.
-static int k1_pass_offsets(Ctx& c, uint64_t nr, const uint16_t* good, uint64_t* pass_off, uint64_t* total) {
-    *total = 0;
-    if (!nr) return 0;
-    uint32_t* np = nullptr;
-    W2_ALLOC(np, uint32_t, nr);
-    LAUNCH(c, "k_k1_passes", k_k1_passes, dim3((unsigned)((nr + 255) / 256)), dim3(256), 0, nr, good, np);
-    W2_HIP(hipGetLastError());
-    W2_TRY(exclusive_scan_u32_to_u64(c, np, pass_off, nr));
-    W2_HIP(hipMemcpyAsync(total, pass_off + nr, 8, hipMemcpyDeviceToHost, c.stream));
-    W2_HIP(hipStreamSynchronize(c.stream));
-    c.release(np);
-    return 0;
-}
-
-static int launch_k1(Ctx& c, uint64_t nr, const uint64_t* boff, const uint16_t* good, uint32_t pb_lo, uint32_t pb_hi, uint32_t* bcount,
-                     uint32_t nbl_part, uint32_t inv_nbl, unsigned long long* d_part, uint2* s_desc, uint32_t spp, uint32_t npass,
-                     const uint64_t* pass_off /* k1_wave: k1_pass_offsets' */,
-                     uint32_t* o_read, uint32_t* o_bkt, uint32_t* o_meta, uint32_t* o_rank, uint64_t ov_cap, unsigned long long* d_ov_cur,
-                     uint32_t* slab_recs = nullptr, uint32_t slab_cap = 0, uint64_t bases_bytes = 0 /* the slab route: the lane kernel stores the records */) {
-    if (getenv("W2RAP_TRACE"))                           // the route (tests assert it: a moved threshold must not go unnoticed)
-        fprintf(stderr, "[w2rap] K1 route: %s, npass %u, spp %u, %llu reads, longest %u, records %s %u\n", k1_wave(spp, npass) ? "wave" : "lane",
-                npass, spp, (unsigned long long)nr, c.max_len, slab_cap ? "to slabs of" : "by scatter pass", slab_cap);
-    if (slab_cap) {
-        if (k1_wave(spp, npass) || REC_DWORDS != 8) { c.err = "partition: the slab route is the lane kernel's"; return W2RAP_E_STATE; }
-#define W2_K1S(SMAX, MINW) LAUNCH(c, "k_superkmers_lane", (k_superkmers_lane<SMAX, false, true, MINW>), dim3((unsigned)((nr + 255) / 256)), dim3(256), 0, nr, c.d_bases, \
-                                  boff, good, c.NB, pb_lo, pb_hi, bcount, nbl_part, inv_nbl, d_part, (uint2*)nullptr, spp * npass, o_read, o_bkt, o_meta, o_rank, ov_cap,   \
-                                  d_ov_cur, slab_recs, slab_cap, bases_bytes)
-        // (eight slots per read -- PE150 -- need half the staging area, so more than four blocks fit a CU, and the tail is a chain of round
-        // trips that only other waves hide: K1 14.5 / 13.6 / 11.9 ms at 4 / 5 / 6 waves per SIMD -- the last with 15 VGPRs spilled --, 16.5 at
-        // 7 and 8, whose instantiations are not kept (NOTES.md section 19).  The six-wave figure rests on WHERE the allocator puts those
-        // spills: two small edits of the tail moved them and lost the whole gain.  After any edit of the kernel, measure 4 / 5 / 6 again
-        // (W2RAP_TEST_K1_SLAB_WAVES = 4, 5: a test hook, announced like the others))
-        int waves = 6;
-        if (const char* wv = getenv("W2RAP_TEST_K1_SLAB_WAVES")) { if (test_hook("W2RAP_TEST_K1_SLAB_WAVES")) waves = atoi(wv); }
-        if (spp * npass > 8 || waves == 4) W2_K1S(16, 4);
-        else if (waves == 5) W2_K1S(8, 5);
-        else W2_K1S(8, 6);
-#undef W2_K1S
-        W2_HIP(hipGetLastError());
-        return 0;
-    }
-    if (!k1_wave(spp, npass)) {
-        // (four waves per SIMD: with five -- the staging area of 8 slots per read would leave room -- the scatter pass beside it loses more
-        // than this kernel gains, partition 20.6 -> 23.8 ms; W2RAP_K1_ALIGN64: the cuts of the wavefront-per-read kernel, for the test that
-        // compares the two)
-        const bool a64 = getenv("W2RAP_K1_ALIGN64") != nullptr;
-        const dim3 grid((unsigned)((nr + 255) / 256));
-#define W2_K1L(A64) LAUNCH(c, "k_superkmers_lane", (k_superkmers_lane<16, A64>), grid, dim3(256), 0, nr, c.d_bases, boff, good, c.NB, pb_lo, pb_hi, bcount, \
-                           nbl_part, inv_nbl, d_part, s_desc, spp * npass, o_read, o_bkt, o_meta, o_rank, ov_cap, d_ov_cur, (uint32_t*)nullptr, 0u, 0ull)
-        if (a64) W2_K1L(true); else W2_K1L(false);
-#undef W2_K1L
-        W2_HIP(hipGetLastError());
-        return 0;
-    }
-    // many more blocks than fit at once (8 resident per CU with __launch_bounds__(256, 8)): the dispatcher refills freed slots,
-    // so no CU waits for a straggler block (a grid of exactly "8 per CU" ran 25 ms instead of 20 -- the occupancy API answers 7,
-    // the hardware admits 6, and the surplus blocks start when the others are done)
-    const uint32_t k1_chunk = k1_chunk_reads();
-    const unsigned grid = (unsigned)((nr + 4ull * k1_chunk - 1) / (4ull * k1_chunk) + 1);
-    static const int k1_minw = getenv("W2RAP_K1_MINW") ? atoi(getenv("W2RAP_K1_MINW")) : 8;
-    if (k1_minw == 6)
-        LAUNCH(c, "k_superkmers", k_superkmers<6>, dim3(grid), dim3(256), 0, nr, k1_chunk, c.d_bases, boff, good, c.NB, pb_lo, pb_hi, bcount, nbl_part, inv_nbl, d_part,
-               s_desc, spp, npass, pass_off, o_read, o_bkt, o_meta, o_rank, ov_cap, d_ov_cur);
-    else if (k1_minw == 7)
-        LAUNCH(c, "k_superkmers", k_superkmers<7>, dim3(grid), dim3(256), 0, nr, k1_chunk, c.d_bases, boff, good, c.NB, pb_lo, pb_hi, bcount, nbl_part, inv_nbl, d_part,
-               s_desc, spp, npass, pass_off, o_read, o_bkt, o_meta, o_rank, ov_cap, d_ov_cur);
-    else
-        LAUNCH(c, "k_superkmers", k_superkmers<8>, dim3(grid), dim3(256), 0, nr, k1_chunk, c.d_bases, boff, good, c.NB, pb_lo, pb_hi, bcount, nbl_part, inv_nbl, d_part,
-               s_desc, spp, npass, pass_off, o_read, o_bkt, o_meta, o_rank, ov_cap, d_ov_cur);
-    W2_HIP(hipGetLastError());
-    return 0;
-}
-
-// ---- K1/K2: super-k-mer records of this rank's reads, grouped by bucket (descriptor pass, scan, scatter pass)
-// (pb_lo, pb_hi): this hash-range pass keeps the records of buckets [pb_lo, pb_hi) of nb only (MapReduceEngine.h:288-299); bucket numbers
-// in the outputs are relative to pb_lo, the n_parts owners divide the RANGE
-int count_partition(Ctx& c, uint32_t nb, uint32_t n_parts, uint32_t pb_lo, uint32_t pb_hi) {
-    if (pb_hi > nb || pb_lo >= pb_hi) { c.err = "partition: bad bucket range"; return W2RAP_E_ARG; }
-    const uint32_t nbr = pb_hi - pb_lo;                  // buckets of this pass
-    if (!c.quality_done) { c.err = "partition before quality_windows"; return W2RAP_E_STATE; }
-    hipStream_t st = c.stream;
-    const uint64_t n = c.n;
-    if (n >= (1ull << 32)) { c.err = "more than 2^32 reads on one GPU (32-bit read ids in the record descriptors)"; return W2RAP_E_LIMIT; }
-    c.NB = nb; c.slab_cap = 0;
-    if (c.d_bcount) c.release(c.d_bcount);
-    if (c.d_bbase) c.release(c.d_bbase);
-    if (c.d_recs) c.release(c.d_recs);
-    W2_ALLOC(c.d_bcount, uint32_t, nbr);
-    W2_ALLOC(c.d_bbase, uint64_t, (uint64_t)nbr + 1);
-    unsigned long long* d_ov_cur = nullptr;
-    W2_ALLOC(d_ov_cur, unsigned long long, 2);
-    // multi-GPU: k-mer instances destined to each of the n_parts owners (their solid sets are bounded by it)
-    unsigned long long* d_part = nullptr;
-    if (n_parts > 64 || (n_parts && nbr % n_parts)) { c.err = "partition: at most 64 parts, dividing the bucket count"; return W2RAP_E_LIMIT; }
-    if (n_parts) W2_ALLOC(d_part, unsigned long long, 64 * 64);
-    const uint32_t nbl_part = n_parts ? nbr / n_parts : 0, inv_nbl = nbl_part > 1 ? (uint32_t)((1ull << 32) / nbl_part) : 0;
-    // descriptor slots: spp per (read, pass of 128 k-mer positions).  A pass of a PE150 read cuts into ~4 records,
-    // 8 slots hold all but ~1 % of them; the surplus goes to the overflow list.  If even that list is too small the
-    // pass is repeated with twice the slots (128 cannot overflow).
-    uint32_t spp, npass;
-    k1_slots(c, &spp, &npass);
-    uint2* s_desc = nullptr; uint32_t *o_read = nullptr, *o_bkt = nullptr, *o_meta = nullptr, *o_rank = nullptr;
-    uint64_t ov_cap = n / 8 + 1024;
-    W2_ALLOC(o_read, uint32_t, ov_cap); W2_ALLOC(o_bkt, uint32_t, ov_cap); W2_ALLOC(o_meta, uint32_t, ov_cap); W2_ALLOC(o_rank, uint32_t, ov_cap);
-    uint64_t nslots = 0, nov = 0, npass_tot = 0;
-    uint64_t* pass_off = nullptr;
-    bool wave = false;
-    for (;;) {
-        wave = k1_wave(spp, npass);
-        if (wave && !pass_off) { W2_ALLOC(pass_off, uint64_t, n + 1); W2_TRY(k1_pass_offsets(c, n, c.d_good, pass_off, &npass_tot)); }
-        nslots = wave ? npass_tot * spp : n * npass * spp;
-        W2_ALLOC(s_desc, uint2, nslots);
-        W2_HIP(hipMemsetAsync(c.d_bcount, 0, (size_t)nbr * 4, st));
-        W2_HIP(hipMemsetAsync(d_ov_cur, 0, 16, st));
-        if (d_part) W2_HIP(hipMemsetAsync(d_part, 0, 64 * 64 * 8, st));
-        if (n) W2_TRY(launch_k1(c, n, c.d_boff, c.d_good, pb_lo, pb_hi, c.d_bcount, nbl_part, inv_nbl, d_part, s_desc, spp, npass, pass_off, o_read, o_bkt, o_meta, o_rank, ov_cap, d_ov_cur));
-        W2_TRY(exclusive_scan_u32_to_u64(c, c.d_bcount, c.d_bbase, nbr));
-        unsigned long long h_ov = 0;
-        W2_HIP(hipMemcpyAsync(&c.nrec, c.d_bbase + nbr, 8, hipMemcpyDeviceToHost, st));
-        W2_HIP(hipMemcpyAsync(&h_ov, d_ov_cur, 8, hipMemcpyDeviceToHost, st));
-        unsigned long long h_part[64 * 64];
-        if (d_part) W2_HIP(hipMemcpyAsync(h_part, d_part, sizeof(h_part), hipMemcpyDeviceToHost, st));
-        W2_HIP(hipStreamSynchronize(st));
-        if (d_part) for (unsigned g = 0; g < 64; ++g) { c.part_kmers[g] = 0; for (unsigned k = 0; k < 64; ++k) c.part_kmers[g] += h_part[k * 64 + g]; }
-        nov = h_ov;
-        if (nov <= ov_cap) break;
-        // the list was too small: its exact need is known now (records beyond rank 65535 of a heavy bucket do not depend on
-        // spp; with many more entries than reads the slots are too few as well)
-        c.release(s_desc);
-        if (nov > n && spp < 128) spp *= 2;
-        for (uint32_t* q : {o_read, o_bkt, o_meta, o_rank}) c.release(q);
-        ov_cap = nov + nov / 8 + 1024;
-        W2_ALLOC(o_read, uint32_t, ov_cap); W2_ALLOC(o_bkt, uint32_t, ov_cap); W2_ALLOC(o_meta, uint32_t, ov_cap); W2_ALLOC(o_rank, uint32_t, ov_cap);
-    }
-    W2_ALLOC(c.d_recs, uint32_t, c.nrec * REC_DWORDS);
-    if (c.nrec) {
-        uint64_t bases_bytes = 0;
-        W2_HIP(hipMemcpy(&bases_bytes, c.d_boff + n, 8, hipMemcpyDeviceToHost));
-        const uint64_t nthreads = nslots + nov;
-        if (wave)
-            LAUNCH(c, "k_scatter_records", k_scatter_records<true>, dim3((unsigned)((nthreads + 255) / 256)), dim3(256), 0, nslots, spp, pass_off, n, s_desc,
-                   nov, o_read, o_bkt, o_meta, o_rank, c.d_bases, c.d_boff, bases_bytes, c.d_bbase, c.d_recs, 0u, 0ull);
-        else
-        LAUNCH(c, "k_scatter_records", k_scatter_records<false>, dim3((unsigned)((nthreads + 255) / 256)), dim3(256), 0, nslots, npass * spp, nullptr, 0, s_desc,
-               nov, o_read, o_bkt, o_meta, o_rank, c.d_bases, c.d_boff, bases_bytes, c.d_bbase, c.d_recs, 0u, 0ull);
-        W2_HIP(hipGetLastError());
-    }
-    W2_HIP(hipStreamSynchronize(st));
-    if (pass_off) c.release(pass_off);
-    c.release(d_ov_cur); if (d_part) c.release(d_part); c.release(s_desc); c.release(o_read); c.release(o_bkt); c.release(o_meta); c.release(o_rank);
-    return 0;
-}
-
-// ---- K1/K2 in batches of reads (single GPU).  K1 is bound by instruction issue, K2 by device atomics and scattered stores:
-// batch k's records are scattered on the side stream while batch k+1 is being cut.  Every batch becomes one SEGMENT of
-// records (grouped by bucket, segments back to back) -- the layout K3 already consumes for the records of several source
-// ranks -- so nothing is merged: c.d_bcount is [n_batches][NB], c.d_recs the segments, *n_seg the number of batches.
-int count_partition_batched(Ctx& c, uint32_t nb, unsigned n_batches, unsigned* n_seg, uint32_t pb_lo, uint32_t pb_hi) {
-    const uint32_t nbl = pb_hi - pb_lo;                  // buckets of this pass: c.d_bcount is [n_batches][nbl]
-    if (!c.quality_done) { c.err = "partition before quality_windows"; return W2RAP_E_STATE; }
-    hipStream_t st = c.stream, st2 = c.stream2;
-    const uint64_t n = c.n;
-    if (n >= (1ull << 32)) { c.err = "more than 2^32 reads on one GPU (32-bit read ids in the record descriptors)"; return W2RAP_E_LIMIT; }
-    if (n_batches < 1) n_batches = 1; if (n_batches > 16) n_batches = 16;
-    if (n < (1u << 20) || !st2) n_batches = 1;
-    c.NB = nb; c.slab_cap = 0;
-    if (c.d_bcount) c.release(c.d_bcount);
-    if (c.d_bbase) { c.release(c.d_bbase); c.d_bbase = nullptr; }
-    if (c.d_recs) c.release(c.d_recs);
-    c.d_recs = nullptr;
-    W2_ALLOC(c.d_bcount, uint32_t, (uint64_t)n_batches * nbl);
-    uint64_t* d_bbase[2] = {nullptr, nullptr};
-    uint2* s_desc[2] = {nullptr, nullptr};
-    uint32_t *o_read[2] = {nullptr, nullptr}, *o_bkt[2] = {nullptr, nullptr}, *o_meta[2] = {nullptr, nullptr}, *o_rank[2] = {nullptr, nullptr};
-    unsigned long long* d_ov_cur = nullptr;
-    W2_ALLOC(d_ov_cur, unsigned long long, 2);
-    uint32_t spp, npass;
-    k1_slots(c, &spp, &npass);
-    // equal batches (W2RAP_LAST_BATCH < 1: a shorter last one, whose scatter pass is the one nothing hides -- measured in round 4: no difference)
-    const double last_frac = getenv("W2RAP_LAST_BATCH") ? std::min(1.0, std::max(0.1, atof(getenv("W2RAP_LAST_BATCH")))) : 1.0;
-    const uint64_t per_batch = n_batches > 1 ? (((uint64_t)((double)n / ((double)n_batches - 1.0 + last_frac)) + 2) & ~1ull) : ((n + 1) & ~1ull);
-    uint64_t ov_cap[2] = {per_batch / 8 + 1024, per_batch / 8 + 1024};
-    uint64_t slots_alloc[2] = {0, 0};
-    uint64_t* pass_off[2] = {nullptr, nullptr};                         // (k1_wave: per batch buffer, the batch it holds, its passes)
-    uint64_t pass_k[2] = {~0ull, ~0ull}, npass_tot[2] = {0, 0};
-    for (int b = 0; b < 2; ++b) {
-        W2_ALLOC(d_bbase[b], uint64_t, (uint64_t)nbl + 1);
-        W2_ALLOC(o_read[b], uint32_t, ov_cap[b]); W2_ALLOC(o_bkt[b], uint32_t, ov_cap[b]); W2_ALLOC(o_meta[b], uint32_t, ov_cap[b]);
-        W2_ALLOC(o_rank[b], uint32_t, ov_cap[b]);
-    }
-    uint64_t bases_bytes = 0;
-    if (n) W2_HIP(hipMemcpy(&bases_bytes, c.d_boff + n, 8, hipMemcpyDeviceToHost));
-    hipEvent_t ev_k2[16] = {};
-    uint64_t rec_cap = 0, seg_base = 0;
-    c.nrec = 0;
-    unsigned nseg = 0;
-    for (unsigned k = 0; k < n_batches; ++k) {
-        const uint64_t r0 = std::min<uint64_t>(n, k * per_batch), r1 = std::min<uint64_t>(n, r0 + per_batch), nr = r1 - r0;
-        const int b = k & 1;
-        uint32_t* bcount = c.d_bcount + (uint64_t)k * nbl;
-        if (k >= 2) W2_HIP(hipEventSynchronize(ev_k2[k - 2]));            // the scatter that read these double buffers is done
-        uint64_t nslots = 0, nov = 0, nrec_k = 0;
-        bool wave = false;
-        for (;;) {
-            wave = k1_wave(spp, npass);
-            if (wave && pass_k[b] != k) {
-                if (!pass_off[b]) W2_ALLOC(pass_off[b], uint64_t, per_batch + 1);
-                W2_TRY(k1_pass_offsets(c, nr, c.d_good + r0, pass_off[b], &npass_tot[b]));
-                pass_k[b] = k;
-            }
-            nslots = wave ? npass_tot[b] * spp : nr * npass * spp;
-            if (slots_alloc[b] < nslots) { if (s_desc[b]) c.release(s_desc[b]); W2_ALLOC(s_desc[b], uint2, nslots); slots_alloc[b] = nslots; }
-            W2_HIP(hipMemsetAsync(bcount, 0, (size_t)nbl * 4, st));
-            W2_HIP(hipMemsetAsync(d_ov_cur, 0, 16, st));
-            if (nr) W2_TRY(launch_k1(c, nr, c.d_boff + r0, c.d_good + r0, pb_lo, pb_hi, bcount, 0u, 0u, nullptr, s_desc[b], spp, npass, wave ? pass_off[b] : nullptr, o_read[b], o_bkt[b], o_meta[b], o_rank[b], ov_cap[b], d_ov_cur));
-            W2_TRY(exclusive_scan_u32_to_u64(c, bcount, d_bbase[b], nbl));
-            unsigned long long h_ov = 0;
-            W2_HIP(hipMemcpyAsync(&nrec_k, d_bbase[b] + nbl, 8, hipMemcpyDeviceToHost, st));
-            W2_HIP(hipMemcpyAsync(&h_ov, d_ov_cur, 8, hipMemcpyDeviceToHost, st));
-            W2_HIP(hipStreamSynchronize(st));
-            nov = h_ov;
-            if (nov <= ov_cap[b]) break;
-            // the list was too small: its exact need is known now (see count_partition); this batch's buffers are free to grow
-            if (nov > nr && spp < 128) spp *= 2;                           // (this and the later batches; earlier ones keep their slots)
-            for (uint32_t* q : {o_read[b], o_bkt[b], o_meta[b], o_rank[b]}) c.release(q);
-            ov_cap[b] = nov + nov / 8 + 1024;
-            W2_ALLOC(o_read[b], uint32_t, ov_cap[b]); W2_ALLOC(o_bkt[b], uint32_t, ov_cap[b]); W2_ALLOC(o_meta[b], uint32_t, ov_cap[b]);
-            W2_ALLOC(o_rank[b], uint32_t, ov_cap[b]);
-        }
-        // room for this segment: the first batch predicts the total (batches are equal samples of the reads)
-        if (seg_base + nrec_k > rec_cap) {
-            const uint64_t want = k == 0 ? (uint64_t)((double)nrec_k * ((double)n / (double)std::max<uint64_t>(nr, 1))) + nrec_k / 16 + (1u << 20) : (seg_base + nrec_k) * 2;
-            uint32_t* bigger = c.alloc<uint32_t>(want * REC_DWORDS);
-            if (!bigger) return W2RAP_E_HIP;
-            if (c.d_recs) {
-                W2_HIP(hipStreamSynchronize(st2));
-                W2_HIP(hipMemcpyAsync(bigger, c.d_recs, seg_base * REC_BYTES, hipMemcpyDeviceToDevice, st2));
-                W2_HIP(hipStreamSynchronize(st2));
-                c.release(c.d_recs);
-            }
-            c.d_recs = bigger; rec_cap = want;
-        }
-        hipStream_t sk = n_batches > 1 ? st2 : st;
-        if (nrec_k) {
-            const uint64_t nthreads = nslots + nov;
-            if (wave)
-                LAUNCH_ON(c, sk, "k_scatter_records", k_scatter_records<true>, dim3((unsigned)((nthreads + 255) / 256)), dim3(256), 0, nslots, spp, pass_off[b], nr, s_desc[b],
-                          nov, o_read[b], o_bkt[b], o_meta[b], o_rank[b], c.d_bases, c.d_boff + r0, bases_bytes, d_bbase[b], c.d_recs + seg_base * REC_DWORDS, 0u, 0ull);
-            else
-            LAUNCH_ON(c, sk, "k_scatter_records", k_scatter_records<false>, dim3((unsigned)((nthreads + 255) / 256)), dim3(256), 0, nslots, npass * spp, nullptr, 0, s_desc[b],
-                      nov, o_read[b], o_bkt[b], o_meta[b], o_rank[b], c.d_bases, c.d_boff + r0, bases_bytes, d_bbase[b], c.d_recs + seg_base * REC_DWORDS, 0u, 0ull);
-            W2_HIP(hipGetLastError());
-        }
-        W2_HIP(hipEventCreateWithFlags(&ev_k2[k], hipEventDisableTiming));
-        W2_HIP(hipEventRecord(ev_k2[k], sk));
-        seg_base += nrec_k;
-        nseg = k + 1;
-    }
-    for (unsigned k = 0; k < nseg; ++k) { W2_HIP(hipEventSynchronize(ev_k2[k])); (void)hipEventDestroy(ev_k2[k]); }
-    c.nrec = seg_base;
-    if (!c.d_recs) W2_ALLOC(c.d_recs, uint32_t, REC_DWORDS);
-    for (int b = 0; b < 2; ++b) {
-        c.release(d_bbase[b]); if (s_desc[b]) c.release(s_desc[b]); if (pass_off[b]) c.release(pass_off[b]);
-        c.release(o_read[b]); c.release(o_bkt[b]); c.release(o_meta[b]); c.release(o_rank[b]);
-    }
-    c.release(d_ov_cur);
-    *n_seg = nseg;
-    return 0;
-}
-
-// ---- K1 alone, records into bucket slabs (single GPU, one hash-range pass, lane route; NOTES.md section 19): bucket b owns records
-// [b * C, (b + 1) * C) of c.d_recs -- not zeroed, the counts bound every read --, the cutter stores a record where its rank atomic says, and
-// what it cannot store from its tail (a read's records beyond its staged slots, ranks >= C) goes through the overflow list: K2's list
-// branch puts the former into their slabs and the latter into an overflow segment behind the slabs (c.d_bbase: the scan of the buckets'
-// excess).  One launch over all reads, one host wait.  c.d_bcount: [nb]; the count reads two (start, count) segments per bucket.
-__global__ void __launch_bounds__(256) k_slab_excess(uint32_t nb, const uint32_t* __restrict__ bcount, uint32_t C, uint32_t* __restrict__ excess) {
-    const uint32_t b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b < nb) excess[b] = bcount[b] > C ? bcount[b] - C : 0u;
-}
-__global__ void __launch_bounds__(256) k_slab_segments(uint32_t nb, const uint32_t* __restrict__ bcount, uint32_t C, const uint64_t* __restrict__ ovbase,
-                                                        uint64_t* __restrict__ seg /* [2][nb] */) {
-    const uint32_t b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b >= nb) return;
-    const uint32_t n = bcount[b];
-    seg[b] = seg_pack((uint64_t)b * C, n < C ? n : C);
-    seg[(uint64_t)nb + b] = seg_pack((uint64_t)nb * C + ovbase[b], n > C ? n - C : 0u);
-}
-
-// records per slab: the resident tile of the shipped k_count_fp shape -- the buckets that overflow are the ones it defers anyway
-static constexpr uint32_t SLAB_CAP = 512;
-
-// whether this count takes the slab route, and its C (0: the scatter pass)
-static uint32_t slab_route(const Ctx& c, uint32_t nb, unsigned npass_hash) {
-    const char* sv = getenv("W2RAP_K1_SLABS");
-    if (sv && atoi(sv) == 0) return 0;
-    if (REC_DWORDS != 8 || npass_hash != 1 || !c.n || getenv("W2RAP_K1_ALIGN64")) return 0;
-    uint32_t spp, npass;
-    k1_slots(c, &spp, &npass);
-    if (!spp || k1_wave(spp, npass)) return 0;
-    uint32_t C = SLAB_CAP;
-    if (const char* t = getenv("W2RAP_TEST_SLAB_CAP")) { if (test_hook("W2RAP_TEST_SLAB_CAP")) C = (uint32_t)std::max(1, atoi(t)); }
-    // the slabs take no more than a quarter of the free HBM (the rule of auto_passes), and a segment word holds every record's number
-    size_t free_b = 0, total_b = 0;
-    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess || !free_b) return 0;
-    const double need = (double)nb * C * REC_BYTES + (double)c.M / 15.0 * REC_BYTES * 0.25;
-    if (need > (double)free_b / 4.0 || (double)nb * C + (double)c.M >= (double)(1ull << SEG_START_BITS)) return 0;
-    return C;
-}
-
-// The slab route pays for every record beyond its slab: the overflow list has ONE cursor word, and its atomics queue up behind each other
-// (~2 ns a listed record: 8.7 M of them -- 50 M reads of a genome with repeat families -- make K1 29 ms instead of 11.5, against 17.5 ms for
-// the scatter pass; the routes break even near reads / 18 such records).  So inputs of 2^20 reads and more are asked first: the old lane
-// kernel cuts the first 1/32 of the reads (0.4 ms at 50 M), and the records its buckets hold beyond C / 32, times 32, estimate the records
-// beyond the slabs.  The estimate runs high by about reads / 25 -- ordinary buckets near C, whose sampled counts scatter above C / 32 --, so
-// the limit is reads / 10 (SLAB_EXCESS_DIV): above it the scatter pass.  -> *est
-static constexpr uint32_t SLAB_EXCESS_DIV = 10;
-static constexpr uint32_t SLAB_SAMPLE = 32;
-static int slab_excess_estimate(Ctx& c, uint32_t nb, uint32_t C, uint64_t* est) {
-    hipStream_t st = c.stream;
-    uint32_t spp, npass;
-    k1_slots(c, &spp, &npass);
-    const uint64_t ns = c.n / SLAB_SAMPLE, lcap = ns / 8 + 1024;
-    c.NB = nb;
-    uint32_t *cnt = nullptr, *exc = nullptr, *o_read = nullptr, *o_bkt = nullptr, *o_meta = nullptr, *o_rank = nullptr;
-    uint64_t* scan = nullptr; uint2* s_desc = nullptr; unsigned long long* d_ov_cur = nullptr;
-    auto run = [&]() -> int {
-        W2_ALLOC(cnt, uint32_t, nb); W2_ALLOC(exc, uint32_t, nb); W2_ALLOC(scan, uint64_t, (uint64_t)nb + 1); W2_ALLOC(s_desc, uint2, ns * spp * npass);
-        W2_ALLOC(d_ov_cur, unsigned long long, 2);
-        W2_ALLOC(o_read, uint32_t, lcap); W2_ALLOC(o_bkt, uint32_t, lcap); W2_ALLOC(o_meta, uint32_t, lcap); W2_ALLOC(o_rank, uint32_t, lcap);
-        W2_HIP(hipMemsetAsync(cnt, 0, (size_t)nb * 4, st));
-        W2_HIP(hipMemsetAsync(d_ov_cur, 0, 16, st));
-        W2_TRY(launch_k1(c, ns, c.d_boff, c.d_good, 0, nb, cnt, 0u, 0u, nullptr, s_desc, spp, npass, nullptr, o_read, o_bkt, o_meta, o_rank, lcap, d_ov_cur));
-        LAUNCH(c, "k_slab_excess", k_slab_excess, dim3((nb + 255) / 256), dim3(256), 0, nb, cnt, std::max(1u, C / SLAB_SAMPLE), exc);
-        W2_HIP(hipGetLastError());
-        W2_TRY(exclusive_scan_u32_to_u64(c, exc, scan, nb));
-        uint64_t h = 0;
-        W2_HIP(hipMemcpyAsync(&h, scan + nb, 8, hipMemcpyDeviceToHost, st));
-        W2_HIP(hipStreamSynchronize(st));
-        *est = h * SLAB_SAMPLE;
-        return 0;
-    };
-    const int rc = run();
-    for (void* q : {(void*)cnt, (void*)exc, (void*)scan, (void*)s_desc, (void*)d_ov_cur, (void*)o_read, (void*)o_bkt, (void*)o_meta, (void*)o_rank}) if (q) c.release(q);
-    return rc;
-}
-
-// *refused: the overflow list of an input of 2^20 reads and more was too small after all (the estimate's sample was not like the rest): nothing
-// is kept, the caller takes the scatter pass -- a second cut of all reads costs more than that.  Smaller inputs are cut again into a list of
-// the exact size.
-int count_partition_slabs(Ctx& c, uint32_t nb, uint32_t C, bool* refused) {
-    *refused = false;
-    if (!c.quality_done) { c.err = "partition before quality_windows"; return W2RAP_E_STATE; }
-    hipStream_t st = c.stream;
-    const uint64_t n = c.n;
-    if (n >= (1ull << 32)) { c.err = "more than 2^32 reads on one GPU (32-bit read ids in the record descriptors)"; return W2RAP_E_LIMIT; }
-    c.NB = nb;
-    if (c.d_bcount) c.release(c.d_bcount);
-    if (c.d_bbase) c.release(c.d_bbase);
-    if (c.d_recs) c.release(c.d_recs);
-    c.d_bcount = nullptr; c.d_bbase = nullptr; c.d_recs = nullptr;
-    uint32_t* d_excess = nullptr;
-    unsigned long long* d_ov_cur = nullptr;
-    uint32_t *o_read = nullptr, *o_bkt = nullptr, *o_meta = nullptr, *o_rank = nullptr;
-    auto drop_lists = [&]() { for (uint32_t** q : {&o_read, &o_bkt, &o_meta, &o_rank}) if (*q) { c.release(*q); *q = nullptr; } };
-    auto run = [&]() -> int {
-        W2_ALLOC(c.d_bcount, uint32_t, nb);
-        W2_ALLOC(c.d_bbase, uint64_t, (uint64_t)nb + 1);
-        W2_ALLOC(d_excess, uint32_t, nb);
-        W2_ALLOC(d_ov_cur, unsigned long long, 2);
-        uint32_t spp, npass;
-        k1_slots(c, &spp, &npass);
-        uint64_t bases_bytes = 0;
-        W2_HIP(hipMemcpy(&bases_bytes, c.d_boff + n, 8, hipMemcpyDeviceToHost));
-        // every record of the overflow segment is a listed one: a list that held them all bounds the segment
-        uint64_t ov_cap = n / 8 + 1024, nov = 0, n_excess = 0;
-        const dim3 bgrid((nb + 255) / 256);
-        for (;;) {
-            W2_ALLOC(o_read, uint32_t, ov_cap); W2_ALLOC(o_bkt, uint32_t, ov_cap); W2_ALLOC(o_meta, uint32_t, ov_cap); W2_ALLOC(o_rank, uint32_t, ov_cap);
-            W2_ALLOC(c.d_recs, uint32_t, ((uint64_t)nb * C + ov_cap) * REC_DWORDS);
-            W2_HIP(hipMemsetAsync(c.d_bcount, 0, (size_t)nb * 4, st));
-            W2_HIP(hipMemsetAsync(d_ov_cur, 0, 16, st));
-            W2_TRY(launch_k1(c, n, c.d_boff, c.d_good, 0, nb, c.d_bcount, 0u, 0u, nullptr, nullptr, spp, npass, nullptr, o_read, o_bkt, o_meta, o_rank, ov_cap, d_ov_cur,
-                             c.d_recs, C, bases_bytes));
-            LAUNCH(c, "k_slab_excess", k_slab_excess, bgrid, dim3(256), 0, nb, c.d_bcount, C, d_excess);
-            W2_HIP(hipGetLastError());
-            W2_TRY(exclusive_scan_u32_to_u64(c, d_excess, c.d_bbase, nb));
-            unsigned long long h_ov = 0;
-            W2_HIP(hipMemcpyAsync(&n_excess, c.d_bbase + nb, 8, hipMemcpyDeviceToHost, st));
-            W2_HIP(hipMemcpyAsync(&h_ov, d_ov_cur, 8, hipMemcpyDeviceToHost, st));
-            W2_HIP(hipStreamSynchronize(st));
-            nov = h_ov;
-            if (nov <= ov_cap) break;
-            // the list was too small: its exact need is known now (the cut does not depend on the list)
-            drop_lists();
-            c.release(c.d_recs); c.d_recs = nullptr;
-            if (n >= (1ull << 20)) { *refused = true; return 0; }
-            ov_cap = nov + nov / 8 + 1024;
-        }
-        if (n_excess > nov) { c.err = "partition: more records beyond the slabs than the overflow list holds"; return W2RAP_E_STATE; }
-        if (nov) {
-            LAUNCH(c, "k_scatter_records", k_scatter_records<false>, dim3((unsigned)((nov + 255) / 256)), dim3(256), 0, 0ull, npass * spp, nullptr, 0, nullptr,
-                   nov, o_read, o_bkt, o_meta, o_rank, c.d_bases, c.d_boff, bases_bytes, c.d_bbase, c.d_recs, C, (uint64_t)nb);
-            W2_HIP(hipGetLastError());
-        }
-        W2_HIP(hipStreamSynchronize(st));
-        if (getenv("W2RAP_TRACE"))
-            fprintf(stderr, "[w2rap] partition slabs: %u buckets x %u records, %llu listed records, %llu beyond their slab\n", nb, C, (unsigned long long)nov,
-                    (unsigned long long)n_excess);
-        c.slab_cap = C;
-        c.nrec = (uint64_t)nb * C + n_excess;                // (the extent of c.d_recs in use)
-        return 0;
-    };
-    const int rc = run();
-    drop_lists();
-    if (d_excess) c.release(d_excess);
-    if (d_ov_cur) c.release(d_ov_cur);
-    return rc;
-}
-
 // ---- K3: count `nbl` buckets whose records arrive in `nseg` segments (one per source rank), each
 // segment grouped by bucket; d_counts[s*nbl + b] = records of bucket b in segment s, d_recs = the
 // segments back to back.  total_kmers bounds the solid set (S <= kmers / min_freq).
@@ -2546,8 +1580,7 @@ int count_buckets_launch(Ctx& c, uint32_t min_freq, uint32_t nbl, uint32_t nseg,
     c.cs_packed = c.slab_cap != 0;
     if (c.cs_packed) {                                   // bucket slabs + overflow segment: (start | count) words, count_partition_slabs
         if (nseg != 2 || d_counts != c.d_bcount || !c.d_bbase) { c.err = "count_records: the slab layout has two segments"; return W2RAP_E_STATE; }
-        LAUNCH(c, "k_slab_segments", k_slab_segments, dim3((nbl + 255) / 256), dim3(256), 0, nbl, d_counts, c.slab_cap, c.d_bbase, d_off);
-        W2_HIP(hipGetLastError());
+        W2_TRY(slab_segments(c, nbl, d_counts, d_off));
     } else
     W2_TRY(exclusive_scan_u32_to_u64(c, d_counts, d_off, nflat));
     // A later pass of a multi-pass count (c.pass > 0) appends to the solid arrays, the chunk list, the counters and the histogram of
@@ -3046,14 +2079,14 @@ int phase_count(Ctx& c, uint32_t min_qual, uint32_t min_freq) {
         uint64_t ask_from = 1ull << 20;                  // (W2RAP_TEST_SLAB_SAMPLE_MIN: a test hook, so that a small input is asked too)
         if (const char* t = getenv("W2RAP_TEST_SLAB_SAMPLE_MIN")) { if (test_hook("W2RAP_TEST_SLAB_SAMPLE_MIN")) ask_from = (uint64_t)std::max(64ll, atoll(t)); }
         if (slabs && c.n >= ask_from) {                  // (an input whose buckets pass their slabs by much is faster on the scatter pass)
-            uint64_t est = 0;
-            W2_TRY(slab_excess_estimate(c, NB, slabs, &est));
-            if (trace) fprintf(stderr, "[w2rap] partition: ~%llu records beyond slabs of %u (limit %llu)\n", (unsigned long long)est, slabs, (unsigned long long)(c.n / SLAB_EXCESS_DIV));
-            if (est > c.n / SLAB_EXCESS_DIV) slabs = 0;
+            uint64_t est = 0, limit = 0;
+            W2_TRY(slab_excess_estimate(c, NB, slabs, &est, &limit));
+            if (trace) fprintf(stderr, "[w2rap] partition: ~%llu records beyond slabs of %u (limit %llu)\n", (unsigned long long)est, slabs, (unsigned long long)limit);
+            if (est > limit) slabs = 0;
         }
-        if (slabs) {
+        if (slabs) {                                     // (an asked input whose list overflows after all is not cut a second time into slabs)
             bool refused = false;
-            W2_TRY(count_partition_slabs(c, NB, slabs, &refused));
+            W2_TRY(count_partition_slabs(c, NB, slabs, ask_from, &refused));
             if (refused) slabs = 0; else nseg = 2;
         }
         if (!slabs) W2_TRY(count_partition_batched(c, NB, bv ? (unsigned)atoi(bv) : 4, &nseg, lo, hi));
