@@ -780,14 +780,19 @@ __device__ inline FpInst fp_fetch(const uint32_t* tile, unsigned rec, unsigned i
 // instance as extracted in MSB-first words (what a verification compares a reference's reverse complement with)
 struct FpKey { uint64_t hi, lo; bool rc; uint32_t f[4]; };
 __device__ inline FpKey fp_key(const FpInst& x) {
-    auto rev2_32 = [](uint32_t v) { v = __brev(v); return ((v & 0x55555555u) << 1) | ((v >> 1) & 0x55555555u); };
-    const uint32_t a0 = rev2_32(x.s[0]), b0 = rev2_32(x.s[1]), a1 = rev2_32(x.s[2]), b1 = rev2_32(x.s[3]);
+    // The bases of a word in reverse order are its bit reverse with the two bits of every base swapped back: two shifts and one bit-field
+    // insert under 0xAAAAAAAA.  The upper word of a half (its last 14 bases, then 4 zero bits) takes the `>> 4` into those two shifts; the
+    // lower word (bases 14 .. 29 of the half) is cut out of the half by one funnel shift BEFORE the reverse, so no 28-bit word is reversed
+    // on its own and masked (9 instructions a half instead of 11)
+    // (the insert is written out: the compiler, knowing the zero bits of a shifted word, narrows the two masks and then needs AND + AND-OR)
+    auto pick = [](uint32_t odd, uint32_t even) { uint32_t r; asm("v_bfi_b32 %0, %1, %2, %3" : "=v"(r) : "s"(0xAAAAAAAAu), "v"(odd), "v"(even)); return r; };
+    const uint32_t r0 = __brev(x.s[0]), r1 = __brev(__funnelshift_r(x.s[0], x.s[1], 28)), r2 = __brev(x.s[2]), r3 = __brev(__funnelshift_r(x.s[2], x.s[3], 28));
     FpKey k;
-    k.f[0] = a0 >> 4; k.f[1] = __funnelshift_r(b0, a0, 4); k.f[2] = a1 >> 4; k.f[3] = __funnelshift_r(b1, a1, 4);
+    k.f[0] = pick(r0 >> 3, r0 >> 5); k.f[1] = pick(r1 << 1, r1 >> 1); k.f[2] = pick(r2 >> 3, r2 >> 5); k.f[3] = pick(r3 << 1, r3 >> 1);
     // reverse complement = complemented LSB-first halves, swapped
     const uint64_t khi_f = ((uint64_t)k.f[0] << 32) | k.f[1], klo_f = ((uint64_t)k.f[2] << 32) | k.f[3];
     const uint64_t khi_r = ((uint64_t)(~x.s[3] & 0x0FFFFFFFu) << 32) | (uint32_t)~x.s[2], klo_r = ((uint64_t)(~x.s[1] & 0x0FFFFFFFu) << 32) | (uint32_t)~x.s[0];
-    k.rc = khi_r != khi_f ? khi_r < khi_f : klo_r < klo_f;
+    k.rc = (khi_r < khi_f) | ((khi_r == khi_f) & (klo_r < klo_f));       // (three compares and two mask operations, no selects)
     k.hi = k.rc ? khi_r : khi_f; k.lo = k.rc ? klo_r : klo_f;
     return k;
 }
@@ -805,29 +810,50 @@ __device__ inline bool fp_same(const uint32_t* tile, unsigned ref, const FpInst&
 }
 
 // Record dedup: is record `rec` of the tile byte-identical to a record that entered the table before it?  Then that record's copy count
-// goes up by one and this one is not flattened.  Equality is decided by the eight dwords, never by the hash.  The table holds record + 1
-// (0 = free), linear probing; it is at most half full, so a probe sequence always ends.
+// goes up by one and this one is not flattened.  Equality is decided by the eight dwords, never by the hash.  A table word is
+// tag << 10 | record + 1 (0 = free; TILE < 1023), the tag being the bits of the record's hash below those that choose the slot; linear
+// probing, and the table is at most half full, so a probe sequence always ends.  A lane reads a holder's record only where the tags are
+// equal under `tag_mask10` (the kernel's tag mask << 10: all tag bits in production; 0, a test hook, makes every held slot a tag match --
+// the form before the tag); any other held slot costs one XOR / AND / compare.  With the tile at the records' own stride a record is two
+// 16-byte LDS reads; the odd stride of -DW2RAP_FP_TS9 keeps dword reads.
 template <unsigned DT, unsigned LOG_DT>
-__device__ inline bool fp_dedup(const uint32_t* tile, uint32_t* dtab, uint32_t* dmul, unsigned rec) {
-    const uint32_t* wp = tile + rec * FP_TS;
-    uint32_t w[REC_DWORDS];
+__device__ inline bool fp_dedup(const uint32_t* tile, uint32_t* dtab, uint32_t* dmul, unsigned rec, uint32_t tag_mask10) {
+    static_assert(REC_DWORDS == 8, "fp_dedup: a record is two 16-byte reads");
+    constexpr unsigned TAG_BITS = 32 - LOG_DT < 22 ? 32 - LOG_DT : 22;       // hash bits that the slot index does not use, as far as the word has room
+    auto rec_load = [&](unsigned r, uint32_t (&v)[REC_DWORDS]) {
+        const uint32_t* p = tile + r * FP_TS;
+        if constexpr (FP_TS == REC_DWORDS) {
+            const u32x4 lo = *reinterpret_cast<const u32x4*>(p), hi = *reinterpret_cast<const u32x4*>(p + 4);
 #pragma unroll
-    for (unsigned i = 0; i < REC_DWORDS; ++i) w[i] = wp[i];
+            for (unsigned i = 0; i < 4; ++i) { v[i] = lo[i]; v[4 + i] = hi[i]; }
+        } else {
+#pragma unroll
+            for (unsigned i = 0; i < REC_DWORDS; ++i) v[i] = p[i];
+        }
+    };
+    uint32_t w[REC_DWORDS];
+    rec_load(rec, w);
     auto rotl = [](uint32_t v, unsigned n) { return __funnelshift_l(v, v, n); };
     uint32_t x = w[0], y = w[REC_DWORDS - 1];
 #pragma unroll
     for (unsigned i = 1; i + 1 < REC_DWORDS; i += 2) { x = rotl(x, 9) + w[i]; y = rotl(y, 13) ^ w[i + 1]; }
     uint32_t h = (x + rotl(y, 16)) * 0x9E3779B1u;
     h ^= h >> 15;
-    unsigned s = (h * 0x85EBCA6Bu) >> (32 - LOG_DT);
+    h *= 0x85EBCA6Bu;
+    unsigned s = h >> (32 - LOG_DT);
+    const uint32_t word = ((h & ((1u << TAG_BITS) - 1u)) << 10) | (rec + 1u);
     for (;;) {
         uint32_t a = ld32(&dtab[s]);
-        if (a == 0u) { a = atomicCAS(&dtab[s], 0u, rec + 1u); if (a == 0u) return false; }
-        const uint32_t* hp = tile + (a - 1u) * FP_TS;
-        uint32_t d = 0;
+        if (a == 0u) { a = atomicCAS(&dtab[s], 0u, word); if (a == 0u) return false; }
+        if (((a ^ word) & tag_mask10) == 0u) {
+            const unsigned holder = (a & 1023u) - 1u;
+            uint32_t hw[REC_DWORDS];
+            rec_load(holder, hw);
+            uint32_t d = 0;
 #pragma unroll
-        for (unsigned i = 0; i < REC_DWORDS; ++i) d |= hp[i] ^ w[i];
-        if (d == 0u) { atomicAdd(&dmul[(a - 1u) >> 1], 1u << (16u * ((a - 1u) & 1u))); return true; }
+            for (unsigned i = 0; i < REC_DWORDS; ++i) d |= hw[i] ^ w[i];
+            if (d == 0u) { atomicAdd(&dmul[holder >> 1], 1u << (16u * (holder & 1u))); return true; }
+        }
         s = (s + 1u) & (DT - 1u);
     }
 }
@@ -841,10 +867,11 @@ __device__ inline bool fp_dedup(const uint32_t* tile, uint32_t* dtab, uint32_t* 
     uint32_t* __restrict__ chunk_cnt, uint32_t chunk_cap, uint32_t* __restrict__ defer /* [0] count, [2..] deferred bucket ids */, uint32_t defer_cap, \
     uint32_t fill_limit /* <= LIMIT */, uint32_t solid_limit /* <= SC: smaller values are test hooks */,                                               \
     uint8_t* __restrict__ sctx, uint8_t* __restrict__ unres, uint32_t* __restrict__ nbr /* all three or none: the chunk-local adjacency prune         \
-    (k_prune_local's outputs) done here, while the table still holds every distinct k-mer of the bucket with its count */
+    (k_prune_local's outputs) done here, while the table still holds every distinct k-mer of the bucket with its count */,                            \
+    uint32_t dedup_tag_mask /* record dedup: the tag bits that two table words are compared in; all ones, fewer are test hooks (see fp_dedup) */
 #define W2_FP_ARGS                                                                                                                                    \
     nb, b_lo, b_hi, nseg, roff, recs, min_freq, queue, shi, slo, scc, solid_cap, counters, ghist, chunk_start, chunk_cnt, chunk_cap, defer, defer_cap, \
-    fill_limit, solid_limit, sctx, unres, nbr
+    fill_limit, solid_limit, sctx, unres, nbr, dedup_tag_mask
 template <unsigned THREADS, unsigned TILE_, unsigned SC_, bool DEDUP>
 __device__ __forceinline__ void count_fp_body(W2_FP_PARAMS) {
     constexpr unsigned long long SMASK = (1ull << 40) - 1;
@@ -870,7 +897,7 @@ __device__ __forceinline__ void count_fp_body(W2_FP_PARAMS) {
     uint32_t* stk = misc + 16;                                     // (class, P) pairs of a bucket counted in hash classes, depth <= 18
     uint16_t* olist = reinterpret_cast<uint16_t*>(stk + 40);       // [OCAP] the occupied slots of the bucket being emitted
     uint32_t* rinfo = reinterpret_cast<uint32_t*>(olist + C::OCAP); // [TILE] DEDUP: the j-th distinct record of the bucket | its copies << 16
-    uint32_t* dtab = stcc;                                         // [DT] DEDUP, S1 .. flatten: record + 1 by content hash (0 = free) ...
+    uint32_t* dtab = stcc;                                         // [DT] DEDUP, S1 .. flatten: hash tag << 10 | record + 1 by content hash (0 = free) ...
     uint32_t* dmul = stcc + C::DT;                                 // [(TILE + 1) / 2] ... and the further copies of each record, 16 bits each
     const unsigned tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
 
@@ -933,12 +960,15 @@ __device__ __forceinline__ void count_fp_body(W2_FP_PARAMS) {
         for (unsigned i = 0; i < 7; ++i) bnd[i] = (i + 1 < nseg && nseg <= 8) ? dp[i + 1] : 0xFFFFFFFFu;
         for (uint32_t d = C::PFREC * REC_DWORDS + tid; d < dend; d += THREADS) tile[fp_tile_index(d)] = stream_dword(q, dp, bnd, d);
     };
-    // context bits of an instance (KMerContext: bits 0..3 successors, 4..7 predecessors); see k_count_buckets
-    auto ctx_of = [&](const FpInst& x, bool rc, uint32_t hdr, unsigned idx) -> unsigned {
-        const unsigned rnk_ = (hdr & 63u) + 1u;
-        const bool hasp = (idx > 0) | ((hdr & 64u) != 0), hass = (idx + 1 < rnk_) | ((hdr & 128u) != 0);
-        const unsigned shl_p = (x.e0 & 3u) ^ (rc ? 3u : 4u), shl_s = ((x.e3 >> 26) & 3u) ^ (rc ? 7u : 0u);
-        return (hasp ? 1u << shl_p : 0u) | (hass ? 1u << shl_s : 0u);
+    // context bits of an instance (KMerContext: bits 0..3 successors, 4..7 predecessors; see k_count_buckets), at their place in a count word
+    // (bits 31:24).  On the forward strand the left flank b is predecessor bit 4 + b and the right flank successor bit b; on the reverse
+    // strand they are successor 3 - b and predecessor 4 + (3 - b): the forward byte with its bits in reverse order, so ONE bit reverse of the
+    // word makes it, at bit 24 already.  A k-mer has a predecessor unless it is the record's first (idx 0) without header flag 64, a successor
+    // unless it is the last (idx = header bits 5:0) without flag 128: idx <= 63, so both are one compare each
+    auto ctx24_of = [&](const FpInst& x, bool rc, uint32_t hdr, unsigned idx) -> uint32_t {
+        const bool hasp = ((hdr & 64u) | idx) != 0u, hass = (hdr & 0xBFu) > idx;
+        const uint32_t fwd = (hasp ? 16u << (x.e0 & 3u) : 0u) | (hass ? 1u << ((x.e3 >> 26) & 3u) : 0u);
+        return rc ? __brev(fwd) : fwd << 24;
     };
 
     // ---- init
@@ -973,7 +1003,7 @@ __device__ __forceinline__ void count_fp_body(W2_FP_PARAMS) {
         const unsigned ref = qv & 0xFFFFu, rec = ref >> 6, idx = ref & 63u;
         const FpInst x = fp_fetch(tile, rec, idx);
         const FpKey k = fp_key(x);
-        const unsigned ctx = ctx_of(x, k.rc, tile[rec * FP_TS], idx);
+        const uint32_t ctx24 = ctx24_of(x, k.rc, tile[rec * FP_TS], idx);
         const uint32_t h1 = fp_hash(k), tag = (h1 >> 5) & 0xFFFFu;
         unsigned s = (h1 >> (33 - C::LOG_CAP)) << 1;                  // the probe sequence starts at an EVEN slot: the window loop looks at a pair
         bool isnew = false;
@@ -990,7 +1020,7 @@ __device__ __forceinline__ void count_fp_body(W2_FP_PARAMS) {
                 s = (s + 1) & (CAP - 1);
                 if (--budget <= 0) break;
             }
-            if (ok) { atomicAdd(&cc[s], DEDUP ? qv >> 16 : 1u); atomicOr(&cc[s], ctx << 24); }
+            if (ok) { atomicAdd(&cc[s], DEDUP ? qv >> 16 : 1u); atomicOr(&cc[s], ctx24); }
             else st32(&misc[FP_OVF], 1u);
         }
         qn -= cnt;
@@ -1029,7 +1059,7 @@ __device__ __forceinline__ void count_fp_body(W2_FP_PARAMS) {
             const unsigned rec = r * THREADS + tid;
             bool dup = false;
             if (DEDUP && !skip && r * THREADS + (tid & ~63u) < nrec)             // (wave-uniform: waves without a record pass)
-                if (rec < nrec) dup = fp_dedup<C::DT, C::LOG_DT>(tile, dtab, dmul, rec);
+                if (rec < nrec) dup = fp_dedup<C::DT, C::LOG_DT>(tile, dtab, dmul, rec, dedup_tag_mask << 10);
             nkr[r] = (!skip && rec < nrec && !dup) ? (tile[rec * FP_TS] & 63u) + 1u : 0u;
             inclr[r] = wave_scan64(DEDUP ? nkr[r] | (nkr[r] ? 1u << 16 : 0u) : nkr[r]);
             if (lane == 63) wtot[r * NW + wv] = inclr[r];
@@ -1092,7 +1122,7 @@ __device__ __forceinline__ void count_fp_body(W2_FP_PARAMS) {
                 // ---- B: cut out the k-mer, canonicalise, hash, look at its home slot
                 const FpInst x = fp_fetch(tile, rec, idx);
                 const FpKey k = fp_key(x);
-                const unsigned ctx = ctx_of(x, k.rc, hdr, idx);
+                const uint32_t ctx24 = ctx24_of(x, k.rc, hdr, idx);
                 const uint32_t h1 = fp_hash(k), tag = (h1 >> 5) & 0xFFFFu;
                 const unsigned s0 = (h1 >> (33 - C::LOG_CAP)) << 1;
                 const unsigned myref = (rec << 6) | idx;
@@ -1105,7 +1135,11 @@ __device__ __forceinline__ void count_fp_body(W2_FP_PARAMS) {
                 const bool second = !m0 & (m1 | ((a0 != EMPTY) & (a1 == EMPTY)));        // act on the second slot: it matches, or it is the first free one
                 const uint32_t a = second ? a1 : a0;
                 const unsigned s = s0 + (second ? 1u : 0u);
-                const bool mine = active & (((h1 >> 2) & (P - 1)) == cls);                 // (a bucket counted in hash classes: this pass's class only)
+                bool mine = active;
+                if (P != 1u) {                                                             // (a bucket counted in hash classes: this pass's class only)
+                    asm volatile("; hash-class pass");                                     // P is wave-uniform: a scalar branch, not three predicated VALU instructions
+                    mine &= ((h1 >> 2) & (P - 1)) == cls;
+                }
                 const bool tagm = mine & (m0 | m1);
                 const bool hit = tagm & fp_same(tile, tagm ? (a & 0xFFFFu) : myref, x, k);
                 const bool want = mine & !tagm & (a == EMPTY);
@@ -1113,7 +1147,7 @@ __device__ __forceinline__ void count_fp_body(W2_FP_PARAMS) {
                 const bool won = want & (old == EMPTY);
                 const bool done = hit | won;
                 atomicAdd(&cc[s], done ? (DEDUP ? inf >> 16 : 1u) : 0u);
-                atomicOr(&cc[s], done ? ctx << 24 : 0u);
+                atomicOr(&cc[s], done ? ctx24 : 0u);
                 const bool parked = mine & !done;
                 unsigned nnew = (unsigned)__builtin_popcountll(__ballot(won));
                 {
@@ -1302,10 +1336,16 @@ __device__ __forceinline__ void count_fp_body(W2_FP_PARAMS) {
 }
 template <unsigned THREADS, unsigned MINW, unsigned TILE_, unsigned SC_>
 __global__ void __launch_bounds__(THREADS, MINW) k_count_fp(W2_FP_PARAMS) { count_fp_body<THREADS, TILE_, SC_, false>(W2_FP_ARGS); }
+// k_count_fp with the record dedup stage behind barrier S1 (fp_dedup: a table of tagged record ids, a record read as two 16-byte words, the
+// eight-dword compare only where the tags are equal) in front of the same window loop, whose lanes then stand for `copies` equal records.
+// The window loop, per window of 64 k-mers and wavefront, is 176 VALU / 70 SALU / 19 LDS instructions in the ISA of <512, 4, 512, 1024> while
+// no bucket is counted in hash classes (NOTES.md section 20: the class test behind a scalar branch, the reversal in fp_key, the context bits
+// by one bit reverse, the strand compare without selects).
 // The dedup stage must not take the kernel past 120 VGPRs: a wavefront is given registers in steps of 8, and k_table_insert finds room beside
 // two resident 512-thread blocks of this kernel only while 4 x its allocation stays below the SIMD's 512 (round 4: at 128 it ran in the gaps,
 // 16 -> 33 ms).  Left alone the scheduler uses whatever occupancy 4 allows (124); the body needs 116.  (The attribute counts registers in
-// halves of the unified file: 60 = 120 VGPRs.  The 1024-thread shape with eight waves per SIMD keeps its bound of 64.)
+// halves of the unified file: 60 = 120 VGPRs.  The 1024-thread shape with eight waves per SIMD keeps its bound of 64.)  As it stands:
+// 120 VGPRs, nothing spilled, no scratch; k_count_fp 117 / 0 / 0.
 template <unsigned THREADS, unsigned MINW, unsigned TILE_, unsigned SC_>
 __global__ void __attribute__((amdgpu_num_vgpr(60))) __launch_bounds__(THREADS, MINW) k_count_fp_dedup(W2_FP_PARAMS) { count_fp_body<THREADS, TILE_, SC_, true>(W2_FP_ARGS); }
 #undef W2_FP_PARAMS
@@ -1670,9 +1710,13 @@ int count_buckets_launch_slice(Ctx& c, unsigned k) {
         uint32_t fill_limit = fp_limit, solid_limit = fp_sc;
         if (const char* t = getenv("W2RAP_TEST_FP_LIMIT")) { if (test_hook("W2RAP_TEST_FP_LIMIT")) fill_limit = std::min<uint32_t>(fill_limit, (uint32_t)std::max(1, atoi(t))); }
         if (const char* t = getenv("W2RAP_TEST_FP_SC")) { if (test_hook("W2RAP_TEST_FP_SC")) solid_limit = std::min<uint32_t>(solid_limit, (uint32_t)std::max(1, atoi(t))); }
+        // (test hook: 0 makes every held slot of the record table a tag match, 1 half of them -- the content compare has to tell the records apart)
+        uint32_t dedup_tag_mask = 0xFFFFFFFFu;
+        if (const char* t = getenv("W2RAP_TEST_DEDUP_TAG_MASK")) { if (test_hook("W2RAP_TEST_DEDUP_TAG_MASK")) dedup_tag_mask = (uint32_t)strtoul(t, nullptr, 0); }
         LAUNCH(c, "k_count_fp", kern, dim3(grid ? grid : 1), dim3(threads), lds, nb_arg, b_lo, b_hi, nseg, c.cs_off, c.cs_recs, c.min_freq, d_queue,
                c.d_shi, c.d_slo, c.d_scc, c.solid_cap, d_cnt + 4, d_cnt + 8, c.d_chunk_start, c.d_chunk_cnt, c.cs_chunk_cap, c.cs_defer, nbl, fill_limit, solid_limit,
-               c.fused_prune ? c.d_sctx : (uint8_t*)nullptr, c.fused_prune ? c.d_unres : (uint8_t*)nullptr, c.fused_prune ? (uint32_t*)c.d_nbr : (uint32_t*)nullptr);
+               c.fused_prune ? c.d_sctx : (uint8_t*)nullptr, c.fused_prune ? c.d_unres : (uint8_t*)nullptr, c.fused_prune ? (uint32_t*)c.d_nbr : (uint32_t*)nullptr,
+               dedup_tag_mask);
         W2_HIP(hipGetLastError());
         if (k + 1 == NS && c.fused_prune) W2_HIP(hipMemcpyAsync(c.h_pinned + 20, d_cnt + 4, 8, hipMemcpyDeviceToHost, st));      // chunks so far: the list kernel's come behind
         if (k + 1 == NS) {
