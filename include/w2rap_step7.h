@@ -4,8 +4,9 @@
  *
  *   LINES   GetTol, GetLineLengths, GetLineNpairs        src/paths/long/large/Lines.cc:329-355, Lines.h:74-117
  *   LINKS   MakeGaps up to the accepted gaps             src/paths/long/large/MakeGaps.cc:25-427
+ *   FILES   DumpLineFiles: a.lines.fasta, .efasta, .src   src/paths/long/large/Lines.cc:680-798 (w2rap_step7_line_files, below)
  * What stays the reference's: the graph edit and the truncation of the paths behind the accepted gaps (MakeGaps.cc:429-493),
- * GAP_CLEANUP, FinalFiles, and FindLines -- the lines come in as data (the .fin.lines file, formats.read_lines).
+ * GAP_CLEANUP, the rest of FinalFiles, and FindLines -- the lines come in as data (the .fin.lines file, formats.read_lines).
  *
  * One call on host arrays; plain pointers and sizes; never throws; returns 0 or a W2RAP_E_* code (w2rap_step2.h) with a message in
  * `err`.  There is no CPU fallback (W2RAP_E_NO_DEVICE).
@@ -169,6 +170,110 @@ void w2rap_step7_free(w2rap_step7_out* out);
 
 /* per-kernel device time of the last w2rap_step7_links in this process: "kernel_name total_ms launches\n" lines; returns the bytes needed */
 size_t w2rap_step7_profile(char* buf, size_t len);
+
+/* ---- FILES: DumpLineFiles (Lines.cc:680-798), the texts of a.lines.fasta, a.lines.efasta and a.lines.src -------------------------------
+ *
+ * One call on host arrays, as above.  HIP kernels for gfx950 (the k7f_* kernels of csrc/step7_fasta.hip, the library's scans and sort):
+ *   the paths index (`invert`, the kernels Step 5's opening builds it with), the vote (k7f_vote: a wavefront per voted cell, lanes over
+ *   the index entries of e and of inv[e], the cov row in LDS up to W2RAP_STEP7_VOTE_ROW paths per cell and in global memory beyond),
+ *   the shares (k7f_share: a wavefront per cell of two or more paths), the layout (k7f_path_len, k7f_cell_size, k7f_pieces: a thread
+ *   per path of a cell turns it into pieces, scans place every piece and line) and the writer (k7f_write: 16 output bytes per thread).
+ * On the HOST: the skip rule and the circular kinds (line-sized), `best` of every voted cell, a.lines.src, and the last argument checks.
+ *
+ * DEPENDENCY ON THE C++ LIBRARY.  best = the first id after ReverseSortSync(cov, ids) (VecUtilities.h:349-405), which is std::sort on the
+ *   index vector 0 .. n-1 with cov[i] > cov[j].  std::sort is not stable: among tied maxima the lowest index wins up to 16 paths
+ *   (insertion sort) and need not from 17 (introsort's partition).  The host code of this call makes the same std::sort call on the same
+ *   vector, so it gives the reference's tie order exactly when it is linked against the libstdc++ the reference was built with; the
+ *   recorded runs (tests/golden/refruns/step7_ff_*) were made with the one this library is built against.  The votes themselves (cov)
+ *   are counted on the device and do not depend on it.
+ *
+ * Semantics, in the reference's order.
+ *   1. Line i is printed unless i > 0 and first_edge(line i-1) == inv[last_edge(line i)], first_edge = front()[0][0], last_edge =
+ *      back()[0][0]: the rule reads the order AS GIVEN (after SortLines a line is followed by its mirror image).
+ *   2. circular kind 1: more than one cell and first_edge == last_edge, the last cell is not written; kind 2: one cell and the edge's two
+ *      vertices are one.  Either adds " circular" to both headers.
+ *   3. A cell of ONE EMPTY path is a gap: 100 N in both texts.  Every other path is the Cat of its edges (the first whole, each further
+ *      one from base K-1), shortened by K-1 bases unless the cell is the line's last; the cut may run back over several edges.
+ *   4. The vote, odd cells only (best = 0 elsewhere), e = the first edge of the cell in front.  For every entry of the paths index of e
+ *      and every position m of that read with p[m] == e, path r matches when p[m+1+s] == x[r][s] for every s still inside the read; the
+ *      occurrence counts for r when it is the ONLY match.  The index lists a read once per occurrence and every entry visits every
+ *      occurrence: a read through e twice counts four times.  The same over the index of inv[e], each read reversed and mapped by inv.
+ *   5. efasta of a cell: one path its bases; several: left_share { middles joined by , } right_share, both shares against path 0 after
+ *      the cut, right_share <= len(path 0) - left_share (efasta/EfastaTools.cc:35-71).
+ *   6. Text: ">line_<i>[ circular]\n" / ">flattened_line_<i>[ circular]\n", i the index in the input, then rows of 80 characters, no empty
+ *      last row, a body of 0 characters the header alone (efasta::Print).
+ *   7. a.lines.src: every line, skipped ones too: cells joined by ",", an even cell its first edge, an odd one {{path},{path}}.
+ *
+ * W2RAP_E_ARG before the device is touched: K outside [16, 640]; an unknown flag; sizes beyond 32-bit ids; null arrays; edge_byte_off that
+ * does not start at 0 or does not match edge_len (packed edges shorter than edge_len says); edge_len < K; adjacency, inv and path faults
+ * as above; the line checks of w2rap_step7_links (w2rap_step7_in) but for "belongs to no line" (no tol is read here); an EVEN cell whose
+ * first path is empty (the reference reads [0] of it); an empty path in a cell of two or more (the reference reads e[0] of an empty
+ * vector); a path shorter than K-1 bases where the cut applies -- behind edge_len >= K no path with an edge is, so this guards the
+ * kernels only.  These three are refused in every line, printed or not.
+ * W2RAP_E_LIMIT: a line of 2^31 K-mers or more; a line body of 2^32 characters or more in either text (Print counts in unsigned).
+ */
+#define W2RAP_STEP7_FASTA   1u
+#define W2RAP_STEP7_EFASTA  2u
+#define W2RAP_STEP7_SRC     4u
+#define W2RAP_STEP7_VOTE_ROW 64      /* paths of a cell whose votes a wavefront keeps in LDS; larger cells count in global memory */
+#define W2RAP_STEP7_GAP_N    100     /* N per gap cell */
+
+typedef struct w2rap_step7_fasta_in {
+    int32_t  K;
+    uint64_t n_edge_objs;
+    const uint8_t*  edge_packed;     /* as w2rap_gfa_in: each object ceil(len/4) bytes, base i at bits 2*(i%4) of byte i/4 */
+    const uint64_t* edge_byte_off;   /* [n_edge_objs+1] */
+    const uint32_t* edge_len;        /* [n_edge_objs] bases, >= K */
+    uint64_t n_vertices;
+    const uint64_t* from_off;        /* the adjacency, inv and the read paths as w2rap_step7_in (n_paths may be odd: no mates here) */
+    const int32_t*  from_v;
+    const int32_t*  from_e;
+    const uint64_t* to_off;
+    const int32_t*  to_e;
+    const int32_t*  inv;
+    uint64_t n_paths;
+    const uint64_t* path_off;
+    const int32_t*  path_edges;
+    uint64_t n_lines;                /* the lines as w2rap_step7_in */
+    const uint64_t* line_off;
+    const uint64_t* cell_off;
+    const uint64_t* lpath_off;
+    const int32_t*  line_edges;
+} w2rap_step7_fasta_in;
+
+typedef struct w2rap_step7_fasta_params {
+    int32_t  device;
+    uint32_t flags;                  /* any of W2RAP_STEP7_FASTA / EFASTA / SRC, 0 = all three */
+} w2rap_step7_fasta_params;
+
+/* library-allocated HOST memory, free with w2rap_step7_line_files_free.  A part that is not asked for launches no kernel of its own and
+ * leaves its pointers null, its counters and its time zero: the vote runs for FASTA, the shares for EFASTA; printed and the line
+ * counters come back with any part */
+typedef struct w2rap_step7_fasta_out {
+    char*    fasta;  uint64_t fasta_len;         /* a.lines.fasta */
+    char*    efasta; uint64_t efasta_len;        /* a.lines.efasta */
+    char*    src;    uint64_t src_len;           /* a.lines.src */
+    uint8_t*  printed;               /* [n_lines] */
+    int32_t*  best;                  /* [n_cells]  FASTA: the path flattened, 0 where no vote is taken */
+    uint32_t* cov;                   /* [n_lpaths] FASTA: the votes of every path of every voted cell (cell_off is its CSR), 0 elsewhere */
+    uint32_t* left_share;            /* [n_cells]  EFASTA: of the written cells of two or more paths, 0 elsewhere */
+    uint32_t* right_share;           /* [n_cells] */
+    uint64_t n_printed, n_skipped, n_circular1, n_circular2;     /* lines (circular: of the printed) */
+    uint64_t n_gap_cells;            /* written cells of one empty path */
+    uint64_t n_cells_voted;          /* written odd cells that are no gap (cells of one path included) */
+    uint64_t n_entries;              /* index entries visited, of e and of inv[e] over all voted cells */
+    uint64_t n_occurrences;          /* positions with p[m] == e */
+    uint64_t n_match_one, n_match_none, n_match_several;         /* of those: exactly one path matches (a vote), none, several */
+    uint64_t n_cells_tied;           /* voted cells whose largest vote is shared by two or more paths */
+    uint64_t n_cells_wide;           /* voted cells of more than W2RAP_STEP7_VOTE_ROW paths (no LDS row) */
+    uint64_t n_pieces_fasta, n_pieces_efasta;                    /* pieces of the layout (those of no characters included) */
+    float ms_vote, ms_share, ms_layout, ms_write;                /* device time per part, milliseconds (ms_vote: the index included) */
+} w2rap_step7_fasta_out;
+
+int  w2rap_step7_line_files(const w2rap_step7_fasta_in* in, const w2rap_step7_fasta_params* params, w2rap_step7_fasta_out* out, char* err, size_t errlen);
+void w2rap_step7_line_files_free(w2rap_step7_fasta_out* out);
+/* per-kernel device time of the last w2rap_step7_line_files in this process, as w2rap_step7_profile */
+size_t w2rap_step7_line_files_profile(char* buf, size_t len);
 
 #ifdef __cplusplus
 }

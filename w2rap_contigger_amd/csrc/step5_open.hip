@@ -47,23 +47,6 @@ __device__ inline void count_block(const bool (&x)[N], unsigned long long* word)
     if (threadIdx.x < N && sum[threadIdx.x]) atomicAdd(&word[threadIdx.x], (unsigned long long)sum[threadIdx.x]);
 }
 
-// off[e] = the first j with keys[j] >> shift >= e, for e in [0, E]: the CSR offsets of a sorted key array whose edge sits above `shift`
-__global__ __launch_bounds__(256) void k5o_lower_bound(uint64_t E, const uint64_t* __restrict__ keys, uint64_t n, unsigned shift, uint64_t* __restrict__ off) {
-    const uint64_t e = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-    if (e > E) return;
-    uint64_t lo = 0, hi = n;                                   // the answer lies in [lo, hi]
-    while (lo < hi) { const uint64_t mid = (lo + hi) >> 1; if ((keys[mid] >> shift) < e) lo = mid + 1; else hi = mid; }
-    off[e] = lo;
-}
-
-// ---- INDEX ---------------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k5o_index_emit(uint64_t n, const uint64_t* __restrict__ poff, const int32_t* __restrict__ pe,
-                                                      uint64_t* __restrict__ keys, uint32_t* __restrict__ vals) {
-    const uint64_t r = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-    if (r >= n) return;
-    for (uint64_t k = poff[r]; k < poff[r + 1]; ++k) { keys[k] = (uint32_t)pe[k]; vals[k] = (uint32_t)r; }
-}
-
 // ---- LINKS ---------------------------------------------------------------------------------------------------------------------
 // Unsat.cc:152-160.  flag[p] = the pair goes on to the search
 __global__ __launch_bounds__(256) void k5o_pair_filter(uint64_t NP, const uint64_t* __restrict__ poff, const int32_t* __restrict__ pe, const int32_t* __restrict__ inv,
@@ -226,10 +209,7 @@ int open_index(Ctx& c, const w2rap_step5_open_in& in, const Dev& d, w2rap_step5_
     out.n_index = N;
     if (!N) { out.ms_index = t.stop(); W2_TRY(host_zeros(c, &out.index_off, E + 1)); return host_zeros(c, &out.index_read, 0); }
     uint64_t *d_keys = nullptr, *d_off = nullptr; uint32_t* d_vals = nullptr;
-    W2_ALLOC(d_keys, uint64_t, N + 1); W2_ALLOC(d_vals, uint32_t, N + 1); W2_ALLOC(d_off, uint64_t, E + 2);
-    LAUNCH(c, "k5o_index_emit", k5o_index_emit, dim3(grid5(n)), dim3(256), 0, n, (const uint64_t*)d.poff, (const int32_t*)d.pe, d_keys, d_vals);
-    W2_TRY(sort_pairs_u64(c, d_keys, d_vals, N, 0, (int)bits_for(E)));
-    LAUNCH(c, "k5o_lower_bound", k5o_lower_bound, dim3(grid5(E + 1)), dim3(256), 0, E, (const uint64_t*)d_keys, N, 0u, d_off);
+    W2_TRY(paths_index(c, d.poff, d.pe, n, N, E, &d_keys, &d_vals, &d_off));
     out.ms_index = t.stop();
     W2_TRY(dl(c, &out.index_off, (const uint64_t*)d_off, E + 1));
     W2_TRY(dl(c, &out.index_read, (const uint32_t*)d_vals, N));

@@ -7,8 +7,12 @@ edge, the length of every line in K-mers and the number of read pairs that touch
 read pair, the links that the bounded search does not find close, the per-link filters and the set rules.  The graph edit behind that
 list, GAP_CLEANUP, FinalFiles and FindLines stay the reference's; the lines come in as data (formats.read_lines).
 
+`line_files` is DumpLineFiles (Lines.cc:680-798): the texts of a.lines.fasta, a.lines.efasta and a.lines.src; `sort_lines` is SortLines
+(Lines.cc:664-678) and `stats_text` the `stats` file of FinalFiles (FinalFiles.cc:73-104), both from the llens of `line_stats`.
+
 ``python -m w2rap_contigger_amd.step7 DIR PREFIX`` reads DIR/PREFIX.contig.hbv, .contig.paths, .fin.lines and .fin.lines.npairs and
-writes the accepted gaps as text.  The HIP library is the only implementation (no CPU fallback)."""
+writes the accepted gaps as text; with ``--line_files LINES_FILE`` it reads DIR/PREFIX.contig.hbv/.paths and that lines file and writes
+a.lines.fasta, a.lines.efasta, a.lines.src and stats into DIR.  The HIP library is the only implementation (no CPU fallback)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -67,6 +71,11 @@ def lib():
         L.w2rap_step7_free.restype = None
         L.w2rap_step7_profile.argtypes = [C.c_char_p, C.c_size_t]
         L.w2rap_step7_profile.restype = C.c_size_t
+        L.w2rap_step7_line_files.argtypes = [C.POINTER(FastaIn), C.POINTER(FastaParams), C.POINTER(FastaOut), C.c_char_p, C.c_size_t]
+        L.w2rap_step7_line_files_free.argtypes = [C.POINTER(FastaOut)]
+        L.w2rap_step7_line_files_free.restype = None
+        L.w2rap_step7_line_files_profile.argtypes = [C.c_char_p, C.c_size_t]
+        L.w2rap_step7_line_files_profile.restype = C.c_size_t
         _ready = True
     return L
 
@@ -143,17 +152,151 @@ def find_gaps(hbv: F.HBV, inv, paths, lines: F.Lines, npairs=None, min_line=5000
     return run(hbv, inv, paths, lines, parts=("lines", "links") if npairs is None else ("links",), npairs=npairs, min_line=min_line, min_link_count=min_link_count, device=device)
 
 
-def profile():
-    """-> {kernel name: (total ms, launches)} of the last call in this process"""
+def profile(line_files=False):
+    """-> {kernel name: (total ms, launches)} of the last find_gaps / line_stats (line_files: of the last line_files) in this process"""
     L = lib()
-    n = L.w2rap_step7_profile(None, 0)
+    f = L.w2rap_step7_line_files_profile if line_files else L.w2rap_step7_profile
+    n = f(None, 0)
     buf = C.create_string_buffer(int(n) + 16)
-    L.w2rap_step7_profile(buf, len(buf))
+    f(buf, len(buf))
     out = {}
     for line in buf.value.decode().splitlines():
         name, ms, k = line.rsplit(" ", 2)
         out[name] = (float(ms), int(k))
     return out
+
+
+# ---------------------------------------------------------------------------------------------------------------- the line files
+FILE_PARTS = {"fasta": 1, "efasta": 2, "src": 4}            # W2RAP_STEP7_FASTA / EFASTA / SRC
+VOTE_ROW = 64                                               # W2RAP_STEP7_VOTE_ROW
+GAP_N = 100                                                 # W2RAP_STEP7_GAP_N
+
+
+class FastaIn(C.Structure):
+    _fields_ = [("K", C.c_int32), ("n_edge_objs", C.c_uint64), ("edge_packed", C.c_void_p), ("edge_byte_off", C.c_void_p), ("edge_len", C.c_void_p),
+                ("n_vertices", C.c_uint64), ("from_off", C.c_void_p), ("from_v", C.c_void_p), ("from_e", C.c_void_p), ("to_off", C.c_void_p), ("to_e", C.c_void_p),
+                ("inv", C.c_void_p), ("n_paths", C.c_uint64), ("path_off", C.c_void_p), ("path_edges", C.c_void_p),
+                ("n_lines", C.c_uint64), ("line_off", C.c_void_p), ("cell_off", C.c_void_p), ("lpath_off", C.c_void_p), ("line_edges", C.c_void_p)]
+
+
+class FastaParams(C.Structure):
+    _fields_ = [("device", C.c_int32), ("flags", C.c_uint32)]
+
+
+FASTA_TEXTS = ("fasta", "efasta", "src")
+FASTA_ARRAYS = {"printed": (np.uint8, "NL"), "best": (np.int32, "NC"), "cov": (np.uint32, "NLP"), "left_share": (np.uint32, "NC"), "right_share": (np.uint32, "NC")}
+FASTA_COUNTERS = ("n_printed", "n_skipped", "n_circular1", "n_circular2", "n_gap_cells", "n_cells_voted", "n_entries", "n_occurrences", "n_match_one", "n_match_none",
+                  "n_match_several", "n_cells_tied", "n_cells_wide", "n_pieces_fasta", "n_pieces_efasta")
+FASTA_PHASES = ("ms_vote", "ms_share", "ms_layout", "ms_write")
+
+
+class FastaOut(C.Structure):
+    _fields_ = ([x for k in FASTA_TEXTS for x in ((k, C.c_void_p), (k + "_len", C.c_uint64))] + [(k, C.c_void_p) for k in FASTA_ARRAYS] +
+                [(k, C.c_uint64) for k in FASTA_COUNTERS] + [(k, C.c_float) for k in FASTA_PHASES])
+
+
+@dataclass
+class LineFiles:
+    """the texts of include/w2rap_step7.h's w2rap_step7_fasta_out as bytes (None: the part was not asked for), its arrays by name, the
+    counters and the device times"""
+    fasta: bytes
+    efasta: bytes
+    src: bytes
+    arrays: dict
+    counters: dict
+    ms: dict
+
+    def __getattr__(self, k):
+        try:
+            return self.__dict__["arrays"][k]
+        except KeyError:
+            raise AttributeError(k)
+
+    def write(self, dir):
+        """a.lines.fasta, a.lines.efasta and a.lines.src into dir, those that were asked for"""
+        import os
+        for k in FASTA_TEXTS:
+            if getattr(self, k) is not None:
+                with open(os.path.join(dir, f"a.lines.{k}"), "wb") as f:
+                    f.write(getattr(self, k))
+
+
+def line_files(hbv: F.HBV, inv, paths, lines: F.Lines, parts=FASTA_TEXTS, device=0, flags=None) -> LineFiles:
+    """w2rap_step7_line_files: DumpLineFiles on the graph with its bases, its involution, the read paths (as for `run`) and the lines.
+    flags overrides parts (the tests of the argument checks)"""
+    L = lib()
+    if flags is None:
+        flags = 0
+        for p in parts:
+            if p not in FILE_PARTS:
+                raise ValueError(f"unknown part {p!r}: one of {sorted(FILE_PARTS)}")
+            flags |= FILE_PARTS[p]
+        if not flags:
+            raise ValueError("no part asked for")
+    keep = [np.ascontiguousarray(hbv.edge_packed, np.uint8), np.ascontiguousarray(hbv.edge_byte_off, np.uint64), np.ascontiguousarray(hbv.edge_len, np.uint32),
+            np.ascontiguousarray(hbv.from_off, np.uint64), np.ascontiguousarray(hbv.from_v, np.int32), np.ascontiguousarray(hbv.from_e, np.int32),
+            np.ascontiguousarray(hbv.to_off, np.uint64), np.ascontiguousarray(hbv.to_e, np.int32), np.ascontiguousarray(inv, np.int32),
+            np.ascontiguousarray(paths[1], np.uint64), np.ascontiguousarray(paths[2], np.int32),
+            np.ascontiguousarray(lines.line_off, np.uint64), np.ascontiguousarray(lines.cell_off, np.uint64), np.ascontiguousarray(lines.lpath_off, np.uint64),
+            np.ascontiguousarray(lines.edges, np.int32)]
+    E = len(keep[2])
+    if len(keep[8]) != E or len(keep[1]) != E + 1:
+        raise ValueError("inv must have one entry per edge object, edge_byte_off one more")
+    if len(keep[9]) < 1 or len(keep[11]) < 1 or len(keep[12]) != int(keep[11][-1]) + 1 or len(keep[13]) != int(keep[12][-1]) + 1:
+        raise ValueError("path_off, line_off, cell_off and lpath_off must each have one entry more than what they divide")
+    NL, NC, NLP = len(keep[11]) - 1, len(keep[12]) - 1, len(keep[13]) - 1
+    p = lambda a: _ptr(a) if len(a) else None
+    i = FastaIn(hbv.K, E, p(keep[0]), p(keep[1]), p(keep[2]), hbv.n_vertices, p(keep[3]), p(keep[4]), p(keep[5]), p(keep[6]), p(keep[7]), p(keep[8]),
+                len(keep[9]) - 1, p(keep[9]), p(keep[10]), NL, p(keep[11]), p(keep[12]), p(keep[13]), p(keep[14]))
+    prm = FastaParams(device, flags)
+    o = FastaOut()
+    err = C.create_string_buffer(1024)
+    rc = L.w2rap_step7_line_files(C.byref(i), C.byref(prm), C.byref(o), err, 1024)
+    if rc:
+        raise Step2Error(rc, err.value.decode(errors="replace"))
+    try:
+        size = {"NL": NL, "NC": NC, "NLP": NLP}
+        texts = {k: (C.string_at(getattr(o, k), int(getattr(o, k + "_len"))) if getattr(o, k) else None) for k in FASTA_TEXTS}
+        arrays = {k: (_np_from(getattr(o, k), dt, size[n]) if getattr(o, k) else None) for k, (dt, n) in FASTA_ARRAYS.items()}
+        return LineFiles(texts["fasta"], texts["efasta"], texts["src"], arrays, {k: int(getattr(o, k)) for k in FASTA_COUNTERS}, {k: float(getattr(o, k)) for k in FASTA_PHASES})
+    finally:
+        L.w2rap_step7_line_files_free(C.byref(o))
+
+
+def sort_lines(hbv: F.HBV, inv, lines: F.Lines, paths=None, device=0) -> F.Lines:
+    """SortLines (Lines.cc:664-678): the lines ordered by (-llens, min(F, inv[B]), F), F and B the first and the last edge of a line --
+    the key of two different lines differs (F is the first edge of one line only), so the order does not depend on the sort.  llens comes
+    from the LINES kernels (line_stats); the sort and the permutation of the nested offsets are line-sized and run here"""
+    if paths is None:
+        paths = (np.zeros(0, np.int32), np.zeros(1, np.uint64), np.zeros(0, np.int32))
+    llens = line_stats(hbv, inv, paths, lines, device=device).llens
+    nested, inv = lines.nested(), np.asarray(inv)
+    key = lambda i: (-int(llens[i]), min(nested[i][0][0][0], int(inv[nested[i][-1][0][0]])), nested[i][0][0][0])
+    return F.Lines.from_nested([nested[i] for i in sorted(range(len(nested)), key=key)])
+
+
+def _commas(x: int) -> str:
+    return f"{x:,}"
+
+
+def stats_text(llens, K, prefix) -> str:
+    """the `stats` file of FinalFiles (FinalFiles.cc:73-104): LineN50 over the lines of 1000 K-mers or more with K-1 added (N50 of
+    math/Functions.cc:300-342 on the ascending lengths: the first length at which the running sum reaches half, the mean with the next
+    one where it lands on half exactly), and the totals of the lines of 1, 10 and 100 thousand K-mers or more, each halved"""
+    llens = [int(x) for x in llens]
+    lens = sorted(x + K - 1 for x in llens if x >= 1000)
+    n50, total, half = 0, sum(lens), 0
+    for i, x in enumerate(lens):
+        half += x
+        if 2 * half == total and i < len(lens) - 1:
+            n50 = (x + lens[i + 1]) // 2
+            break
+        if 2 * half >= total:
+            n50 = x
+            break
+    tot = [sum(x for x in llens if x >= m) // 2 for m in (1000, 10000, 100000)]
+    return (f"# {prefix} assembly statistics\n\nN50: {_commas(n50)}\ntotal bases in 1 kb+ sequences: {_commas(tot[0])}\n"
+            f"total bases in 10 kb+ sequences: {_commas(tot[1])}\ntotal bases in 100 kb+ sequences: {_commas(tot[2])}\n")
 
 
 def involution(hbv: F.HBV) -> np.ndarray:
@@ -184,10 +327,19 @@ def main(argv=None):
     ap.add_argument("--min_line", type=int, default=5000); ap.add_argument("--min_link_count", type=int, default=3)
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("-o", "--out", default=None, help="the text file to write (default DIR/PREFIX.gaps.txt)")
+    ap.add_argument("--line_files", metavar="LINES_FILE", default=None, help="write a.lines.fasta, a.lines.efasta, a.lines.src and stats into DIR from this lines file instead")
     a = ap.parse_args(argv)
     stem = os.path.join(a.dir, a.prefix)
     hbv = F.read_hbv(stem + ".contig.hbv")
     paths = F.read_paths(stem + ".contig.paths")
+    if a.line_files:
+        lines, inv = F.read_lines(a.line_files), involution(hbv)
+        res = line_files(hbv, inv, paths, lines, device=a.device)
+        res.write(a.dir)
+        with open(os.path.join(a.dir, "stats"), "w") as f:
+            f.write(stats_text(line_stats(hbv, inv, paths, lines, device=a.device).llens, hbv.K, a.prefix))
+        print(f"{res.counters['n_printed']} lines printed, {res.counters['n_skipped']} skipped, {res.counters['n_cells_voted']} cells voted -> {a.dir}/a.lines.fasta, .efasta, .src, stats")
+        return 0
     lines = F.read_lines(stem + ".fin.lines")
     npairs = F.read_int_vec(stem + ".fin.lines.npairs")
     res = find_gaps(hbv, involution(hbv), paths, lines, npairs=npairs, min_line=a.min_line, min_link_count=a.min_link_count, device=a.device)
