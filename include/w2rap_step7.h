@@ -5,8 +5,9 @@
  *   LINES   GetTol, GetLineLengths, GetLineNpairs        src/paths/long/large/Lines.cc:329-355, Lines.h:74-117
  *   LINKS   MakeGaps up to the accepted gaps             src/paths/long/large/MakeGaps.cc:25-427
  *   FILES   DumpLineFiles: a.lines.fasta, .efasta, .src   src/paths/long/large/Lines.cc:680-798 (w2rap_step7_line_files, below)
+ *   COVER   ComputeCoverage, CNIntegerFraction: .covs, .lines.stats  src/paths/long/large/Lines.cc:442-624 (w2rap_step7_coverage, below)
  * What stays the reference's: the graph edit and the truncation of the paths behind the accepted gaps (MakeGaps.cc:429-493),
- * GAP_CLEANUP, the rest of FinalFiles, and FindLines -- the lines come in as data (the .fin.lines file, formats.read_lines).
+ * GAP_CLEANUP, the edge report and the GFA of FinalFiles, and FindLines -- the lines come in as data (the .fin.lines file, formats.read_lines).
  *
  * One call on host arrays; plain pointers and sizes; never throws; returns 0 or a W2RAP_E_* code (w2rap_step2.h) with a message in
  * `err`.  There is no CPU fallback (W2RAP_E_NO_DEVICE).
@@ -274,6 +275,171 @@ int  w2rap_step7_line_files(const w2rap_step7_fasta_in* in, const w2rap_step7_fa
 void w2rap_step7_line_files_free(w2rap_step7_fasta_out* out);
 /* per-kernel device time of the last w2rap_step7_line_files in this process, as w2rap_step7_profile */
 size_t w2rap_step7_line_files_profile(char* buf, size_t len);
+
+/* ---- COVERAGE: ComputeCoverage (Lines.cc:442-624), what .covs, .lines.npairs and .lines.stats hang on, and CNIntegerFraction -------------
+ *
+ * FinalFiles.cc:40-50 calls it in Step 7 and w2rap-contigger.cc:528-536 in Step 6, where CNIntegerFraction (GapToyTools5.cc:1520-1538) turns
+ * it into the `CN fraction good = ...` line.  ONE sample (subsam_starts = {0}): the reference's main never has more than one.
+ *
+ * What runs where.  HIP kernels for gfx950:
+ *   npairs, llens          the LINES kernels of w2rap_step7_links (k7_path_len, k7_line_stats, k7_pair_lines), unchanged, where they lie
+ *   the paths index        k5o_index_emit, the radix sort, k5o_lower_bound (step5_runs.h); built only when a group or a long edge needs it
+ *   distinct pairs         of a GROUP of edges = the distinct read / 2 over the index rows of every e of the group and of every inv[e] (Pids,
+ *                          Lines.cc:390-404): k7c_row_len (a thread per (group edge, pass)), a scan, k7c_emit (a thread per index entry: key
+ *                          group << pbits | pid), ONE stable radix sort on bits_for(groups) + bits_for(pairs) bits, head flags and their scan
+ *                          (k5_heads), k5o_lower_bound for the groups' first keys, k7c_group_count (differences of the scanned flags).  No
+ *                          atomic on a shared address.  The cell groups (one per (in, out) class, Lines.cc:591-604) go through it first, the long
+ *                          edges (one edge each, :619-624) in a second round, because the long-edge rule reads what the cell rule left; they take the
+ *                          sort-free form described at the end of this text unless the sorted one is asked for.
+ *   the E-sized rules      k7c_line_pos (a thread per line: the loop position of the last even cell that names an edge as its first, atomicMax
+ *                          per edge), k7c_cell_pos (a thread per edge of a z: the last group), k7c_edge_cov (a thread per edge: line rule, then
+ *                          cell rule, and whether the long-edge rule is due), k7c_edge_long (the long-edge rule, the counts of CNIntegerFraction)
+ * On the HOST (csrc/step7_peak.h, plain C++): covl, the candidates, their sort, mass, PeakFinder::FindPeaks and CN1PeakFinder::FindPeak,
+ *   and the grouping of every cell's paths (io, ins, outs, pi, the upper median, z): line- or cell-sized and sequential in meaning.
+ *
+ * Semantics, in the reference's order.
+ *   1. npairs, llens as part LINES.  covl[l] = double(npairs[l]) / double(llens[l]).
+ *   2. Candidates: llens >= min(10000, max_len / 2) and covl > 0, sorted by covl (equal coverages by line id here, in no stated order in the
+ *      reference: mass, and so base_cov, do not depend on it).  mass[i] = the llens of the contiguous window around i whose ends are found with
+ *      covx[i] - covx[j] > 0.08 * covx[i] going down and covx[j] - covx[i] > 0.08 * covx[i] going up, in double, as written.
+ *   3. base_cov = CN1PeakFinder::FindPeak(covx, mass): peaks are the first maximum of their 21 neighbours (so none below 21 candidates),
+ *      not below max / 10000 (integer), with upper_bound windows of +-5% that do not touch either end of the data and hold 10 points on
+ *      each side, the maximum of their window, and 1.2 x the deeper of the two troughs not above them; plateaus are centred; peaks above
+ *      5 x the largest-mass peak go; one peak: it; none: the candidate of the largest mass (the first of equals); several: every peak is
+ *      scored as CN1 (the half step for all but the first, then 2x .. 5x, each within 10%), the best score that uses the largest peak wins, a
+ *      tie only for a diploid half-step peak of under a tenth of the mass.  At the end the larger of the first two chosen peaks decides: the
+ *      second, halved, when it is larger.  No candidate: base_cov = 0, and every later quotient is what IEEE gives (inf or NaN).
+ *   4. Line rule: for every line of llens >= 1000, every even cell j: cov[lines[l][j][0][0]] = float(covl[l] / base_cov).
+ *   5. Cell rule: every odd cell with a non-empty first path, whose paths' (first, last) pairs, firsts and lasts are equally many and at
+ *      least 2: per class of (first, last), len = the UPPER median of its paths' K-mers (v[n / 2]); len >= 1000: c = double(distinct pairs of
+ *      the class's edges) / double(len), and cov[z] = float(c / base_cov) for every edge z that every path of the class holds.
+ *   6. Long-edge rule: every edge with !(cov >= 0) (NaN is undefined: Def() is cov_ >= 0) and Kmers >= 1000:
+ *      cov = float(double(distinct pairs of e) / double(Kmers(e)) / base_cov).
+ *   Later writes win: a later cell over an earlier one, the cell rule over the line rule; rule[e] = the rule that wrote last
+ *   (W2RAP_STEP7_RULE_*).  There is ONE rounding to float, at Set.
+ *   7. CNIntegerFraction(frac, min_edge_size): over the edges of min_edge_size BASES or more with cov >= 0: int_cov = int(double(cov) + 0.5)
+ *      (a cov of 2^31 or more -- inf with base_cov 0 -- is the reference's undefined behaviour; here int_cov saturates), good when
+ *      |int_cov - cov| <= frac in double.  cn_fraction = double(good) / double(counted): NaN when nothing is counted.
+ *
+ * W2RAP_E_ARG before the device is touched: K outside [16, 640]; an unknown flag; negative or NaN frac, negative min_edge_size; sizes beyond
+ * 32-bit ids; an odd n_paths; null arrays; NO LINES (the reference dereferences the end of an empty vector); edge_len < K; inv that is no
+ * involution; path and line faults as w2rap_step7_links (an edge out of range, an even number of cells, an edge object in no line, ...); an
+ * even cell whose first path is empty.  W2RAP_E_LIMIT: a line of 2^31 K-mers or more.
+ * A cell that holds an empty path behind its first one (the reference reads front() of it) forms no group and counts as n_cells_empty.
+ *
+ * WHAT IS PINNED BY WHAT.  Recorded runs of the reference's own main (tests/golden/refruns/step7_cov_*, `--from_step 7`, at 1 thread and at 4):
+ *   .covs bit for bit, .lines.stats byte for byte and .lines.npairs for lone contigs below 21 candidates (the largest mass), 20 and 22
+ *   candidates, one peak of 80 lines (a single peak), two peaks of 120 lines with and without a far outlier (scored, the second halved), a line
+ *   below min_len, no pairs at all and pairs on a short line only (base_cov 0: NaN and inf), bubbles of 999 / 1,000 / 1,001 K-mers (the cell rule
+ *   on either side of 1000), classes of two and of four parallel paths (the upper median), a shared first edge of 1,000 and of 999 K-mers (the
+ *   long-edge rule on either side), reads with both mates on one edge, on e and inv[e], through e twice, with an unplaced mate.  Step-6 runs
+ *   (step7_cn_*) of the three Step-4 fixtures and of a hand-staged input of eight isolated contigs: the `CN fraction good` line, a `-nan` among them.
+ *   On the MODEL only (tests/step7_cov_model.py, a loop-for-loop restatement, and literal outcomes derived by hand): the overwrite order of
+ *   hand-written lines, a cell named twice, e and inv[e] in one group, an edge that is its own inverse (and the odd candidate count it gives:
+ *   21), index rows of 0 .. 257 entries, 1 .. 257 groups, a group of 20 edges, gap cells, the prefilter at 5x (no record reaches it), frac and
+ *   min_edge_size other than the defaults.  The diploid tie of the scoring is reached by no case: it rests on the text.
+ * WHICH FORMS OF THE ARITHMETIC THE RECORDS CHOSE (the reference is built with -Ofast):
+ *   - `x / base_cov` is a DIVISION in all three rules, not x * (1.0 / base_cov): the record `reciprocal` holds a line found by search
+ *     (2,839 pairs on 1,024 K-mers over base_cov 512 / 9,907: 53.64603805541992 as written, 53.646034240722656 by the reciprocal) under the
+ *     line rule, the cell rule and the long-edge rule, and the recorded .covs has the first value six times.
+ *   - abs(int_cov - frac_cov) in CNIntegerFraction is the FLOATING function: the integer one truncates every difference to 0 and would print 1
+ *     where the record of repeats_snps prints 0.8 (16 of 20) and the hand-staged input with copy numbers of 1.3, 2.3 and 0.7 (step7_cn_hand) 0.625 (10 of 16).
+ *   - Median(lens) is the upper median (the record parallel_4: 1,140 of 1,100, 1,110, 1,140, 1,150).
+ *   - A NaN is stored in .covs as ffc00000 (x86-64's default NaN, sign bit set), and the library stores that pattern whatever the device gives;
+ *     a NaN of 0 / 0 in cn_fraction prints as `-nan`.
+ *   - In .lines.stats a NaN prints as ` cov=?x`: under -Ofast the first `covs[ss][e].Def()` of WriteLineStats holds for a NaN and the second
+ *     does not (record no_pairs); -1 prints nothing and inf prints `cov=infx` (step7.line_stats_text).
+ * THE TWO FORMS OF THE LONG EDGES' COUNT.  A group of one edge needs no sort: an index row ascends in read id, so its distinct pairs are the
+ *   entries that open a pair, and the group's count is those of row e, plus those of row inv[e], minus the pairs in both (k7c_single_flag: a
+ *   thread per entry, a binary search into the other row; then a scan and k7c_single_count).  Measured against the sorted form on the 2,000
+ *   long edges (198,440 index entries) of tools/step7_time.py --coverage, both forms in turn in one process, two processes on an MI355X
+ *   (profiles/step7_coverage_generated_4M.json, _process2.json): sorted 0.295-0.312 ms, sort-free 0.132-0.137 ms of device time for that
+ *   round; the two processes differ by 0.016 ms at most.  The sort-free form is ahead by ten times that and is the default
+ *   (W2RAP_STEP7_LONG_DEFAULT); the cell groups, of several edges, keep the one radix sort.  tests/test_gpu_step7_cov.py holds the two forms
+ *   to each other and to Pids.
+ */
+#define W2RAP_STEP7_COV_NPAIRS 1u    /* npairs, llens */
+#define W2RAP_STEP7_COV_PEAK   2u    /* + covl, the candidates, base_cov */
+#define W2RAP_STEP7_COV_EDGES  4u    /* + cov, rule, the cell groups, the CN counts (the paths index only here) */
+
+#define W2RAP_STEP7_LONG_DEFAULT   0u  /* the library's choice: the sort-free form (the measurement is in the text above) */
+#define W2RAP_STEP7_LONG_SORTED    1u  /* keys and the radix sort, as the cell groups */
+#define W2RAP_STEP7_LONG_SORT_FREE 2u  /* k7c_single_flag: pairs of row e + pairs of row inv[e] - pairs in both, by binary search */
+
+#define W2RAP_STEP7_RULE_NONE 0
+#define W2RAP_STEP7_RULE_LINE 1
+#define W2RAP_STEP7_RULE_CELL 2
+#define W2RAP_STEP7_RULE_LONG 3
+
+#define W2RAP_STEP7_PEAK_NO_DATA      0   /* no candidate: base_cov 0 */
+#define W2RAP_STEP7_PEAK_SINGLE       1
+#define W2RAP_STEP7_PEAK_LARGEST_MASS 2   /* no peak (always below 21 candidates) */
+#define W2RAP_STEP7_PEAK_SCORED       3
+
+typedef struct w2rap_step7_cov_in {
+    int32_t  K;
+    uint64_t n_edge_objs;
+    const uint32_t* edge_len;        /* [n_edge_objs] bases, >= K; Kmers(e) = edge_len[e] - K + 1 */
+    const int32_t*  inv;             /* [n_edge_objs] */
+    uint64_t n_paths;                /* even */
+    const uint64_t* path_off;        /* [n_paths+1] */
+    const int32_t*  path_edges;
+    uint64_t n_lines;                /* the lines as w2rap_step7_in; at least one */
+    const uint64_t* line_off;
+    const uint64_t* cell_off;
+    const uint64_t* lpath_off;
+    const int32_t*  line_edges;
+} w2rap_step7_cov_in;
+
+typedef struct w2rap_step7_cov_params {
+    int32_t  device;
+    uint32_t flags;                  /* the highest W2RAP_STEP7_COV_* asked for decides (a part needs those before it); 0 = everything */
+    double   frac;                   /* CNIntegerFraction: the reference's default 0.1 */
+    int32_t  min_edge_size;          /* bases; the reference's default 2000 */
+    uint32_t long_form;              /* how the long edges' pairs are counted: W2RAP_STEP7_LONG_* (both give the same counts) */
+} w2rap_step7_cov_params;
+
+/* library-allocated HOST memory, free with w2rap_step7_coverage_free; a part that is not asked for leaves its pointers null and its counters zero */
+typedef struct w2rap_step7_cov_out {
+    int32_t* npairs;                 /* [n_lines] */
+    int32_t* llens;                  /* [n_lines] */
+    double*  covl;                   /* [n_lines]  PEAK */
+    double*  covx;                   /* [n_candidates] sorted */
+    int64_t* mass;                   /* [n_candidates] */
+    int32_t* ids;                    /* [n_candidates] */
+    float*   cov;                    /* [n_edge_objs] EDGES: -1 undefined; what .covs holds */
+    uint8_t* rule;                   /* [n_edge_objs] W2RAP_STEP7_RULE_* */
+    int32_t* group_line;             /* [n_groups] one record per qualifying class of a cell, in the reference's loop order */
+    int32_t* group_cell;             /* the cell's position in its line */
+    int32_t* group_len;              /* the upper median */
+    int64_t* group_pairs;            /* distinct pairs */
+    uint64_t* group_z_off;           /* [n_groups+1] into group_z */
+    int32_t* group_z;
+    int32_t* long_edge;              /* [n_long_asked] the edges the long-edge rule counted pairs for, ascending */
+    int64_t* long_pairs;             /* [n_long_asked] their distinct pairs */
+    double   base_cov;
+    double   cn_fraction;            /* double(n_cn_good) / double(n_cn_edges) */
+    int32_t  max_len, min_len;
+    uint64_t n_candidates, n_groups;
+    uint64_t n_cn_edges, n_cn_good;
+    /* the peak finder's branches (csrc/step7_peak.h) */
+    uint64_t n_simple, n_noise, n_edge, n_sparse, n_not_window_max, n_shallow, n_centred, n_prefiltered, n_peaks, peak_way, n_score_ties_taken, halved;
+    /* the cell rule's branches */
+    uint64_t n_cells, n_cells_empty, n_cells_sizes, n_cells_one_in, n_classes, n_classes_short;
+    /* the edge rules */
+    uint64_t n_line_lines;           /* lines of llens >= 1000 */
+    uint64_t n_rule[4];              /* edges per W2RAP_STEP7_RULE_* */
+    uint64_t n_long_asked;           /* edges the long-edge rule counted pairs for */
+    uint64_t n_undefined;            /* edges with !(cov >= 0) at the end (NaN included) */
+    uint64_t n_group_entries[2];     /* index entries sorted for the cell groups / for the long edges */
+    uint64_t index_built;
+    float ms_lines, ms_index, ms_groups, ms_rules;   /* device time per part, milliseconds */
+    float ms_long;                   /* of ms_groups: the long edges' round */
+} w2rap_step7_cov_out;
+
+int  w2rap_step7_coverage(const w2rap_step7_cov_in* in, const w2rap_step7_cov_params* params, w2rap_step7_cov_out* out, char* err, size_t errlen);
+void w2rap_step7_coverage_free(w2rap_step7_cov_out* out);
+/* the per-kernel device time of the last w2rap_step7_coverage comes from w2rap_step7_profile (the LINES kernels are in it) */
 
 #ifdef __cplusplus
 }

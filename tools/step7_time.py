@@ -20,7 +20,18 @@ on a seeded contig: on a bubble contig read 1 walks a, one of the branches (seed
 of c; elsewhere one edge each.  Per call the wall time, the per-part device milliseconds, the per-kernel lines of
 w2rap_step7_line_files_profile and the writer's rate: (text written + a quarter of it read as packed bases) / the time of the two
 k7f_write kernels -- counted as NOTES counts kg_seg_write's 1.08 TB/s, the only comparison there is: one kernel of ours beside another
-of ours, not against the reference, which cannot time this passage alone."""
+of ours, not against the reference, which cannot time this passage alone.
+
+    python tools/step7_time.py --coverage [--contigs 20000] [--reads 4000000] [--seed 7] [--span 0.1] [--unplaced 0.02] [--calls 7]
+
+times w2rap_step7_coverage (ComputeCoverage and CNIntegerFraction) on the contigs of the first workload with their pairs (lengths only,
+as there), and: every tenth contig a is followed by a bubble whose two branches are 1,200 K-mers and a closing edge c of 1,000 -- one
+line a -> {b1, b2} -> c, so the cell rule runs: two classes per line --; every twentieth instead by a cell whose two paths share a first
+edge of 1,200 K-mers, a -> {[p, q1], [p, q2]} -> c with q1 and q2 of 40 and 45 -- no class is formed and p is left to the long-edge rule.
+Every line is followed by its mirror image.  Read 1 of a pair on such a contig walks a, one of the two paths (seeded) and c, read 2 lies
+on the mirror of c (or, for --span of the pairs, of the next contig's first edge); --unplaced as above.  Per call the wall time, the
+per-part device milliseconds and the per-kernel lines of w2rap_step7_profile.  The calls take the two forms of the long edges' count in
+turn (sorted, sort-free, sorted, ...): ms_long is the device time of that round alone."""
 import argparse
 import json
 import os
@@ -109,6 +120,71 @@ def workload_line_files(n_contigs, n_reads, seed):
     return hbv, (np.arange(E) ^ 1).astype(np.int32), (np.zeros(2 * NP, np.int32), path_off, edges), F.Lines.from_nested(nested)
 
 
+def workload_coverage(n_contigs, n_reads, seed, span, unplaced):
+    rng = np.random.default_rng(seed)
+    kmers = rng.integers(3000, 12001, n_contigs)
+    lens, nested = [], []                                   # K-mers of every edge (e and its mirror e ^ 1); the lines
+    W = np.full((n_contigs, 2, 4), -1, np.int64)            # read 1's walk on contig i, either variant
+    first, last = np.zeros(n_contigs, np.int64), np.zeros(n_contigs, np.int64)
+
+    def edge(k):
+        lens.extend((k, k))
+        return len(lens) - 2
+    for i in range(n_contigs):
+        a = edge(int(kmers[i]))
+        first[i] = a
+        if i % 10:
+            nested += [[[[a]]], [[[a ^ 1]]]]; W[i, :, 0] = a; last[i] = a
+            continue
+        if i % 20:
+            b1, b2, c = edge(1200), edge(1200), edge(1000)
+            line = [[[a]], [[b1], [b2]], [[c]]]
+            W[i, 0, :3] = (a, b1, c); W[i, 1, :3] = (a, b2, c)
+        else:
+            p, q1, q2, c = edge(1200), edge(40), edge(45), edge(1000)
+            line = [[[a]], [[p, q1], [p, q2]], [[c]]]
+            W[i, 0] = (a, p, q1, c); W[i, 1] = (a, p, q2, c)
+        nested += [line, [[[e ^ 1 for e in reversed(path)] for path in cell] for cell in reversed(line)]]
+        last[i] = c
+    E = len(lens)
+    edge_len = (np.array(lens) + K - 1).astype(np.uint32)
+    bo = np.zeros(E + 1, np.uint64); np.cumsum((edge_len.astype(np.uint64) + 3) // 4, out=bo[1:])
+    z = np.zeros(1, np.uint64)
+    hbv = F.HBV(K, z, np.zeros(0, np.int32), np.zeros(0, np.int32), z.copy(), np.zeros(0, np.int32), np.zeros(0, np.uint8), bo, edge_len)      # (the call reads K and the lengths only)
+    NP = n_reads // 2
+    c = rng.integers(0, n_contigs - 1, NP)
+    kind, variant = rng.random(NP), rng.integers(0, 2, NP)
+    r1 = W[c, variant]                                       # [NP, 4]
+    r2 = np.where(kind < span, first[c + 1] ^ 1, last[c] ^ 1)
+    has1 = ~((kind >= span) & (kind < span + unplaced / 2)); has2 = ~((kind >= span + unplaced / 2) & (kind < span + unplaced))
+    both = np.concatenate([r1, r2[:, None], np.full((NP, 3), -1, np.int64)], 1).reshape(2 * NP, 4)       # row 2p: read 1, row 2p + 1: read 2
+    both[0::2][~has1] = -1; both[1::2][~has2] = -1
+    keep = both >= 0
+    path_off = np.zeros(2 * NP + 1, np.uint64); np.cumsum(keep.sum(1), out=path_off[1:])
+    return hbv, (np.arange(E) ^ 1).astype(np.int32), (np.zeros(2 * NP, np.int32), path_off, both[keep].astype(np.int32)), F.Lines.from_nested(nested)
+
+
+def main_coverage(a):
+    hbv, inv, paths, lines = workload_coverage(a.contigs, a.reads, a.seed, a.span, a.unplaced)
+    walls, parts, kernels, forms = [], [], [], []
+    for i in range(max(1, a.calls)):                        # the two forms of the long edges' count in turn (ms_long is their round, inside ms_groups)
+        forms.append(("sorted", "sort_free")[i % 2])
+        t0 = time.perf_counter()
+        res = step7.coverage(hbv, inv, paths, lines, long_form=forms[-1])
+        walls.append(round(time.perf_counter() - t0, 4))
+        parts.append({k: round(v, 4) for k, v in res.ms.items()})
+        kernels.append({k: [round(v[0], 4), v[1]] for k, v in step7.profile().items()})
+        print(f"call {len(walls)} ({forms[-1]}): wall {walls[-1]:.4f} s, device {sum(v for k, v in res.ms.items() if k != 'ms_long'):.3f} ms, long edges {res.ms['ms_long']:.4f} ms", file=sys.stderr)
+    out = {"workload": f"generated (tools/step7_time.py --coverage): {a.contigs} contigs of 3,000-12,000 K-mers, every tenth followed by a bubble of two 1,200-K-mer branches, every "
+                       f"twentieth by a cell whose two paths share a first edge of 1,200 K-mers, every line followed by its mirror image, {a.reads} reads, {a.span:g} of the pairs span "
+                       f"to the neighbour contig, {a.unplaced:g} have a mate without a path (seed {a.seed})",
+           "entry": "w2rap_step7_coverage", "parts": "npairs+peak+edges", "edge_objects": int(len(hbv.edge_len)), "lines": int(lines.n_lines), "reads": int(len(paths[0])),
+           "path_entries": int(paths[1][-1]), "base_cov": res.base_cov, "cn_fraction": res.cn_fraction, "counters": res.counters, "wall_s_calls": walls, "ms_parts_calls": parts,
+           "ms_device_sum_calls": [round(sum(v for k, v in p.items() if k != "ms_long"), 3) for p in parts], "kernels_calls": kernels,
+           "long_form_calls": forms, "ms_long_calls": [p["ms_long"] for p in parts]}
+    print(json.dumps(out))
+
+
 def main_line_files(a):
     hbv, inv, paths, lines = workload_line_files(a.contigs, a.reads, a.seed)
     walls, parts, kernels, rates = [], [], [], []
@@ -136,6 +212,7 @@ def main_line_files(a):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--line_files", action="store_true", help="time w2rap_step7_line_files instead")
+    ap.add_argument("--coverage", action="store_true", help="time w2rap_step7_coverage instead")
     ap.add_argument("--contigs", type=int, default=20_000)
     ap.add_argument("--reads", type=int, default=4_000_000)
     ap.add_argument("--seed", type=int, default=7)
@@ -145,6 +222,8 @@ def main():
     a = ap.parse_args()
     if a.line_files:
         return main_line_files(a)
+    if a.coverage:
+        return main_coverage(a)
     hbv, inv, paths, lines = workload(a.contigs, a.reads, a.seed, a.span, a.unplaced)
     walls, parts, kernels = [], [], []
     for _ in range(max(1, a.calls)):

@@ -639,6 +639,14 @@ int step7_check(const w2rap_step7_in* in, const w2rap_step7_params* P, char* err
 }
 
 }  // namespace
+
+// for step7_cov.hip (w2rap_step7_coverage): part LINES as above on the caller's context -- tol, llens, npairs and the LINES counters in
+// `out` --, and the profile that w2rap_step7_profile reads
+int step7_lines_part(Ctx& c, const w2rap_step7_in& in, w2rap_step7_out& out) {
+    const w2rap_step7_params P{};
+    return step7(c, in, P, W2RAP_STEP7_LINES, out);
+}
+void save_profile7_shared(Ctx& c) { save_profile7(c); }
 }  // namespace w2
 
 using namespace w2;

@@ -537,6 +537,48 @@ def read_int_vec(path) -> np.ndarray:
     return np.frombuffer(raw, dtype="<i4", count=n, offset=16).astype(np.int32)
 
 
+# --------------------------------------------------------------------------- covs
+# vec<vec<covcount>> (.covs): covcount is TRIVIALLY_SERIALIZABLE (paths/long/large/Lines.h:50-66), one float; BinaryWriter writes a vector
+# of such elements as its u64 size and the elements' bytes (feudal/BinaryStream.h), the outer vector as its size and every inner one.
+def covs_to_bytes(covs) -> bytes:
+    """covs: one float32 array per sample"""
+    out = bytearray(b"BINWRITE") + struct.pack("<Q", len(covs))
+    for c in covs:
+        c = np.asarray(c, "<f4")
+        out += struct.pack("<Q", len(c)) + c.tobytes()
+    return bytes(out)
+
+
+def write_covs(path, covs):
+    with open(path, "wb") as f:
+        f.write(covs_to_bytes(covs))
+
+
+def read_covs(path):
+    """-> list of float32 arrays, one per sample (-1: undefined)"""
+    with open(path, "rb") as f:
+        return covs_from_bytes(f.read(), path)
+
+
+def covs_from_bytes(raw: bytes, path="covs"):
+    if raw[:8] != b"BINWRITE" or len(raw) < 16:
+        raise ValueError(f"{path}: missing BINWRITE magic or size")
+    (ns,) = struct.unpack_from("<Q", raw, 8)
+    p, out = 16, []
+    for _ in range(ns):
+        if p + 8 > len(raw):
+            raise ValueError(f"{path}: truncated")
+        (n,) = struct.unpack_from("<Q", raw, p)
+        p += 8
+        if n > (len(raw) - p) // 4:
+            raise ValueError(f"{path}: a vector of {n} floats in a file of {len(raw)} bytes")
+        out.append(np.frombuffer(raw, dtype="<f4", count=n, offset=p).astype(np.float32))
+        p += 4 * n
+    if p != len(raw):
+        raise ValueError(f"{path}: {len(raw) - p} trailing bytes")
+    return out
+
+
 # --------------------------------------------------------------------------- freqs
 def freqs_text(hist) -> str:
     """hist: 101 counts -> small_K.freqs text (BuildReadQGraph.cc:1108-1112)"""

@@ -12,7 +12,12 @@ list, GAP_CLEANUP, FinalFiles and FindLines stay the reference's; the lines come
 
 ``python -m w2rap_contigger_amd.step7 DIR PREFIX`` reads DIR/PREFIX.contig.hbv, .contig.paths, .fin.lines and .fin.lines.npairs and
 writes the accepted gaps as text; with ``--line_files LINES_FILE`` it reads DIR/PREFIX.contig.hbv/.paths and that lines file and writes
-a.lines.fasta, a.lines.efasta, a.lines.src and stats into DIR.  The HIP library is the only implementation (no CPU fallback)."""
+a.lines.fasta, a.lines.efasta, a.lines.src and stats into DIR; with ``--coverage LINES_FILE`` it writes DIR/PREFIX_assembly.covs,
+.lines.npairs and .lines.stats and prints the `CN fraction good` line of Step 6.  The HIP library is the only implementation (no CPU
+fallback).
+
+`coverage` is ComputeCoverage (Lines.cc:442-624) with CNIntegerFraction (GapToyTools5.cc:1520-1538): the copy number of every edge;
+`line_stats_text` is WriteLineStats (Lines.cc:357-379)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -76,6 +81,9 @@ def lib():
         L.w2rap_step7_line_files_free.restype = None
         L.w2rap_step7_line_files_profile.argtypes = [C.c_char_p, C.c_size_t]
         L.w2rap_step7_line_files_profile.restype = C.c_size_t
+        L.w2rap_step7_coverage.argtypes = [C.POINTER(CovIn), C.POINTER(CovParams), C.POINTER(CovOut), C.c_char_p, C.c_size_t]
+        L.w2rap_step7_coverage_free.argtypes = [C.POINTER(CovOut)]
+        L.w2rap_step7_coverage_free.restype = None
         _ready = True
     return L
 
@@ -263,6 +271,148 @@ def line_files(hbv: F.HBV, inv, paths, lines: F.Lines, parts=FASTA_TEXTS, device
         L.w2rap_step7_line_files_free(C.byref(o))
 
 
+# ---------------------------------------------------------------------------------------------------------------- the coverage
+COV_PARTS = {"npairs": 1, "peak": 2, "edges": 4}           # W2RAP_STEP7_COV_*: a part brings those before it
+RULES = ("none", "line", "cell", "long")                    # W2RAP_STEP7_RULE_*
+PEAK_WAYS = ("no_data", "single", "largest_mass", "scored") # W2RAP_STEP7_PEAK_*
+
+
+class CovIn(C.Structure):
+    _fields_ = [("K", C.c_int32), ("n_edge_objs", C.c_uint64), ("edge_len", C.c_void_p), ("inv", C.c_void_p), ("n_paths", C.c_uint64), ("path_off", C.c_void_p),
+                ("path_edges", C.c_void_p), ("n_lines", C.c_uint64), ("line_off", C.c_void_p), ("cell_off", C.c_void_p), ("lpath_off", C.c_void_p), ("line_edges", C.c_void_p)]
+
+
+class CovParams(C.Structure):
+    _fields_ = [("device", C.c_int32), ("flags", C.c_uint32), ("frac", C.c_double), ("min_edge_size", C.c_int32), ("long_form", C.c_uint32)]
+
+
+LONG_FORMS = {"default": 0, "sorted": 1, "sort_free": 2}    # W2RAP_STEP7_LONG_*
+COV_ARRAYS = {"npairs": (np.int32, "NL"), "llens": (np.int32, "NL"), "covl": (np.float64, "NL"), "covx": (np.float64, "n_candidates"), "mass": (np.int64, "n_candidates"),
+              "ids": (np.int32, "n_candidates"), "cov": (np.float32, "E"), "rule": (np.uint8, "E"), "group_line": (np.int32, "n_groups"), "group_cell": (np.int32, "n_groups"),
+              "group_len": (np.int32, "n_groups"), "group_pairs": (np.int64, "n_groups"), "group_z_off": (np.uint64, "n_groups+1"), "group_z": (np.int32, "NZ"),
+              "long_edge": (np.int32, "n_long_asked"), "long_pairs": (np.int64, "n_long_asked")}
+COV_SCALARS = (("base_cov", C.c_double), ("cn_fraction", C.c_double), ("max_len", C.c_int32), ("min_len", C.c_int32))
+COV_COUNTERS = ("n_candidates", "n_groups", "n_cn_edges", "n_cn_good", "n_simple", "n_noise", "n_edge", "n_sparse", "n_not_window_max", "n_shallow", "n_centred", "n_prefiltered",
+                "n_peaks", "peak_way", "n_score_ties_taken", "halved", "n_cells", "n_cells_empty", "n_cells_sizes", "n_cells_one_in", "n_classes", "n_classes_short",
+                "n_line_lines", "n_rule", "n_long_asked", "n_undefined", "n_group_entries", "index_built")
+COV_PHASES = ("ms_lines", "ms_index", "ms_groups", "ms_rules", "ms_long")
+_COV_CTYPE = {"n_rule": C.c_uint64 * 4, "n_group_entries": C.c_uint64 * 2}
+
+
+class CovOut(C.Structure):
+    _fields_ = ([(k, C.c_void_p) for k in COV_ARRAYS] + list(COV_SCALARS) + [(k, _COV_CTYPE.get(k, C.c_uint64)) for k in COV_COUNTERS] + [(k, C.c_float) for k in COV_PHASES])
+
+
+@dataclass
+class Coverage:
+    """w2rap_step7_cov_out: the arrays by name (None: the part was not asked for; group_z as one list per group), base_cov, cn_fraction,
+    max_len and min_len, the counters and the device times"""
+    arrays: dict
+    base_cov: float
+    cn_fraction: float
+    max_len: int
+    min_len: int
+    counters: dict
+    ms: dict
+
+    def __getattr__(self, k):
+        try:
+            return self.__dict__["arrays"][k]
+        except KeyError:
+            raise AttributeError(k)
+
+    def cn_line(self) -> str:
+        """`CN fraction good = ...` as the reference's stream prints the double (operator<< at the default precision of 6: %g)"""
+        return "CN fraction good = " + _stream_double(self.cn_fraction)
+
+
+def _stream_double(x: float) -> str:
+    """a double through std::ostream at its defaults: %g; inf and nan as the C library prints them (a NaN of 0 / 0 carries the sign bit on
+    x86-64: "-nan")"""
+    import math
+    if math.isnan(x):
+        return "-nan" if math.copysign(1.0, x) < 0 else "nan"
+    return "%g" % x
+
+
+def coverage(hbv: F.HBV, inv, paths, lines: F.Lines, parts=("edges",), frac=0.1, min_edge_size=2000, device=0, flags=None, long_form="default") -> Coverage:
+    """w2rap_step7_coverage: ComputeCoverage and CNIntegerFraction for one sample.  parts: "npairs" (npairs and llens only), "peak" (and
+    covl, the candidates, base_cov), "edges" (everything).  flags overrides parts (the tests of the argument checks); long_form: how the
+    long edges' pairs are counted, "sorted" or "sort_free" (the same counts either way)"""
+    L = lib()
+    if flags is None:
+        flags = 0
+        for p in parts:
+            if p not in COV_PARTS:
+                raise ValueError(f"unknown part {p!r}: one of {sorted(COV_PARTS)}")
+            flags |= COV_PARTS[p]
+        if not flags:
+            raise ValueError("no part asked for")
+    keep = [np.ascontiguousarray(hbv.edge_len, np.uint32), np.ascontiguousarray(inv, np.int32), np.ascontiguousarray(paths[1], np.uint64), np.ascontiguousarray(paths[2], np.int32),
+            np.ascontiguousarray(lines.line_off, np.uint64), np.ascontiguousarray(lines.cell_off, np.uint64), np.ascontiguousarray(lines.lpath_off, np.uint64),
+            np.ascontiguousarray(lines.edges, np.int32)]
+    if len(keep[1]) != len(keep[0]):
+        raise ValueError("inv must have one entry per edge object")
+    if len(keep[2]) < 1 or len(keep[4]) < 1 or len(keep[5]) != int(keep[4][-1]) + 1 or len(keep[6]) != int(keep[5][-1]) + 1:
+        raise ValueError("path_off, line_off, cell_off and lpath_off must each have one entry more than what they divide")
+    E, NL = len(keep[0]), len(keep[4]) - 1
+    p = lambda a: _ptr(a) if len(a) else None
+    i = CovIn(hbv.K, E, p(keep[0]), p(keep[1]), len(keep[2]) - 1, p(keep[2]), p(keep[3]), NL, p(keep[4]), p(keep[5]), p(keep[6]), p(keep[7]))
+    prm = CovParams(device, flags, frac, min_edge_size, LONG_FORMS[long_form])
+    o = CovOut()
+    err = C.create_string_buffer(1024)
+    rc = L.w2rap_step7_coverage(C.byref(i), C.byref(prm), C.byref(o), err, 1024)
+    if rc:
+        raise Step2Error(rc, err.value.decode(errors="replace"))
+    try:
+        size = {"E": E, "NL": NL, "n_candidates": int(o.n_candidates), "n_groups": int(o.n_groups), "n_groups+1": int(o.n_groups) + 1, "n_long_asked": int(o.n_long_asked)}
+        arrays = {}
+        for k, (dt, n) in COV_ARRAYS.items():
+            if k == "group_z":
+                continue
+            arrays[k] = _np_from(getattr(o, k), dt, size[n]) if getattr(o, k) else None
+        if arrays["group_z_off"] is not None:
+            zo = arrays.pop("group_z_off").astype(np.int64)
+            z = _np_from(o.group_z, np.int32, int(zo[-1])) if o.group_z else np.zeros(0, np.int32)
+            arrays["group_z"] = [z[zo[g]:zo[g + 1]].tolist() for g in range(len(zo) - 1)]
+        else:
+            arrays.pop("group_z_off")
+            arrays["group_z"] = None
+        counters = {k: ([int(x) for x in getattr(o, k)] if k in _COV_CTYPE else int(getattr(o, k))) for k in COV_COUNTERS}
+        return Coverage(arrays, float(o.base_cov), float(o.cn_fraction), int(o.max_len), int(o.min_len), counters, {k: float(getattr(o, k)) for k in COV_PHASES})
+    finally:
+        L.w2rap_step7_coverage_free(C.byref(o))
+
+
+def _fixed2(x) -> str:
+    """ToString(float, 2) (feudal/CharString.h:35-37): the float through a fixed stream of precision 2 -- printf's %.2f of the float's
+    value; inf and nan as the C library prints them"""
+    import math
+    x = float(np.float32(x))
+    if math.isnan(x):
+        return "-nan" if math.copysign(1.0, x) < 0 else "nan"
+    if math.isinf(x):
+        return "inf" if x > 0 else "-inf"
+    return "%.2f" % x
+
+
+def line_stats_text(result, lines: F.Lines) -> str:
+    """WriteLineStats (Lines.cc:357-379), the text of .lines.stats, for one sample: per line `line[i] e1..e2 len= npairs=` and, where the
+    first edge of the line has a defined coverage (cov >= 0), ` cov=<two decimals>x`; ` cov=?x` for a NaN.  result: a Coverage (or anything with llens, npairs, cov)"""
+    nested = lines.nested()
+    out = []
+    for i, line in enumerate(nested):
+        e1, e2 = line[0][0][0], line[-1][0][0]
+        row = f"line[{i}] {e1}..{e2} len={int(result.llens[i])} npairs={int(result.npairs[i])}"
+        c = result.cov[e1]
+        if c >= 0:
+            row += f" cov={_fixed2(c)}x"
+        elif c != c:                                            # a NaN (base_cov 0 and no pairs): what the reference's -Ofast build prints, see w2rap_step7.h
+            row += " cov=?x"
+        out.append(row + "\n")
+    return "".join(out)
+
+
 def sort_lines(hbv: F.HBV, inv, lines: F.Lines, paths=None, device=0) -> F.Lines:
     """SortLines (Lines.cc:664-678): the lines ordered by (-llens, min(F, inv[B]), F), F and B the first and the last edge of a line --
     the key of two different lines differs (F is the first edge of one line only), so the order does not depend on the sort.  llens comes
@@ -328,10 +478,21 @@ def main(argv=None):
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("-o", "--out", default=None, help="the text file to write (default DIR/PREFIX.gaps.txt)")
     ap.add_argument("--line_files", metavar="LINES_FILE", default=None, help="write a.lines.fasta, a.lines.efasta, a.lines.src and stats into DIR from this lines file instead")
+    ap.add_argument("--coverage", metavar="LINES_FILE", default=None, help="write PREFIX_assembly.covs, .lines.npairs and .lines.stats into DIR from this lines file and print the CN fraction")
     a = ap.parse_args(argv)
     stem = os.path.join(a.dir, a.prefix)
     hbv = F.read_hbv(stem + ".contig.hbv")
     paths = F.read_paths(stem + ".contig.paths")
+    if a.coverage:
+        lines = F.read_lines(a.coverage)
+        res = coverage(hbv, involution(hbv), paths, lines, device=a.device)
+        F.write_covs(stem + "_assembly.covs", [res.cov])
+        F.write_int_vec(stem + "_assembly.lines.npairs", res.npairs)
+        with open(stem + "_assembly.lines.stats", "w") as f:
+            f.write(line_stats_text(res, lines))
+        print(res.cn_line())
+        if not a.line_files:
+            return 0
     if a.line_files:
         lines, inv = F.read_lines(a.line_files), involution(hbv)
         res = line_files(hbv, inv, paths, lines, device=a.device)
