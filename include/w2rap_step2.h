@@ -335,6 +335,9 @@ int w2rap_step2_selftest_prims(w2rap_step2_ctx*, uint64_t n, uint64_t seed, int 
  * [fw * w_lo_frac16 / 16, fw * w_hi_frac16 / 16) -- (0, 16) is the whole filter, anything else a slice as the sharded graph phase builds
  * it.  0 = equal, 1 = a word differs, 2 = the word behind the slice was written, < 0 = could not run */
 int w2rap_step2_selftest_filter32(w2rap_step2_ctx*, uint64_t nbases, uint64_t seed, uint32_t w_lo_frac16, uint32_t w_hi_frac16);
+/* ... the same for a stream that repeats its first `period` (>= 1) pseudo-random bases: equal words from end to end (period 1: the whole
+ * stream is one run of one word) */
+int w2rap_step2_selftest_filter32_periodic(w2rap_step2_ctx*, uint64_t nbases, uint32_t period, uint64_t seed, uint32_t w_lo_frac16, uint32_t w_hi_frac16);
 /* device bytes the context holds at the moment (live blocks of its pool): what the per-rank share of the dictionary is measured by */
 uint64_t w2rap_step2_device_bytes(w2rap_step2_ctx*);
 /* ... and their maximum since the context was created or since the last call with reset != 0 (which restarts the maximum at the current

@@ -235,27 +235,48 @@ struct alignas(32) ObjRec { int32_t succ[4]; uint32_t eo_lo, eo_hi, elen, edge_r
 // after a sequencing error at base e, TWO probes (31-mers at e-30 and e: 2 x 30 k-mers) replace the 60 per-k-mer probes
 // that BRQ_Pather::path's base-by-base slide costs (31 is the largest length for which two suffice).  No false negatives.
 // Layout: 64-bit words.  The WORD of a 31-mer is chosen by a canonical minimizer -- the smallest hashed 15-mer, over both
-// strands, among the five windows at offsets 0, 4, .., 16 (a set that maps onto itself under reverse complement) -- its two
-// BITS by the hash of the canonical 31-mer.  31-mers four positions apart share four of their five windows, so the 31-mers
-// of an edge fall into runs with a common word; the builder ORs the bits of a wavefront's equal words together and issues
-// ONE atomic per run (a quarter of the positions' count or less; device atomics run at 27 G/s whatever the table size).
+// strands, among the windows at offsets 0, FMER_STRIDE, .., 16 (a set that maps onto itself under reverse complement, j <-> 16 - j,
+// for every stride that divides 16) -- its two BITS by the hash of the canonical 31-mer.  31-mers FMER_STRIDE positions apart share
+// all but one of their windows, so the 31-mers of an edge fall into runs with a common word along FMER_STRIDE interleaved chains; the
+// builder ORs the bits of a wavefront's equal words together and issues ONE atomic per run.  Stride 2 (nine windows) ships: runs of
+// 5 on two chains, 14 atomics per 64 positions.  Stride 4 (five windows, the form of rounds 4 - 6) has runs of 3 and 24 atomics;
+// stride 1 (all 17 windows: the minimizer of the 31-mer, runs of 9 neighbours) has 8, but a word then holds the bits of nine
+// neighbours and a 31-mer with one wrong base is proven absent in 87 % of the cases instead of 92 % (stride 4: 95 %) -- read pathing
+// lost 7 ms to win 0.3.  NOTES section 22; -DW2RAP_FMER_STRIDE=1 / 4 build the others.
 // 31 bases as one u64, LSB first (base t at bits 2t+1:2t; the callers hand over 64 stream bits, the top group is dropped).
 constexpr unsigned FMER = 31;                  // filter-mer length
 constexpr unsigned FSPAN = K - FMER;           // the FMER-mer at base t lies in the k-mers t-FSPAN .. t
+#ifndef W2RAP_FMER_STRIDE
+#define W2RAP_FMER_STRIDE 2
+#endif
+constexpr unsigned FMER_STRIDE = W2RAP_FMER_STRIDE;      // distance of the minimizer windows: builder and readers share it through fmer_key
+static_assert(FMER_STRIDE >= 1 && (FMER - MMER_F) % FMER_STRIDE == 0, "the window offsets must map onto themselves under j <-> 16 - j");
 struct FmerKey { uint32_t word; uint64_t mask; };        // word: index before masking with the table size
+// (FENCED: the instruction scheduler may not move anything across the key's first and last instruction.  Read pathing asks for three
+//  to six keys at once; left free, the scheduler interleaves the windows of all of them and k_path_dyn spills 37 VGPRs (nine windows)
+//  or 68 (seventeen) instead of the 34 of the five-window key -- fenced it spills 33 with either.  A rolled loop spilled 66 - 76.)
+template <unsigned STRIDE = FMER_STRIDE, bool FENCED = false>
 __host__ __device__ inline FmerKey fmer_key(uint64_t x) {
+    static_assert(STRIDE >= 1 && (FMER - MMER_F) % STRIDE == 0, "stride must divide 16");
     x &= (1ull << (2 * FMER)) - 1;
     const uint64_t rx = rev2_64(~x) >> (64 - 2 * FMER);   // reverse complement: its 15-mer at 16-j is the RC of x's 15-mer at j
     uint32_t mu = 0xFFFFFFFFu;
+#if defined(__HIP_DEVICE_COMPILE__)
+    if (FENCED) __builtin_amdgcn_sched_barrier(0);
+#endif
 #pragma unroll
-    for (unsigned j = 0; j <= FMER - MMER_F; j += 4) {
+    for (unsigned j = 0; j <= FMER - MMER_F; j += STRIDE) {
         const uint32_t f = (uint32_t)(x >> (2 * j)) & 0x3FFFFFFFu, r = (uint32_t)(rx >> (2 * (FMER - MMER_F - j))) & 0x3FFFFFFFu;
         const uint32_t key = (f < r ? f : r) * 0x9E3779B1u;                         // odd multiplier: a bijection, no ties
         mu = key < mu ? key : mu;
     }
     uint32_t w = mu ^ (mu >> 15); w *= 0x85EBCA6Bu; w ^= w >> 13;
     const uint64_t h = (rx < x ? rx : x) * 0x9E3779B97F4A7C15ull;
-    return FmerKey{w, (1ull << ((h >> 58) & 63)) | (1ull << ((h >> 40) & 63))};
+    const FmerKey k{w, (1ull << ((h >> 58) & 63)) | (1ull << ((h >> 40) & 63))};
+#if defined(__HIP_DEVICE_COMPILE__)
+    if (FENCED) __builtin_amdgcn_sched_barrier(0);
+#endif
+    return k;
 }
 
 // ---- super-k-mer records (extract -> count hand-off) -------------------------------

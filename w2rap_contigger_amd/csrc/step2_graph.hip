@@ -602,7 +602,7 @@ __global__ void __launch_bounds__(256) k_pack_codes(uint64_t nbytes, uint64_t nb
 
 // absence filter over every 31-mer of the edge stream (common.h).  31-mers that straddle two edges in the concatenated
 // stream are inserted as well: harmless, a filter may only err towards "maybe present".  Lane = position; the bits of
-// lanes that fall into the same word are ORed together with four shuffle steps and only the first lane of a run
+// lanes that fall into the same word are ORed together with log2(64 / FMER_STRIDE) shuffle steps and only the first lane of a run
 // issues the atomic (equal words that are not neighbours in a run may be merged too: they ARE the same word).
 // (w_lo, w_hi): only the words of that range are written, at filter[word - w_lo] -- the sharded graph phase has every rank build ITS
 // slice of the words (the whole stream is scanned, the atomics -- what bounds this kernel -- are the slice's) and gathers the slices
@@ -618,12 +618,14 @@ __global__ void __launch_bounds__(256) k_filter32(uint64_t npos, const uint8_t* 
         const FmerKey k = fmer_key(x);
         word = k.word & fmask; mask = k.mask;
     }
-    // positions g, g+4, g+8, .. share windows: a run's lanes are 4 apart.  Gather along distance 4 (4, 8, 16, 32), then a
-    // lane is the head of its run iff the lane 4 before it has another word.
-    const uint32_t prev = __shfl_up(word, 4);
-    const bool head = g < npos && (lane < 4 || prev != word);
+    // positions g, g+D, g+2D, .. share windows (D = FMER_STRIDE, common.h): a run's lanes are D apart.  Gather along distance D
+    // (D, 2D, .., 32: log2(64 / D) steps), then a lane is the head of its run iff the lane D before it has another word, or is none.
+    constexpr unsigned D = FMER_STRIDE;
+    static_assert(D <= 32 && (D & (D - 1)) == 0, "the gather doubles its distance up to 32");
+    const uint32_t prev = __shfl_up(word, D);
+    const bool head = g < npos && (lane < D || prev != word);
 #pragma unroll
-    for (unsigned d = 4; d < 64; d <<= 1) {
+    for (unsigned d = D; d < 64; d <<= 1) {
         const uint32_t ow = __shfl_down(word, d);
         const unsigned long long om = __shfl_down(mask, d);
         if (lane + d < 64 && ow == word) mask |= om;
@@ -907,11 +909,12 @@ __global__ void __launch_bounds__(256) k_end_vertices(uint64_t n, const uint32_t
     uint32_t id = perm[j];
     if (id & 1) right[id >> 1] = vid; else left[id >> 1] = vid;
 }
-__global__ void __launch_bounds__(256) k_adj_keys(uint64_t NO, const int32_t* __restrict__ a, const int32_t* __restrict__ b,
+// (vbits: the bits a vertex number occupies -- the key is 2 * vbits wide and the sort runs over those bits alone)
+__global__ void __launch_bounds__(256) k_adj_keys(uint64_t NO, const int32_t* __restrict__ a, const int32_t* __restrict__ b, unsigned vbits,
                                                    uint64_t* __restrict__ keys, uint32_t* __restrict__ vals, uint32_t* __restrict__ deg) {
     uint64_t o = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (o >= NO) return;
-    keys[o] = ((uint64_t)(uint32_t)a[o] << 32) | (uint32_t)b[o];
+    keys[o] = ((uint64_t)(uint32_t)a[o] << vbits) | (uint32_t)b[o];
     vals[o] = (uint32_t)o;
     atomicAdd(&deg[a[o]], 1u);
 }
@@ -1602,13 +1605,17 @@ int graph_finish(Ctx& c) {
     W2_ALLOC(c.d_to_v, int32_t, NO); W2_ALLOC(c.d_to_e, int32_t, NO);
     uint32_t* deg = nullptr; uint64_t* akeys = nullptr; uint32_t* avals = nullptr;
     W2_ALLOC(deg, uint32_t, NV); W2_ALLOC(akeys, uint64_t, NO); W2_ALLOC(avals, uint32_t, NO);
+    // the keys (this vertex << vbits | other vertex) hold 2 vbits bits -- 36 of 64 at 140 k vertices: five sort passes instead of
+    // eight, the same order (a stable sort by the same pair)
+    unsigned vbits = 1;
+    while (vbits < 32 && ((NV ? NV - 1 : 0) >> vbits)) ++vbits;
     for (int dir = 0; dir < 2; ++dir) {
         const int32_t* a = dir == 0 ? c.d_left : c.d_right;
         const int32_t* b = dir == 0 ? c.d_right : c.d_left;
         W2_HIP(hipMemsetAsync(deg, 0, (NV ? NV : 1) * 4, st));
         if (NO) {
-            LAUNCH(c, "k_adj_keys", k_adj_keys, dim3(grid_for(NO)), dim3(256), 0, NO, a, b, akeys, avals, deg);
-            W2_TRY(sort_pairs_u64(c, akeys, avals, NO, 0, 64));
+            LAUNCH(c, "k_adj_keys", k_adj_keys, dim3(grid_for(NO)), dim3(256), 0, NO, a, b, vbits, akeys, avals, deg);
+            W2_TRY(sort_pairs_u64(c, akeys, avals, NO, 0, (int)(2 * vbits)));
             LAUNCH(c, "k_adj_out", k_adj_out, dim3(grid_for(NO)), dim3(256), 0, NO, avals, b, dir == 0 ? c.d_from_v : c.d_to_v,
                                dir == 0 ? c.d_from_e : c.d_to_e);
         }
@@ -1766,7 +1773,8 @@ int phase_graph(Ctx& c, const w2rap_edge_hint* hint) {
 // A pseudo-random 2-bit stream of nbases bases, the words [fw lo/16, fw hi/16) of its absence filter built by filter32_build (what the
 // graph phase and filter32_slice call) against a host loop over fmer_key.  -> 0, 1 a word differs, 2 the word behind the range was
 // written, < 0 could not run
-extern "C" int w2rap_step2_selftest_filter32(w2rap_step2_ctx* h, uint64_t nbases, uint64_t seed, uint32_t w_lo_frac16, uint32_t w_hi_frac16) {
+// period 0: every base drawn from the generator; period p: the first p bases drawn, the stream repeats them
+static int selftest_filter32_stream(w2rap_step2_ctx* h, uint64_t nbases, uint64_t seed, uint32_t period, uint32_t w_lo_frac16, uint32_t w_hi_frac16) {
     using namespace w2;
     if (!h || nbases < FMER || nbases > (1ull << 33) || w_lo_frac16 > w_hi_frac16 || w_hi_frac16 > 16) return -1;
     Ctx& c = h->c;
@@ -1775,8 +1783,10 @@ extern "C" int w2rap_step2_selftest_filter32(w2rap_step2_ctx* h, uint64_t nbases
     std::vector<uint8_t> hb(nby + 16, 0);
     uint64_t x = seed * 0x9E3779B97F4A7C15ull + 1;
     for (uint64_t g = 0; g < nbases; ++g) {
-        x ^= x << 13; x ^= x >> 7; x ^= x << 17;
-        hb[g >> 2] |= (uint8_t)(((x >> 33) & 3) << (2 * (g & 3)));
+        unsigned b;
+        if (period && g >= period) b = (hb[(g - period) >> 2] >> (2 * ((g - period) & 3))) & 3u;
+        else { x ^= x << 13; x ^= x >> 7; x ^= x << 17; b = (unsigned)((x >> 33) & 3); }
+        hb[g >> 2] |= (uint8_t)(b << (2 * (g & 3)));
     }
     const uint64_t fw = filter32_words_for(nbases), lo = fw * w_lo_frac16 / 16, hi = fw * w_hi_frac16 / 16, npos = nbases - (FMER - 1);
     std::vector<unsigned long long> want(hi - lo + 1, 0), got(hi - lo + 1);
@@ -1801,4 +1811,14 @@ extern "C" int w2rap_step2_selftest_filter32(w2rap_step2_ctx* h, uint64_t nbases
     if (!bad && got[hi - lo] != 0) bad = 2;
     c.release(d_bits); c.release(d_out);
     return bad;
+}
+extern "C" int w2rap_step2_selftest_filter32(w2rap_step2_ctx* h, uint64_t nbases, uint64_t seed, uint32_t w_lo_frac16, uint32_t w_hi_frac16) {
+    return selftest_filter32_stream(h, nbases, seed, 0, w_lo_frac16, w_hi_frac16);
+}
+// ... of a stream that repeats its first `period` (>= 1) pseudo-random bases: period 1 is one run in one word from end to end, period 17 ends a
+// run at every position class
+extern "C" int w2rap_step2_selftest_filter32_periodic(w2rap_step2_ctx* h, uint64_t nbases, uint32_t period, uint64_t seed, uint32_t w_lo_frac16,
+                                                      uint32_t w_hi_frac16) {
+    if (!period) return -1;
+    return selftest_filter32_stream(h, nbases, seed, period, w_lo_frac16, w_hi_frac16);
 }

@@ -413,7 +413,7 @@ __global__ void __launch_bounds__(PATH_THREADS) __attribute__((amdgpu_waves_per_
             else {
                 uint32_t p = 0;
                 const uint32_t end = L - K + 1;
-                auto mer32_at = [&](uint32_t tt) -> FmerKey { return fmer_key(rd.bits64(tt)); };   // the 31-mer at base tt <= L-31 (common.h)
+                auto mer32_at = [&](uint32_t tt) -> FmerKey { return fmer_key<FMER_STRIDE, (FMER_STRIDE < 4)>(rd.bits64(tt)); };   // the 31-mer at base tt <= L-31 (common.h)
                 auto f32_absent = [&](const FmerKey& k, unsigned long long w) -> bool { return (w & k.mask) != k.mask; };
                 const uint32_t last = L - K, tmax = L - FMER;
                 // Up to three 31-mers that contain base e, fetched together: how many k-mers from `cur` on do they prove absent?  (A
@@ -700,7 +700,7 @@ __global__ void __launch_bounds__(PATH_THREADS) __attribute__((amdgpu_waves_per_
         if (has && p != end) {
             if (A.part_budget && np >= A.part_budget) { deferred = true; p = end; }
             else {
-                auto mer32_at = [&](uint32_t tt) -> FmerKey { return fmer_key(rd.bits64(tt)); };   // the 31-mer at base tt <= L-31 (common.h)
+                auto mer32_at = [&](uint32_t tt) -> FmerKey { return fmer_key<FMER_STRIDE, (FMER_STRIDE < 4)>(rd.bits64(tt)); };   // the 31-mer at base tt <= L-31 (common.h)
                 auto f32_absent = [&](const FmerKey& k, unsigned long long w) -> bool { return (w & k.mask) != k.mask; };
                 const uint32_t last = L - K, tmax = L - FMER;
                 auto probe3 = [&](uint32_t cur0, uint32_t e) -> uint32_t {
